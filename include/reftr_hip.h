@@ -159,6 +159,32 @@ int rt_small_wgrad_grouped(const rt_small_wgrad_job* jobs, int njobs, rt_stream_
 int rt_conv_wgrad_grouped(const rt_conv_wgrad_desc* descs, int n, float* workspace, int64_t workspace_bytes, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * rt_gconv / rt_gconv_wgrad — grouped 3x3 convolution: conv2 of the ResNeXt bottlenecks (torchvision Bottleneck with groups > 1,
+ * reached through models/modeling/backbone.py:112-125, which builds ANY torchvision ResNet by name: resnext50_32x4d,
+ * resnext101_32x8d, resnext101_64x4d).  FrozenBatchNorm2d folded as in rt_conv_gemm (scale into wgt, shift into `bias`).
+ * `groups` G splits the SC input channels into G groups of Cg = SC / G; output channel n reads group n / Cg only.
+ *
+ * rt_gconv reuses rt_conv_gemm_desc (same field meanings, same geometry in both directions):
+ *   transposed = 0  forward      : out[m, n] = act(sum_{tap, c} gather(src)[m, tap, g(n) * Cg + c] * wgt[n][tap][c] + bias[n]) (* gate)
+ *   transposed = 1  backward-data: src = dy, out = dx; the transposed gather of rt_conv_gemm, reading the FORWARD weight layout
+ *                   (no [C][T][N] copy); `gate` fuses the ReLU mask of the tensor whose gradient is produced
+ * wgt  bf16 [SC][3][3][Cg] (forward layout; torchvision's [Cout][Cg][3][3] channels-last)     out  bf16 and/or fp32 [M, N]
+ * supported: KH = KW = 3, N = SC (square groups), Cg in {4, 8, 16, 32, 64}, SC % max(Cg, 32) == 0, stride 1 | 2, dil > 1 only
+ *   at stride 1, act NONE | RELU, bias, gate (gate_scale); RT_ERR_UNSUPPORTED for res_*, preact, dtanh, out_preact, acc2_f32,
+ *   dropout, tile_hint != 0 and any other Cg / geometry.
+ *
+ * rt_gconv_wgrad reuses rt_conv_wgrad_desc:
+ *   dw[n][tap][c] (+)= scale[n] * sum_m dy[m, n] * gather(x)[m, tap, g(n) * Cg + c]       dw fp32 [N][3][3][Cg]
+ *   The M axis is split over the chip (`msplit`, 0 = auto); the split partials go to `workspace` (REQUIRED: at least
+ *   N * 9 * Cg floats; the split count is capped by its size) and one reduction launch applies scale, `overwrite`, the clip-norm
+ *   contribution (`sqacc`) and the bf16 twin (`g16`), as rt_conv_wgrad does.  RT_ERR_UNSUPPORTED for dbias, variant != 0
+ *   and the geometries rt_gconv refuses.
+ * Both enqueue kernels only (capture-safe: no host synchronisation, no allocation).
+ * ------------------------------------------------------------------------------------------ */
+int rt_gconv(const rt_conv_gemm_desc* d, int groups, rt_stream_t stream);
+int rt_gconv_wgrad(const rt_conv_wgrad_desc* d, int groups, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * rt_layernorm_fwd / rt_layernorm_bwd — nn.LayerNorm over the last axis, fp32 statistics, one wave per row.
  * Replaces: encoder/decoder norm1-3 and decoder.norm (models/modeling/transformer.py:157-158,217-219,
  * 176-180,243-251,131-138), BERT LayerNorms (eps 1e-12), the LayerNorms inside mlp_mapping

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2, 3
 _c_float_p = POINTER(c_float)
@@ -305,6 +305,8 @@ _SIGNATURES = {
     "rt_conv_gemm": (c_int, [POINTER(ConvGemmDesc), c_void_p]),
     "rt_conv_gemm_grouped": (c_int, [c_void_p, c_int, c_void_p]),
     "rt_conv_wgrad": (c_int, [POINTER(ConvWgradDesc), c_void_p]),
+    "rt_gconv": (c_int, [POINTER(ConvGemmDesc), c_int, c_void_p]),
+    "rt_gconv_wgrad": (c_int, [POINTER(ConvWgradDesc), c_int, c_void_p]),
     "rt_layernorm_fwd": (c_int, [POINTER(LayerNormDesc), c_void_p]),
     "rt_layernorm_bwd": (c_int, [POINTER(LayerNormBwdDesc), c_void_p]),
     "rt_groupnorm_fwd": (c_int, [POINTER(GroupNormDesc), c_void_p]),
@@ -668,6 +670,58 @@ def conv_wgrad(dy, x, dw, *, geom, scale=None, msplit=0, dbias=None, variant=0, 
                       _p(ws), WGRAD_WS_BYTES if ws is not None else 0, int(bool(overwrite)), int(dil), _sqacc(dw), _g16(dw))
     _timed("conv_wgrad", 2.0 * B * DH * DW * N * KH * KW * SC,
            lambda: _check(lib().rt_conv_wgrad(ctypes.byref(d), _stream()), "rt_conv_wgrad"), tag=("W",) + tuple(geom))
+    return dw
+
+
+def gconv(src, wgt, *, geom, groups, bias=None, gate=None, gate_scale=1.0, act=ACT_NONE, transposed=False,
+          out_bf16=True, out_f32=False, dil=1, **unsupported):
+    """Grouped 3x3 convolution (rt_gconv): out[B,DH,DW,N] = epilogue(grouped_conv(src[B,SH,SW,SC], wgt[SC,3,3,SC/groups])).
+
+    geom as in conv_gemm (transposed=True: backward-data, geom of the transposed problem, `wgt` still the FORWARD layout).
+    Fields the grouped kernel does not implement (res_*, preact, dropout, tile_hint, ...) are passed on and refused by the
+    library.  Returns (out_bf16 | None, out_f32 | None)."""
+    B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad = geom
+    _req(src, torch.bfloat16, "src"); _req(wgt, torch.bfloat16, "wgt"); _req(bias, torch.float32, "bias"); _req(gate, torch.bfloat16, "gate")
+    assert src.numel() == B * SH * SW * SC, (src.shape, geom)
+    cg = SC // groups if groups > 0 else 0
+    assert wgt.numel() == SC * KH * KW * cg, (wgt.shape, geom, groups)
+    M = B * DH * DW
+    ob = out_bf16 if torch.is_tensor(out_bf16) else (torch.empty((M, N), dtype=torch.bfloat16, device=src.device) if out_bf16 else None)
+    of = out_f32 if torch.is_tensor(out_f32) else (torch.empty((M, N), dtype=torch.float32, device=src.device) if out_f32 else None)
+    _req(ob, torch.bfloat16, "out_bf16"); _req(of, torch.float32, "out_f32")
+    assert (ob is None or ob.numel() == M * N) and (of is None or of.numel() == M * N)
+    d = ConvGemmDesc(_p(src), _p(wgt), _p(ob), _p(of), _p(bias), None, None, _p(gate), None, B, SH, SW, SC, DH, DW, N, KH, KW,
+                     stride, pad, 1 if transposed else 0, act, gate_scale, 0.0, 0, 0, None, None, 0, None, 0, None, int(dil))
+    keep = []
+    for k, v in unsupported.items():          # forwarded so that the library refuses them (no silent drop)
+        if k in ("res_f32", "res_bf16", "preact", "dtanh", "acc2_f32"):
+            if v is not None:
+                setattr(d, k, _p(v)); keep.append(v)
+        elif k in ("drop_p", "tile_hint", "res_first", "drop_shift"):
+            setattr(d, k, v)
+        else:
+            raise TypeError(f"gconv: unknown argument {k}")
+    spatial = B * (SH * SW if transposed else DH * DW)
+    flops = 2.0 * spatial * SC * KH * KW * cg
+    _timed("gconv", flops, lambda: _check(lib().rt_gconv(ctypes.byref(d), int(groups), _stream()), "rt_gconv"),
+           nbytes=2.0 * (B * SH * SW * SC + M * N) + 2.0 * wgt.numel())
+    return ob, of
+
+
+def gconv_wgrad(dy, x, dw, *, geom, groups, scale=None, msplit=0, overwrite=False, dil=1, dbias=None, variant=0):
+    """Grouped 3x3 weight gradient (rt_gconv_wgrad): dw[N,3,3,Cg] (fp32) += (overwrite: =) scale[n] * sum_m dy[m,n] *
+    gather(x)[m, (kh, kw, g(n) * Cg + c)].  The split partials use this stream's weight-gradient workspace."""
+    B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad = geom
+    _req(dy, torch.bfloat16, "dy"); _req(x, torch.bfloat16, "x"); _req(dw, torch.float32, "dw"); _req(scale, torch.float32, "scale")
+    _req(dbias, torch.float32, "dbias")
+    cg = SC // groups if groups > 0 else 0
+    assert dy.numel() == B * DH * DW * N and x.numel() == B * SH * SW * SC and dw.numel() == N * KH * KW * cg
+    ws = _wgrad_workspace(dy.device)
+    d = ConvWgradDesc(_p(dy), _p(x), _p(dw), _p(scale), B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad, msplit, _p(dbias), variant,
+                      _p(ws), WGRAD_WS_BYTES, int(bool(overwrite)), int(dil), _sqacc(dw), _g16(dw))
+    _timed("gconv_wgrad", 2.0 * B * DH * DW * N * KH * KW * cg,
+           lambda: _check(lib().rt_gconv_wgrad(ctypes.byref(d), int(groups), _stream()), "rt_gconv_wgrad"),
+           nbytes=2.0 * (B * DH * DW * N + B * SH * SW * SC) + 4.0 * dw.numel())
     return dw
 
 

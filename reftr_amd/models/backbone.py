@@ -1,9 +1,10 @@
 """ResNet-50/101 v1.5 body with FrozenBatchNorm folded into the convolutions — forward and hand-written
 backward over the HIP implicit-GEMM kernels (NHWC bf16 activations).
 
-Mirrors models/modeling/backbone.py:83-125 of the reference (torchvision resnet + FrozenBatchNorm2d
+Mirrors models/modeling/backbone.py:83-125 of the reference (torchvision resnet / resnext / wide_resnet + FrozenBatchNorm2d
 :43-80, conv1/layer1 frozen :87-89, pad-mask interpolation :107).  Every conv+BN(+ReLU)(+residual) is ONE
-rt_conv_gemm launch: BN scale is folded into the bf16 weight, BN shift is the epilogue bias.
+rt_conv_gemm launch: BN scale is folded into the bf16 weight, BN shift is the epilogue bias.  The grouped 3x3 of a ResNeXt
+bottleneck (groups > 1) is one rt_gconv launch per direction and one rt_gconv_wgrad for its weight gradient.
 
 Backward convention: every gradient tensor that flows between blocks is dL/d(pre-ReLU value) — the ReLU
 mask of a tensor is applied by the kernel that PRODUCES its gradient (`gate=` epilogue), so no separate
@@ -16,13 +17,19 @@ from . import layout as L
 
 
 class ConvSpec:
-    __slots__ = ("name", "bn", "cin", "cout", "k", "stride", "pad", "trainable", "dil")
+    __slots__ = ("name", "bn", "cin", "cout", "k", "stride", "pad", "trainable", "dil", "groups")
 
-    def __init__(self, name, bn, cin, cout, k, stride, trainable, dil=1):
+    def __init__(self, name, bn, cin, cout, k, stride, trainable, dil=1, groups=1):
         self.name, self.bn, self.cin, self.cout, self.k, self.stride = name, bn, cin, cout, k, stride
         self.dil = dil
+        self.groups = groups
         self.pad = (k // 2) * dil
         self.trainable = trainable
+
+    @property
+    def cg(self):
+        """Input channels per group: the C extent of the weight [cout][k*k][cg]."""
+        return self.cin // self.groups
 
 
 class BlockSpec:
@@ -40,8 +47,11 @@ class ResNetBody:
         # --dilation (torchvision replace_stride_with_dilation=[False, False, True], backbone.py:117-125): layer4's stride becomes a
         # dilation -- its first block runs at stride 1 with the PREVIOUS dilation (1), the following blocks dilate their 3x3 by 2
         dilate = bool(getattr(cfg, "dilation", False))
+        groups = int(getattr(cfg, "resnet_groups", 1))
+        wpg = int(getattr(cfg, "resnet_width_per_group", 64))
         for li, n in enumerate(cfg.resnet_layers):
             planes = 64 * 2 ** li
+            width = L.bottleneck_width(planes, groups, wpg)
             tr = li > 0 and getattr(cfg, "train_backbone", True)     # lr_backbone 0: nothing trains, nothing is saved for backward
             stage = []
             for bi in range(n):
@@ -51,9 +61,9 @@ class ResNetBody:
                 if dilate and li == 3:
                     s, dl = 1, (1 if bi == 0 else 2)
                 b = BlockSpec()
-                b.conv1 = ConvSpec(p + "conv1.weight", p + "bn1.", inpl, planes, 1, 1, tr)
-                b.conv2 = ConvSpec(p + "conv2.weight", p + "bn2.", planes, planes, 3, s, tr, dil=dl)
-                b.conv3 = ConvSpec(p + "conv3.weight", p + "bn3.", planes, planes * 4, 1, 1, tr)
+                b.conv1 = ConvSpec(p + "conv1.weight", p + "bn1.", inpl, width, 1, 1, tr)
+                b.conv2 = ConvSpec(p + "conv2.weight", p + "bn2.", width, width, 3, s, tr, dil=dl, groups=groups)
+                b.conv3 = ConvSpec(p + "conv3.weight", p + "bn3.", width, planes * 4, 1, 1, tr)
                 b.down = ConvSpec(p + "downsample.0.weight", p + "downsample.1.", inpl, planes * 4, 1, s, tr) if bi == 0 else None
                 b.trainable = tr
                 b.first_trainable = (li == 1 and bi == 0)     # its input (layer1 output) needs no gradient
@@ -67,7 +77,8 @@ class ResNetBody:
         self.fuse_stem = True             # frozen stem + max-pool as one launch (rt_stem_pool)
         self.batch = H.WgradBatch(workspace_mb=1024) if on_gpu else None      # conv weight gradients: grouped launches per stage
         self.wgs = H.SideStream(False)
-        self.W = {}      # bf16 operands: name -> [N][T][C]; name + '.t' -> [C][T][N]
+        self.gq = []     # grouped weight gradients of the current stage: launched with the stage's batch (same stream)
+        self.W = {}      # bf16 operands: name -> [N][T][C]; name + '.t' -> [C][T][N] (dense only: grouped kernels read [N][T][Cg] both ways)
         self.bn = {}     # bn prefix -> (scale, shift) fp32
         self.all_convs = [c for st in self.blocks for b in st for c in (b.conv1, b.conv2, b.conv3, b.down) if c is not None]
         for c in self.all_convs:
@@ -96,14 +107,14 @@ class ResNetBody:
         for c in self.all_convs:
             T = c.k * c.k
             if c.name not in self.W:
-                self.W[c.name] = torch.empty(c.cout, T, c.cin, dtype=torch.bfloat16, device=dev)
-                if c.trainable:
+                self.W[c.name] = torch.empty(c.cout, T, c.cg, dtype=torch.bfloat16, device=dev)
+                if c.trainable and c.groups == 1:
                     self.W[c.name + ".t"] = torch.empty(c.cin, T, c.cout, dtype=torch.bfloat16, device=dev)
         if full:       # the BN scale tensors were re-created: rebuild both job tables
             self._prep_all = H.WeightPrepBatch(dev)
             self._prep_train = H.WeightPrepBatch(dev)
             for c in self.all_convs:
-                args = (st.phys(c.name), c.cout, c.k * c.k, c.cin)
+                args = (st.phys(c.name), c.cout, c.k * c.k, c.cg)
                 kw = dict(scale=self.bn[c.bn][0], dst=self.W[c.name], dst_t=self.W.get(c.name + ".t"))
                 self._prep_all.add(*args, **kw)
                 if c.trainable:
@@ -118,6 +129,11 @@ class ResNetBody:
         Ho = (Hh + 2 * c.pad - c.dil * (c.k - 1) - 1) // c.stride + 1
         Wo = (Ww + 2 * c.pad - c.dil * (c.k - 1) - 1) // c.stride + 1
         geom = (B, Hh, Ww, c.cin, Ho, Wo, c.cout, c.k, c.k, c.stride, c.pad)
+        if c.groups > 1:
+            assert res is None
+            y, _ = H.gconv(x, self.W[c.name], geom=geom, groups=c.groups, bias=self.bn[c.bn][1],
+                           act=H.ACT_RELU if relu else H.ACT_NONE, dil=c.dil)
+            return y, (B, Ho, Wo), geom
         y, _ = H.conv_gemm(x, self.W[c.name], geom=geom, bias=self.bn[c.bn][1], res_bf16=res, res_first=True,
                            act=H.ACT_RELU if relu else H.ACT_NONE, dil=c.dil)
         return y, (B, Ho, Wo), geom
@@ -144,7 +160,7 @@ class ResNetBody:
                 if ready is not None and b.trainable:
                     torch.cuda.current_stream().wait_event(ready)
                     ready = None
-                if self.fuse_frozen and not b.trainable and b.conv1.cout == 64 and b.conv2.stride == 1 and (b.down is None or b.conv1.cin == 64):
+                if self.fuse_frozen and not b.trainable and b.conv1.cout == 64 and b.conv2.groups == 1 and b.conv2.stride == 1 and (b.down is None or b.conv1.cin == 64):
                     # frozen layer1 block: one launch, h1 / h2 never reach HBM (nothing of it is read by a backward)
                     Bn, Hh, Ww = shp
                     c1, c2, c3, cd = b.conv1, b.conv2, b.conv3, b.down
@@ -172,7 +188,14 @@ class ResNetBody:
     def _wgrad(self, g, x, c, geom):
         dw, sc = self.store.phys(c.name, grad=True), self.bn[c.bn][0]
         ow = self.store.claim(dw)
-        if self.batch is not None:
+        if c.groups > 1:
+            # its own launch, queued with the stage's batched dense weight gradients (same stream, same point of completion)
+            fn = lambda: H.gconv_wgrad(g, x, dw, geom=geom, groups=c.groups, scale=sc, overwrite=ow, dil=c.dil)     # noqa: E731
+            if self.batch is not None:
+                self.gq.append((fn, g, x))
+            else:
+                self.wg.run(fn, g, x)
+        elif self.batch is not None:
             self.batch.add_conv(g, x, dw, geom, scale=sc, overwrite=ow, dil=c.dil)
         else:
             self.wg.run(lambda: H.conv_wgrad(g, x, dw, geom=geom, scale=sc, overwrite=ow, dil=c.dil), g, x)
@@ -180,6 +203,10 @@ class ResNetBody:
     def _dgrad(self, g, c, geom, res=None, gate=None, res_f32=None):
         B, SH, SW, SC, DH, DW, N, KH, KW, s, p = geom
         geom_t = (B, DH, DW, N, SH, SW, SC, KH, KW, s, p)
+        if c.groups > 1:
+            assert res is None and res_f32 is None
+            y, _ = H.gconv(g, self.W[c.name], geom=geom_t, groups=c.groups, transposed=True, gate=gate, dil=c.dil)
+            return y
         y, _ = H.conv_gemm(g, self.W[c.name + ".t"], geom=geom_t, transposed=True, res_bf16=res, res_f32=res_f32, gate=gate, dil=c.dil)
         return y
 
@@ -197,6 +224,7 @@ class ResNetBody:
         try:
             yield from self._backward(saved, g_out, extra)
         finally:
+            self.gq = []
             self.wgs.join()
 
     def _backward(self, saved, g_out, extra):
@@ -213,7 +241,14 @@ class ResNetBody:
                 # end of a stage: its queued weight gradients go out together -- on the side stream when enabled, under the
                 # next stage's backward-data chain
                 alive = [t for k in self.batch.keep for t in k if t is not None]      # until the side stream is joined
-                self.wgs.run(self.batch.run, *alive)
+                gq, self.gq = self.gq, []
+                alive += [t for q in gq for t in q[1:]]
+
+                def stage_wgrads(gq=gq):
+                    self.batch.run()
+                    for q in gq:
+                        q[0]()
+                self.wgs.run(stage_wgrads, *alive)
             if b.down is not None:
                 yield b.stage_in + 2                    # layer number (4, 3, 2) whose gradients are all launched now
             if b.first_trainable:

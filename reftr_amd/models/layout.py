@@ -43,6 +43,8 @@ class ModelConfig:
     n_q: int = 1                       # num_queries_per_phrase
     aux_loss: bool = True
     resnet_layers: tuple = (3, 4, 6, 3)   # resnet50; resnet101 = (3, 4, 23, 3)
+    resnet_groups: int = 1                # torchvision Bottleneck `groups` (ResNeXt: 32 / 64): conv2 is a grouped 3x3
+    resnet_width_per_group: int = 64      # torchvision `width_per_group` (ResNeXt 4 / 8, Wide ResNet 128)
     masks: bool = False                   # RefTRSeg: RES head (bbox_attention + mask_head), single phrase, no aux loss
     pos_learned: bool = False             # --position_embedding learned: PositionEmbeddingLearned (position_encoding.py:59-84)
     train_backbone: bool = True           # False: --lr_backbone 0 freezes the whole ResNet (backbone.py:87-89,150)
@@ -70,20 +72,27 @@ def _bn(pfx, c, out):
         out.append((pfx + k, (c,), "buffer"))
 
 
-def resnet_table(pfx, layers, train=True):
+def bottleneck_width(planes, groups=1, width_per_group=64):
+    """torchvision Bottleneck: the channel count of conv1 / conv2 (conv3 always outputs planes * 4)."""
+    return int(planes * (width_per_group / 64.0)) * groups
+
+
+def resnet_table(pfx, layers, train=True, groups=1, width_per_group=64):
     """Returns [(name, shape, kind)], kind in {'param', 'frozen', 'buffer'} (backbone.py:87-89: conv1 and
-    layer1 never train; FrozenBatchNorm2d tensors are buffers, backbone.py:52-57)."""
+    layer1 never train; FrozenBatchNorm2d tensors are buffers, backbone.py:52-57).  groups / width_per_group: torchvision's
+    ResNeXt / Wide ResNet bottlenecks (conv2 weight [width, width // groups, 3, 3])."""
     t = [(pfx + "conv1.weight", (64, 3, 7, 7), "frozen")]
     _bn(pfx + "bn1.", 64, t)
     inpl = 64
     for li, n in enumerate(layers):
         planes = 64 * 2 ** li
+        w = bottleneck_width(planes, groups, width_per_group)
         kind = "frozen" if (li == 0 or not train) else "param"
         for bi in range(n):
             p = f"{pfx}layer{li + 1}.{bi}."
-            t.append((p + "conv1.weight", (planes, inpl, 1, 1), kind)); _bn(p + "bn1.", planes, t)
-            t.append((p + "conv2.weight", (planes, planes, 3, 3), kind)); _bn(p + "bn2.", planes, t)
-            t.append((p + "conv3.weight", (planes * 4, planes, 1, 1), kind)); _bn(p + "bn3.", planes * 4, t)
+            t.append((p + "conv1.weight", (w, inpl, 1, 1), kind)); _bn(p + "bn1.", w, t)
+            t.append((p + "conv2.weight", (w, w // groups, 3, 3), kind)); _bn(p + "bn2.", w, t)
+            t.append((p + "conv3.weight", (planes * 4, w, 1, 1), kind)); _bn(p + "bn3.", planes * 4, t)
             if bi == 0:
                 t.append((p + "downsample.0.weight", (planes * 4, inpl, 1, 1), kind)); _bn(p + "downsample.1.", planes * 4, t)
             inpl = planes * 4
@@ -221,7 +230,7 @@ def phys_dims(cfg: ModelConfig):
 def full_table(cfg: ModelConfig):
     """All tensors of the model.  Trainable ones are listed group by group (main, backbone, bert) in the
     order they are laid out in the flat parameter buffer."""
-    return main_table(cfg) + (seg_table(cfg) if cfg.masks else []) + (cem_table(cfg) if cfg.masks and cfg.cem else []) + resnet_table("img_backbone.0.body.", cfg.resnet_layers, cfg.train_backbone) + bert_table("lang_backbone.", cfg.bert)
+    return main_table(cfg) + (seg_table(cfg) if cfg.masks else []) + (cem_table(cfg) if cfg.masks and cfg.cem else []) + resnet_table("img_backbone.0.body.", cfg.resnet_layers, cfg.train_backbone, cfg.resnet_groups, cfg.resnet_width_per_group) + bert_table("lang_backbone.", cfg.bert)
 
 
 def reference_param_order(cfg: ModelConfig):

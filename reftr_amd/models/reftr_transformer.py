@@ -176,8 +176,8 @@ class RefTR(nn.Module):
         jobs = [(off(l.w32), l.N, 1, l.K, None, l.W, l.WT) for l in self.net.lins.values()]
         for c in self.body.all_convs:
             if c.trainable:
-                jobs.append((off(st.phys(c.name)), c.cout, c.k * c.k, c.cin, self.body.bn[c.bn][0], self.body.W[c.name],
-                             self.body.W[c.name + ".t"]))
+                jobs.append((off(st.phys(c.name)), c.cout, c.k * c.k, c.cg, self.body.bn[c.bn][0], self.body.W[c.name],
+                             self.body.W.get(c.name + ".t")))         # grouped convolutions have no transposed copy
         if self.seg is not None:
             jobs += [(off(c.w32), c.cop, c.k * c.k, c.cip, None, c.W, c.WT) for c in self.seg.convs.values()]
         # large tables that feed no GEMM (BERT's word / position embeddings: 24 M parameters) take the same tiled pass without
@@ -1006,6 +1006,19 @@ class RefTR(nn.Module):
         H.mark("backward join (language branch in)")
 
 
+# torchvision name -> (blocks per stage, groups, width_per_group) of its bottleneck ResNet (models/modeling/backbone.py:112-125 builds
+# the backbone by name with getattr(torchvision.models, args.backbone)); stage outputs are 256 / 512 / 1024 / 2048 channels for all
+BACKBONES = {
+    "resnet50": ((3, 4, 6, 3), 1, 64),
+    "resnet101": ((3, 4, 23, 3), 1, 64),
+    "resnext50_32x4d": ((3, 4, 6, 3), 32, 4),
+    "resnext101_32x8d": ((3, 4, 23, 3), 32, 8),
+    "resnext101_64x4d": ((3, 4, 23, 3), 64, 4),
+    "wide_resnet50_2": ((3, 4, 6, 3), 1, 128),
+    "wide_resnet101_2": ((3, 4, 23, 3), 1, 128),
+}
+
+
 def build_config(args):
     if int(getattr(args, "num_feature_levels", 1)) != 1:
         raise NotImplementedError("num_feature_levels > 1: the reference's own forward raises for every such value "
@@ -1025,9 +1038,10 @@ def build_config(args):
         raise NotImplementedError("--ablation cem_loss with hidden_dim != 256: the CEM kernels (rt_cem_fwd / rt_cem_bwd) are built for "
                                   "hidden_dim // 16 == 16 channels (every reference config uses hidden_dim 256)")
     backbone = str(getattr(args, "backbone", "resnet50"))
-    if backbone not in ("resnet50", "resnet101"):
+    if backbone not in BACKBONES:
         raise NotImplementedError(f"--backbone {backbone}: the reference takes any torchvision ResNet name (models/modeling/backbone.py:"
-                                  "119); this build has the bottleneck stacks of resnet50 (3, 4, 6, 3) and resnet101 (3, 4, 23, 3) only")
+                                  "119); this build has the bottleneck stacks of " + ", ".join(BACKBONES) + " only")
+    layers, groups, wpg = BACKBONES[backbone]
     bert_name = str(getattr(args, "bert_model", "bert-base-uncased"))
     if "base" not in bert_name.split("-"):
         raise NotImplementedError(f"--bert_model {bert_name}: the reference reads hidden_size from the checkpoint's config "
@@ -1035,7 +1049,6 @@ def build_config(args):
                                   "of bert-base-* / roberta-base only")
     # models/reftr_transformer.py:315-318: RobertaModel when args.bert_model starts with 'roberta', BertModel otherwise
     bc = L.roberta_config() if str(getattr(args, "bert_model", "bert-base-uncased")).split("-")[0] == "roberta" else L.BertConfig()
-    layers = (3, 4, 23, 3) if getattr(args, "backbone", "resnet50") == "resnet101" else (3, 4, 6, 3)
     for k in ("bert_layers",):
         if hasattr(args, k):
             bc.layers = getattr(args, k)
@@ -1043,6 +1056,7 @@ def build_config(args):
                          dec_layers=0 if getattr(args, "no_decoder", False) else args.dec_layers,
                          ffn=args.dim_feedforward, dropout=args.dropout, max_lang_seq=args.max_lang_seq,
                          n_q=args.num_queries_per_phrase, aux_loss=args.aux_loss, resnet_layers=layers, bert=bc,
+                         resnet_groups=groups, resnet_width_per_group=wpg,
                          masks=bool(getattr(args, "masks", False)),
                          # lr_backbone <= 0 freezes the whole ResNet (train_backbone = False, models/modeling/backbone.py:87-89,150):
                          # its parameters leave the optimizer and the clip norm, its backward is not run
