@@ -109,6 +109,28 @@ __device__ __forceinline__ int rt_xcd_remap(int b, int n, int xcd_on) {
 __device__ __forceinline__ void rt_sq_add(float* slots, unsigned who, float v) {
     atomicAdd(slots + (size_t)(who & (RT_SQ_SLOTS - 1)) * RT_SQ_STRIDE, v);
 }
+__device__ __forceinline__ float rt_hsum(float v) { return v; }
+__device__ __forceinline__ float rt_hsum(f32x4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
+__device__ __forceinline__ void rt_store_bf16(bf16_t* p, float v) { *p = (bf16_t)v; }
+__device__ __forceinline__ void rt_store_bf16(bf16_t* p, f32x4 v) {
+    *reinterpret_cast<bf16x4*>(p) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+}
+// The commit step of a finished weight-gradient piece (T = float or f32x4).  `a` is the reduced value, ALREADY multiplied by
+// scale[n]; `old` what *o holds (read only when `accumulate`: a kernel that keeps several pieces' loads in flight reads it itself).
+// Overwrites or accumulates *o, writes the bf16 exchange twin of the FINAL value (`twin` may be null) and returns the piece's
+// |after|^2 - |before|^2 for the accumulator slots: (old + a)^2 - old^2 = a (2 old + a).
+template <class T>
+__device__ __forceinline__ float rt_wg_commit(T a, T old, T* o, bf16_t* twin, bool accumulate) {
+    T d = a * a;
+    if (accumulate) { d = a * (old + old + a); a = old + a; }
+    *o = a;
+    if (twin) rt_store_bf16(twin, a);
+    return rt_hsum(d);
+}
+template <class T>
+__device__ __forceinline__ float rt_wg_commit(T a, T* o, bf16_t* twin, bool accumulate) {
+    return rt_wg_commit(a, accumulate ? *o : a, o, twin, accumulate);
+}
 // sign * |buf|^2 of up to 32 fp32 buffers into the slots (the producers without an in-kernel contribution: a pass with sign -1
 // in front of an accumulating launch, +1 behind every launch); rt_optim.hip
 int rt_sq_pass(float* const* bufs, const long long* counts, const float* signs, int n, float* slots, hipStream_t s);

@@ -219,11 +219,7 @@ __global__ __launch_bounds__(256) void gwgrad_finish_kernel(const GwgradFinish f
         float s = 0.f;
         for (int k = 0; k < f.nsplit; ++k) s += f.part[(size_t)k * f.E + i];
         if (f.scale) s *= f.scale[i / f.per_n];
-        float fin;
-        if (f.overwrite) { fin = s; ss = s * s; }
-        else { const float old = f.dw[i]; fin = old + s; ss = s * (old + old + s); }
-        f.dw[i] = fin;
-        if (f.g16) f.g16[i] = (bf16_t)fin;
+        ss = rt_wg_commit(s, f.dw + i, f.g16 ? f.g16 + i : nullptr, !f.overwrite);
     }
     if (f.sqacc) {
         ss = rt_block_sum(ss, sm);

@@ -506,23 +506,26 @@ __global__ __launch_bounds__(256, MINB) void conv_wgrad_dma_grouped_kernel(const
 struct ReduceGroup { const float* part[24]; float* dw[24]; const float* scale[24]; int out_elems[24], row_elems[24], nsplit[24], overwrite[24], first[25]; int n; };
 
 // dw[i] += scale[i / row_elems] * sum_s part[s][i].  A workgroup owns 64 float4 columns; its 4 thread rows take the
-// splits round-robin (4 independent loads in flight each) and meet in LDS.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
-                                                           const float* __restrict__ scale, int out_elems, int row_elems, int nsplit, int overwrite) {
+// splits round-robin (4 independent loads in flight each) and meet in LDS.  UNROLL: the single launch sums 16 splits per trip
+// (another summation order than the plain loop of the grouped launch: each keeps its own).
+template <bool UNROLL>
+__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ part, float* __restrict__ dw, const float* __restrict__ scale,
+                                                  int out_elems, int row_elems, int nsplit, int overwrite, int block) {
     __shared__ f32x4 red[3][64];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int i = (blockIdx.x * 64 + tx) * 4;
+    const int i = (block * 64 + tx) * 4;
     const bool ok = i < out_elems;
     f32x4 a = {0.f, 0.f, 0.f, 0.f};
     if (ok) {
         int sidx = ty;
-        for (; sidx + 12 < nsplit; sidx += 16) {
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(part + (size_t)sidx * out_elems + i);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(part + (size_t)(sidx + 4) * out_elems + i);
-            const f32x4 v2 = *reinterpret_cast<const f32x4*>(part + (size_t)(sidx + 8) * out_elems + i);
-            const f32x4 v3 = *reinterpret_cast<const f32x4*>(part + (size_t)(sidx + 12) * out_elems + i);
-            a += (v0 + v1) + (v2 + v3);
-        }
+        if (UNROLL)
+            for (; sidx + 12 < nsplit; sidx += 16) {
+                const f32x4 v0 = *reinterpret_cast<const f32x4*>(part + (size_t)sidx * out_elems + i);
+                const f32x4 v1 = *reinterpret_cast<const f32x4*>(part + (size_t)(sidx + 4) * out_elems + i);
+                const f32x4 v2 = *reinterpret_cast<const f32x4*>(part + (size_t)(sidx + 8) * out_elems + i);
+                const f32x4 v3 = *reinterpret_cast<const f32x4*>(part + (size_t)(sidx + 12) * out_elems + i);
+                a += (v0 + v1) + (v2 + v3);
+            }
         for (; sidx < nsplit; sidx += 4) a += *reinterpret_cast<const f32x4*>(part + (size_t)sidx * out_elems + i);
     }
     if (ty) red[ty - 1][tx] = a;
@@ -530,30 +533,20 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     if (ty || !ok) return;
     a += red[0][tx] + red[1][tx] + red[2][tx];
     if (scale) a *= scale[i / row_elems];
-    f32x4* o = reinterpret_cast<f32x4*>(dw + i);
-    *o = overwrite ? a : *o + a;
+    rt_wg_commit(a, reinterpret_cast<f32x4*>(dw + i), nullptr, !overwrite);      // (norm and twin: sq_account / twin_account)
+}
+
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
+                                                           const float* __restrict__ scale, int out_elems, int row_elems, int nsplit, int overwrite) {
+    wgrad_reduce_body<true>(part, dw, scale, out_elems, row_elems, nsplit, overwrite, blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const ReduceGroup g) {
-    __shared__ f32x4 red[3][64];
     int lo = 0, hi = g.n - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (g.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
     lo = __builtin_amdgcn_readfirstlane(lo);
-    const float* part = g.part[lo]; float* dw = g.dw[lo]; const float* scale = g.scale[lo];
-    const int out_elems = g.out_elems[lo], row_elems = g.row_elems[lo], nsplit = g.nsplit[lo];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int i = (((int)blockIdx.x - g.first[lo]) * 64 + tx) * 4;
-    const bool ok = i < out_elems;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-    if (ok)
-        for (int sidx = ty; sidx < nsplit; sidx += 4) a += *reinterpret_cast<const f32x4*>(part + (size_t)sidx * out_elems + i);
-    if (ty) red[ty - 1][tx] = a;
-    __syncthreads();
-    if (ty || !ok) return;
-    a += red[0][tx] + red[1][tx] + red[2][tx];
-    if (scale) a *= scale[i / row_elems];
-    f32x4* o = reinterpret_cast<f32x4*>(dw + i);
-    *o = g.overwrite[lo] ? a : *o + a;
+    wgrad_reduce_body<false>(g.part[lo], g.dw[lo], g.scale[lo], g.out_elems[lo], g.row_elems[lo], g.nsplit[lo], g.overwrite[lo],
+                             (int)blockIdx.x - g.first[lo]);
 }
 
 // M <= 16 rows (decoder-side Linears): plain outer-product accumulation, one thread per (n, 4 k's)
@@ -615,18 +608,8 @@ __global__ __launch_bounds__(256) void small_m_wgrad_grouped_kernel(const SmallJ
 #pragma unroll
             for (int r = 0; r < 4; ++r) a[r] += gv[m] * (float)xv[m][r];
         }
-        f32x4* o = reinterpret_cast<f32x4*>(q.dw + (size_t)n * q.K + kk);
-        f32x4 fin;
-        if (q.overwrite) {
-            const f32x4 d = a * a; ss = (d[0] + d[1]) + (d[2] + d[3]);
-            fin = a;
-        } else {
-            const f32x4 old = *o;
-            const f32x4 d = a * (old + old + a); ss = (d[0] + d[1]) + (d[2] + d[3]);
-            fin = old + a;
-        }
-        *o = fin;
-        if (q.g16) *reinterpret_cast<bf16x4*>((bf16_t*)q.g16 + (size_t)n * q.K + kk) = bf16x4{(bf16_t)fin[0], (bf16_t)fin[1], (bf16_t)fin[2], (bf16_t)fin[3]};
+        const size_t e = (size_t)n * q.K + kk;
+        ss = rt_wg_commit(a, reinterpret_cast<f32x4*>(q.dw + e), q.g16 ? (bf16_t*)q.g16 + e : nullptr, !q.overwrite);
         if (q.dbias && kk == 0) q.dbias[n] += gs;
     }
     if (q.sqacc) {                           // uniform per workgroup: a workgroup belongs to one job
@@ -642,6 +625,29 @@ static int wg_clear_for_atomics(WgradArgs& a, hipStream_t s) {
     const hipError_t e = rt_zero_f32(a.dw, n, s);
     a.overwrite = 0;
     return e == hipSuccess ? RT_OK : (int)e;
+}
+
+// cuts the row chunks into (at most) msplit splits without an empty one: sets a.chunks_per_block, returns the split count
+static int wg_set_splits(WgradArgs& a, int total_chunks, int msplit) {
+    if (msplit > total_chunks) msplit = total_chunks;
+    if (msplit < 1) msplit = 1;
+    a.chunks_per_block = (total_chunks + msplit - 1) / msplit;
+    return (total_chunks + a.chunks_per_block - 1) / a.chunks_per_block;
+}
+
+// The split rule of the first-generation DMA kernel (single and grouped launch) when the caller leaves msplit to the library
+static int wg_dma_auto_split(const WgradArgs& a, long long base_blocks, int total_chunks, int CR) {
+    static const int target = RT_TUNE("REFTR_WG_TARGET", 512);
+    // each split costs one more partial tile through the workspace: small outputs take >= 256-row splits, larger
+    // ones >= 512 (benchmarks/wgrad_probe.py)
+    static const int minrows_env = RT_TUNE("REFTR_WG_MINROWS", 0);
+    const int minrows = minrows_env ? minrows_env : ((long long)a.N * a.KH * a.KW * a.SC * 4 <= (512 << 10) ? 256 : 512);
+    long long want = (target + base_blocks - 1) / base_blocks;
+    long long maxs = (long long)total_chunks * CR / minrows;
+    if (maxs < 1) maxs = 1;
+    if (want > maxs) want = maxs;
+    if (want > total_chunks) want = total_chunks;
+    return want < 1 ? 1 : (int)want;
 }
 
 template <int BN, int BC>
@@ -661,10 +667,7 @@ int launch_wgrad(WgradArgs a, int msplit, hipStream_t s) {
         if (want < 1) want = 1;
         msplit = (int)want;
     }
-    if (msplit > total_chunks) msplit = total_chunks;
-    if (msplit < 1) msplit = 1;
-    a.chunks_per_block = (total_chunks + msplit - 1) / msplit;
-    const int gy = (total_chunks + a.chunks_per_block - 1) / a.chunks_per_block;
+    const int gy = wg_set_splits(a, total_chunks, msplit);
     constexpr size_t smem = 2 * (size_t)(32 * (BN * 2 + 32) + 32 * (BC * 2 + 32));
     const dim3 grid((unsigned)base_blocks, (unsigned)gy), block(256);
     const bool simple = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0);
@@ -685,28 +688,15 @@ int launch_wgrad_dma(WgradArgs a, int msplit, float* ws, long long ws_bytes, hip
     const int taps = a.KH * a.KW;
     const int total_chunks = (a.M + CR - 1) / CR;
     const long long base_blocks = (long long)nt * a.c_tiles * taps;
-    if (msplit <= 0) {
-        static const int target = RT_TUNE("REFTR_WG_TARGET", 512);
-        // each split costs one more partial tile through the workspace: small outputs take >= 256-row splits, larger
-        // ones >= 512 (benchmarks/wgrad_probe.py)
-        static const int minrows_env = RT_TUNE("REFTR_WG_MINROWS", 0);
-        const int minrows = minrows_env ? minrows_env : ((long long)a.N * taps * a.SC * 4 <= (512 << 10) ? 256 : 512);
-        long long want = (target + base_blocks - 1) / base_blocks;
-        long long maxs = (long long)total_chunks * CR / minrows;
-        if (maxs < 1) maxs = 1;
-        if (want > maxs) want = maxs;
-        if (want < 1) want = 1;
-        msplit = (int)want;
-    }
-    if (msplit > total_chunks) msplit = total_chunks;
-    if (msplit < 1) msplit = 1;
     const long long out_elems = (long long)a.N * taps * a.SC;
-    if (auto_split && ws && msplit > 1) {           // keep the partials inside the caller's workspace
-        const long long fit = ws_bytes / (out_elems * 4);
-        if (fit < msplit) msplit = fit >= 2 ? (int)fit : msplit;
+    if (auto_split) {
+        msplit = wg_dma_auto_split(a, base_blocks, total_chunks, CR);
+        if (ws && msplit > 1) {                     // keep the partials inside the caller's workspace
+            const long long fit = ws_bytes / (out_elems * 4);
+            if (fit < msplit) msplit = fit >= 2 ? (int)fit : msplit;
+        }
     }
-    a.chunks_per_block = (total_chunks + msplit - 1) / msplit;
-    const int gy = (total_chunks + a.chunks_per_block - 1) / a.chunks_per_block;
+    const int gy = wg_set_splits(a, total_chunks, msplit);
     const bool use_ws = ws && gy > 1 && (long long)gy * out_elems * 4 <= ws_bytes && (out_elems & 3) == 0;
     a.part = use_ws ? ws : nullptr; a.out_elems = (int)out_elems;
     if (!use_ws && gy > 1) { const int zrc = wg_clear_for_atomics(a, s); if (zrc != RT_OK) return zrc; }
@@ -740,6 +730,23 @@ static int w2_enabled() {
     static const int e = RT_TUNE("REFTR_WG2", 1);
     return e;
 }
+
+// Which kernel family serves a descriptor.  variant: 0 = the library's choice, 9 = register-staged kernel, 1..5 = pinned 128x128
+// DMA staging shapes of the first generation.
+enum WgRoute { WG_SMALL_M, WG_V2, WG_DMA, WG_REG };
+static int wg_variant(const rt_conv_wgrad_desc& d) {
+    static const int wgv_env = RT_TUNE("REFTR_WGV", 0);
+    return d.variant > 0 ? d.variant : wgv_env;
+}
+static WgRoute wg_route(const rt_conv_wgrad_desc& d) {
+    const long long M = (long long)d.B * d.DH * d.DW;
+    if (M <= 16 && d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0 && (d.SC & 3) == 0) return WG_SMALL_M;
+    if (w2_enabled() && rt_w2_eligible(d) && !RT_TUNE_SET("REFTR_WGV")) return WG_V2;
+    return wg_variant(d) != 9 && (d.N & 7) == 0 ? WG_DMA : WG_REG;
+}
+// Does the route add its share of the clip norm (sqacc) and write the bf16 twin (g16) in its own kernels?  The others are
+// bracketed by the passes of wg_with_passes.
+static bool wg_self_accounts(WgRoute r) { return r == WG_V2; }
 
 // The Linear weight gradients a grouped launch accepts: plain [M,N]^T [M,K] products on the 128x128 DMA kernel.
 static bool groupable(const rt_conv_wgrad_desc& d) {
@@ -796,38 +803,36 @@ static int twin_account(const rt_conv_wgrad_desc* descs, int n, hipStream_t s) {
     return RT_OK;
 }
 
+template <class Launch>
+static int wg_with_passes(const rt_conv_wgrad_desc* descs, int n, hipStream_t s, Launch launch) {
+    int rc = sq_account(descs, n, false, s);
+    if (rc == RT_OK) rc = launch();
+    if (rc == RT_OK) rc = sq_account(descs, n, true, s);
+    if (rc == RT_OK) rc = twin_account(descs, n, s);
+    return rc;
+}
+
 extern "C" int rt_conv_wgrad_grouped(const rt_conv_wgrad_desc* descs, int n, float* workspace, int64_t workspace_bytes,
                                      rt_stream_t stream) {
     if (!descs || n <= 0) return RT_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
-    if (w2_enabled()) {
-        // second generation: every eligible problem of the group (1x1 / 3x3 convolutions and Linears alike) shares the grouped
-        // v2 launches and their group-level split policy; the rest (ragged channel counts, pinned variants) goes on below
-        static int idx[4096];
-        static rt_conv_wgrad_desc rest[4096];
-        int m = 0, nr = 0;
-        for (int i = 0; i < n && i < 4096; ++i) {
-            if (!descs[i].dy || !descs[i].x || !descs[i].dw) return RT_ERR_BADARG;
-            if (rt_w2_eligible(descs[i])) idx[m++] = i; else rest[nr++] = descs[i];
-        }
-        if (n > 4096) return RT_ERR_UNSUPPORTED;
-        if (m > 0) {
-            const int rc = rt_w2_run(descs, idx, m, workspace, workspace ? (long long)workspace_bytes : 0, s);
-            if (rc != RT_OK) return rc;
-        }
-        // (the v2 launches above have consumed the workspace; the first-generation group below re-uses it -- same stream, in order)
-        if (nr == 0) return RT_OK;
-        int rc = sq_account(rest, nr, false, s);
-        if (rc == RT_OK) rc = wgrad_grouped_v1(rest, nr, workspace, workspace_bytes, stream);
-        if (rc == RT_OK) rc = sq_account(rest, nr, true, s);
-        if (rc == RT_OK) rc = twin_account(rest, nr, s);
-        return rc;
+    if (n > 4096) return RT_ERR_UNSUPPORTED;
+    // second generation: every eligible problem of the group (1x1 / 3x3 convolutions and Linears alike) shares the grouped
+    // v2 launches and their group-level split policy; the rest (ragged channel counts, pinned variants, few rows) goes on below
+    static int idx[4096];
+    static rt_conv_wgrad_desc rest[4096];
+    int m = 0, nr = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!descs[i].dy || !descs[i].x || !descs[i].dw) return RT_ERR_BADARG;
+        if (wg_self_accounts(wg_route(descs[i]))) idx[m++] = i; else rest[nr++] = descs[i];
     }
-    int rc = sq_account(descs, n, false, s);
-    if (rc == RT_OK) rc = wgrad_grouped_v1(descs, n, workspace, workspace_bytes, stream);
-    if (rc == RT_OK) rc = sq_account(descs, n, true, s);
-    if (rc == RT_OK) rc = twin_account(descs, n, s);
-    return rc;
+    if (m > 0) {
+        const int rc = rt_w2_run(descs, idx, m, workspace, workspace ? (long long)workspace_bytes : 0, s);
+        if (rc != RT_OK) return rc;
+    }
+    // (the v2 launches above have consumed the workspace; the first-generation group below re-uses it -- same stream, in order)
+    if (nr == 0) return RT_OK;
+    return wg_with_passes(rest, nr, s, [&] { return wgrad_grouped_v1(rest, nr, workspace, workspace_bytes, stream); });
 }
 
 static int wgrad_grouped_v1(const rt_conv_wgrad_desc* descs, int n, float* workspace, int64_t workspace_bytes, rt_stream_t stream) {
@@ -862,21 +867,11 @@ static int wgrad_grouped_v1(const rt_conv_wgrad_desc* descs, int n, float* works
         WgradArgs a;
         const int rc = fill_wgrad_args(&d, a);
         if (rc != RT_OK) return rc;
-        // same split rule as the single launch (launch_wgrad_dma)
-        const int nt = (a.N + BN - 1) / BN;
         a.c_tiles = (a.SC + BC - 1) / BC;
         const int total_chunks = (a.M + CR - 1) / CR;
-        const long long base_blocks = (long long)nt * a.c_tiles;
+        const long long base_blocks = (long long)((a.N + BN - 1) / BN) * a.c_tiles;
         const long long out_elems = (long long)a.N * a.SC;
-        const int minrows = out_elems * 4 <= (512 << 10) ? 256 : 512;
-        static const int gtarget = RT_TUNE("REFTR_WG_TARGET", 512);
-        long long want = (gtarget + base_blocks - 1) / base_blocks, maxs = (long long)total_chunks * CR / minrows;
-        if (maxs < 1) maxs = 1;
-        if (want > maxs) want = maxs;
-        int msplit = (int)(want < 1 ? 1 : want);
-        if (msplit > total_chunks) msplit = total_chunks;
-        a.chunks_per_block = (total_chunks + msplit - 1) / msplit;
-        const int gy = (total_chunks + a.chunks_per_block - 1) / a.chunks_per_block;
+        const int gy = wg_set_splits(a, total_chunks, wg_dma_auto_split(a, base_blocks, total_chunks, CR));
         const long long need = gy > 1 ? (long long)gy * out_elems * 4 : 0;
         if (g.n == 24 || (need > 0 && workspace && ws_off + need > workspace_bytes && g.n > 0)) {
             const int frc = flush();
@@ -922,16 +917,8 @@ static int fill_wgrad_args(const rt_conv_wgrad_desc* d, WgradArgs& a) {
 
 extern "C" int rt_conv_wgrad(const rt_conv_wgrad_desc* d, rt_stream_t stream) {
     if (!d) return RT_ERR_BADARG;
-    if (!d->sqacc && !d->g16) return conv_wgrad_impl(d, stream);
-    const long long M = (long long)d->B * d->DH * d->DW;
-    const bool v2 = w2_enabled() && rt_w2_eligible(*d) && !RT_TUNE_SET("REFTR_WGV") &&
-                    !(M <= 16 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && (d->SC & 3) == 0);
-    if (v2) return conv_wgrad_impl(d, stream);           // the second-generation kernels account in their epilogues
-    int rc = sq_account(d, 1, false, (hipStream_t)stream);
-    if (rc == RT_OK) rc = conv_wgrad_impl(d, stream);
-    if (rc == RT_OK) rc = sq_account(d, 1, true, (hipStream_t)stream);
-    if (rc == RT_OK) rc = twin_account(d, 1, (hipStream_t)stream);
-    return rc;
+    if (wg_self_accounts(wg_route(*d))) return conv_wgrad_impl(d, stream);
+    return wg_with_passes(d, 1, (hipStream_t)stream, [&] { return conv_wgrad_impl(d, stream); });
 }
 
 static int conv_wgrad_impl(const rt_conv_wgrad_desc* d, rt_stream_t stream) {
@@ -939,26 +926,24 @@ static int conv_wgrad_impl(const rt_conv_wgrad_desc* d, rt_stream_t stream) {
     const int frc = fill_wgrad_args(d, a);
     if (frc != RT_OK) return frc;
     hipStream_t s = (hipStream_t)stream;
-    if (a.M <= 16 && a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && (a.SC & 3) == 0) {
+    const WgRoute route = wg_route(*d);
+    if (route == WG_SMALL_M) {
         const size_t total = (size_t)a.N * (a.SC >> 2);
         int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(small_m_wgrad_kernel, dim3(blocks), dim3(256), 0, s, a.dy, a.x, a.dw, a.scale, a.dbias, a.M, a.N, a.SC, a.overwrite);
         RT_CHECK_LAUNCH();
         return RT_OK;
     }
-    if (w2_enabled() && rt_w2_eligible(*d) && !RT_TUNE_SET("REFTR_WGV")) {       // a group of one
+    if (route == WG_V2) {                                  // a group of one
         const int zero = 0;
         return rt_w2_run(d, &zero, 1, d->workspace, d->workspace ? (long long)d->workspace_bytes : 0, s);
     }
-    // variant: 0 = LDS-DMA kernels (default), 9 = register-staged kernel, 1..5 = pinned 128x128 DMA staging shapes
-    static const int wgv_env = RT_TUNE("REFTR_WGV", 0);
-    const int wgv = d->variant > 0 ? d->variant : wgv_env;
     float* ws = d->workspace; long long wsb = d->workspace ? d->workspace_bytes : 0;
     static const int no_ws = RT_TUNE("REFTR_WG_NOWS", 0);
     if (no_ws) { ws = nullptr; wsb = 0; }
-    if (wgv != 9 && (a.N & 7) == 0) {
+    if (route == WG_DMA) {
         if (a.N >= 128 && a.SC >= 128) {
-            switch (wgv) {
+            switch (wg_variant(*d)) {
                 case 1: return launch_wgrad_dma<128, 128, 64, 2, 2>(a, d->msplit, ws, wsb, s);
                 case 2: return launch_wgrad_dma<128, 128, 32, 4, 2>(a, d->msplit, ws, wsb, s);
                 case 3: return launch_wgrad_dma<128, 128, 64, 3, 2>(a, d->msplit, ws, wsb, s);

@@ -425,27 +425,16 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
                 o[i] = dst + ((size_t)(ok[i] ? n : 0) * taps + otap) * p.SC + (ok[i] ? c : 0);
                 if (direct && p.scale) v[i] *= p.scale[ok[i] ? n : 0];
             }
-            if (direct && p.accumulate) {
+            if (!direct) {                   // a split's partial tile: the reduction commits
 #pragma unroll
-                for (int i = 0; i < NB; ++i) old[i] = *reinterpret_cast<const f32x4*>(o[i]);
-                if (p.sqacc) {               // (a + b)^2 - a^2 = b (2a + b)
-#pragma unroll
-                    for (int i = 0; i < NB; ++i) if (ok[i]) { const f32x4 d = v[i] * (old[i] + old[i] + v[i]); ss += (d[0] + d[1]) + (d[2] + d[3]); }
-                }
-#pragma unroll
-                for (int i = 0; i < NB; ++i) v[i] += old[i];
-            } else if (direct && p.sqacc) {
-#pragma unroll
-                for (int i = 0; i < NB; ++i) if (ok[i]) { const f32x4 d = v[i] * v[i]; ss += (d[0] + d[1]) + (d[2] + d[3]); }
+                for (int i = 0; i < NB; ++i) if (ok[i]) *reinterpret_cast<f32x4*>(o[i]) = v[i];
+                continue;
             }
 #pragma unroll
-            for (int i = 0; i < NB; ++i) if (ok[i]) *reinterpret_cast<f32x4*>(o[i]) = v[i];
-            if (direct && p.g16) {           // the bf16 exchange twin of the same elements
-                typedef bf16_t w2_bf16x4 __attribute__((ext_vector_type(4)));
+            for (int i = 0; i < NB; ++i) old[i] = p.accumulate ? *reinterpret_cast<const f32x4*>(o[i]) : v[i];
 #pragma unroll
-                for (int i = 0; i < NB; ++i)
-                    if (ok[i]) *reinterpret_cast<w2_bf16x4*>(p.g16 + (o[i] - p.dw)) = w2_bf16x4{(bf16_t)v[i][0], (bf16_t)v[i][1], (bf16_t)v[i][2], (bf16_t)v[i][3]};
-            }
+            for (int i = 0; i < NB; ++i)
+                if (ok[i]) ss += rt_wg_commit(v[i], old[i], reinterpret_cast<f32x4*>(o[i]), p.g16 ? p.g16 + (o[i] - p.dw) : nullptr, p.accumulate != 0);
         }
     }
     }
@@ -527,23 +516,7 @@ __global__ __launch_bounds__(256) void w2_reduce_kernel(const W2Reduce g) {
     }
     for (; s < nsplit; ++s) a += *reinterpret_cast<const f32x4*>(part + (size_t)s * out_elems + i);
     if (scale) a *= scale[i / g.row_elems[lo]];
-    f32x4* o = reinterpret_cast<f32x4*>(dw + i);
-    f32x4 fin;
-    if (g.accumulate[lo]) {
-        const f32x4 old = *o;
-        const f32x4 d = a * (old + old + a);              // |old + a|^2 - |old|^2
-        ss = (d[0] + d[1]) + (d[2] + d[3]);
-        fin = old + a;
-    } else {
-        const f32x4 d = a * a;
-        ss = (d[0] + d[1]) + (d[2] + d[3]);
-        fin = a;
-    }
-    *o = fin;
-    if (g.g16[lo]) {
-        typedef bf16_t w2_bf16x4 __attribute__((ext_vector_type(4)));
-        *reinterpret_cast<w2_bf16x4*>(g.g16[lo] + i) = w2_bf16x4{(bf16_t)fin[0], (bf16_t)fin[1], (bf16_t)fin[2], (bf16_t)fin[3]};
-    }
+    ss = rt_wg_commit(a, reinterpret_cast<f32x4*>(dw + i), g.g16[lo] ? g.g16[lo] + i : nullptr, g.accumulate[lo] != 0);
     }
     if (sq) {                                             // uniform per workgroup (one problem per workgroup)
         ss = rt_block_sum(ss, sm);

@@ -512,6 +512,38 @@ def _req(t, dtype, name):
         raise RuntimeError(f"{name}: tensor must be contiguous")
 
 
+_GEOM = ("B", "SH", "SW", "SC", "DH", "DW", "N", "KH", "KW", "stride", "pad")
+
+
+def _geom_desc(cls, geom, fields):
+    """A `cls` descriptor: the geometry tuple and every other field BY NAME (a tensor gives its address; fields not named stay
+    zero / NULL).  A name the struct does not have is an error."""
+    d = cls(**dict(zip(_GEOM, geom, strict=True)))
+    known = {name for name, _ in cls._fields_}
+    for k, v in fields.items():
+        if k not in known:
+            raise TypeError(f"{cls.__name__}: no field {k!r}")
+        setattr(d, k, _p(v) if torch.is_tensor(v) else v)
+    return d
+
+
+def _gemm_desc(src, wgt, geom, **fields):
+    return _geom_desc(ConvGemmDesc, geom, dict(fields, src=src, wgt=wgt))
+
+
+def _wgrad_desc(dy, x, dw, geom, **fields):
+    """... of a weight gradient into `dw`, with the norm accumulator and the bf16 twin `dw` is registered for."""
+    return _geom_desc(ConvWgradDesc, geom, dict(fields, dy=dy, x=x, dw=dw, sqacc=_sqacc(dw), g16=_g16(dw)))
+
+
+def _out_buffer(o, dtype, name, M, N, dev):
+    """An [M, N] output of a product: an existing tensor to write into, True (allocate) or False / None (none)."""
+    o = o if torch.is_tensor(o) else (torch.empty((M, N), dtype=dtype, device=dev) if o else None)
+    _req(o, dtype, name)
+    assert o is None or o.numel() == M * N
+    return o
+
+
 # --------------------------------------------------------------------------------------------
 # op wrappers
 # --------------------------------------------------------------------------------------------
@@ -533,15 +565,14 @@ def conv_gemm(src, wgt, *, geom, bias=None, res_f32=None, res_bf16=None, gate=No
     assert wgt.numel() == N * KH * KW * SC, (wgt.shape, geom)
     M = B * DH * DW
     _req(dtanh, torch.bfloat16, "dtanh")
-    ob = out_bf16 if torch.is_tensor(out_bf16) else (torch.empty((M, N), dtype=torch.bfloat16, device=src.device) if out_bf16 else None)
-    of = out_f32 if torch.is_tensor(out_f32) else (torch.empty((M, N), dtype=torch.float32, device=src.device) if out_f32 else None)
-    _req(ob, torch.bfloat16, "out_bf16"); _req(of, torch.float32, "out_f32"); _req(acc2_f32, torch.float32, "acc2_f32")
+    ob = _out_buffer(out_bf16, torch.bfloat16, "out_bf16", M, N, src.device)
+    of = _out_buffer(out_f32, torch.float32, "out_f32", M, N, src.device)
+    _req(acc2_f32, torch.float32, "acc2_f32")
     assert acc2_f32 is None or acc2_f32.numel() == M * N
-    assert (ob is None or ob.numel() == M * N) and (of is None or of.numel() == M * N)
-    d = ConvGemmDesc(_p(src), _p(wgt), _p(ob), _p(of), _p(bias), _p(res_f32), _p(res_bf16), _p(gate),
-                     _p(preact), B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad,
-                     1 if transposed else 0, act, gate_scale, drop_p, drop_seed & 0xFFFFFFFF, tile_hint, None, _p(dtanh), 1 if res_first else 0, _seedp(drop_p),
-                     drop_shift, _p(acc2_f32), int(dil))
+    d = _gemm_desc(src, wgt, geom, out_bf16=ob, out_f32=of, bias=bias, res_f32=res_f32, res_bf16=res_bf16, gate=gate, preact=preact,
+                   transposed=int(bool(transposed)), act=act, gate_scale=gate_scale, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF,
+                   tile_hint=tile_hint, dtanh=dtanh, res_first=int(bool(res_first)), seed_dev=_seedp(drop_p), drop_shift=drop_shift,
+                   acc2_f32=acc2_f32, dil=int(dil))
     op = None
     if out_preact:
         op = torch.empty((M, N), dtype=torch.bfloat16, device=src.device)
@@ -666,8 +697,8 @@ def conv_wgrad(dy, x, dw, *, geom, scale=None, msplit=0, dbias=None, variant=0, 
     assert dy.numel() == B * DH * DW * N and x.numel() == B * SH * SW * SC and dw.numel() == N * KH * KW * SC
     _req(dbias, torch.float32, "dbias")
     ws = _wgrad_workspace(dy.device) if workspace else None
-    d = ConvWgradDesc(_p(dy), _p(x), _p(dw), _p(scale), B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad, msplit, _p(dbias), variant,
-                      _p(ws), WGRAD_WS_BYTES if ws is not None else 0, int(bool(overwrite)), int(dil), _sqacc(dw), _g16(dw))
+    d = _wgrad_desc(dy, x, dw, geom, scale=scale, msplit=msplit, dbias=dbias, variant=variant, workspace=ws,
+                    workspace_bytes=WGRAD_WS_BYTES if ws is not None else 0, overwrite=int(bool(overwrite)), dil=int(dil))
     _timed("conv_wgrad", 2.0 * B * DH * DW * N * KH * KW * SC,
            lambda: _check(lib().rt_conv_wgrad(ctypes.byref(d), _stream()), "rt_conv_wgrad"), tag=("W",) + tuple(geom))
     return dw
@@ -686,21 +717,10 @@ def gconv(src, wgt, *, geom, groups, bias=None, gate=None, gate_scale=1.0, act=A
     cg = SC // groups if groups > 0 else 0
     assert wgt.numel() == SC * KH * KW * cg, (wgt.shape, geom, groups)
     M = B * DH * DW
-    ob = out_bf16 if torch.is_tensor(out_bf16) else (torch.empty((M, N), dtype=torch.bfloat16, device=src.device) if out_bf16 else None)
-    of = out_f32 if torch.is_tensor(out_f32) else (torch.empty((M, N), dtype=torch.float32, device=src.device) if out_f32 else None)
-    _req(ob, torch.bfloat16, "out_bf16"); _req(of, torch.float32, "out_f32")
-    assert (ob is None or ob.numel() == M * N) and (of is None or of.numel() == M * N)
-    d = ConvGemmDesc(_p(src), _p(wgt), _p(ob), _p(of), _p(bias), None, None, _p(gate), None, B, SH, SW, SC, DH, DW, N, KH, KW,
-                     stride, pad, 1 if transposed else 0, act, gate_scale, 0.0, 0, 0, None, None, 0, None, 0, None, int(dil))
-    keep = []
-    for k, v in unsupported.items():          # forwarded so that the library refuses them (no silent drop)
-        if k in ("res_f32", "res_bf16", "preact", "dtanh", "acc2_f32"):
-            if v is not None:
-                setattr(d, k, _p(v)); keep.append(v)
-        elif k in ("drop_p", "tile_hint", "res_first", "drop_shift"):
-            setattr(d, k, v)
-        else:
-            raise TypeError(f"gconv: unknown argument {k}")
+    ob = _out_buffer(out_bf16, torch.bfloat16, "out_bf16", M, N, src.device)
+    of = _out_buffer(out_f32, torch.float32, "out_f32", M, N, src.device)
+    d = _gemm_desc(src, wgt, geom, out_bf16=ob, out_f32=of, bias=bias, gate=gate, transposed=int(bool(transposed)), act=act,
+                   gate_scale=gate_scale, dil=int(dil), **unsupported)      # (forwarded so that the library refuses them: no silent drop)
     spatial = B * (SH * SW if transposed else DH * DW)
     flops = 2.0 * spatial * SC * KH * KW * cg
     _timed("gconv", flops, lambda: _check(lib().rt_gconv(ctypes.byref(d), int(groups), _stream()), "rt_gconv"),
@@ -717,8 +737,8 @@ def gconv_wgrad(dy, x, dw, *, geom, groups, scale=None, msplit=0, overwrite=Fals
     cg = SC // groups if groups > 0 else 0
     assert dy.numel() == B * DH * DW * N and x.numel() == B * SH * SW * SC and dw.numel() == N * KH * KW * cg
     ws = _wgrad_workspace(dy.device)
-    d = ConvWgradDesc(_p(dy), _p(x), _p(dw), _p(scale), B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad, msplit, _p(dbias), variant,
-                      _p(ws), WGRAD_WS_BYTES, int(bool(overwrite)), int(dil), _sqacc(dw), _g16(dw))
+    d = _wgrad_desc(dy, x, dw, geom, scale=scale, msplit=msplit, dbias=dbias, variant=variant, workspace=ws,
+                    workspace_bytes=WGRAD_WS_BYTES, overwrite=int(bool(overwrite)), dil=int(dil))
     _timed("gconv_wgrad", 2.0 * B * DH * DW * N * KH * KW * cg,
            lambda: _check(lib().rt_gconv_wgrad(ctypes.byref(d), int(groups), _stream()), "rt_gconv_wgrad"),
            nbytes=2.0 * (B * DH * DW * N + B * SH * SW * SC) + 4.0 * dw.numel())
@@ -1344,17 +1364,15 @@ class WgradBatch:
         M, N = dy.shape
         K = x.shape[1]
         assert x.shape[0] == M and dw.numel() == N * K
-        self.descs.append(ConvWgradDesc(_p(dy), _p(x), _p(dw), None, M, 1, 1, K, 1, 1, N, 1, 1, 1, 0, 0, _p(dbias), 0, None, 0,
-                                        int(bool(overwrite)), 0, _sqacc(dw), _g16(dw)))
+        geom = (M, 1, 1, K, 1, 1, N, 1, 1, 1, 0)
+        self.descs.append(_wgrad_desc(dy, x, dw, geom, dbias=dbias, overwrite=int(bool(overwrite))))
         self.keep.append((dy, x))
-        self._account((M, 1, 1, K, 1, 1, N, 1, 1, 1, 0))
+        self._account(geom)
 
     def add_conv(self, dy, x, dw, geom, scale=None, overwrite=False, dil=1):
         """A convolution weight gradient (any geometry: the non-groupable ones are forwarded to rt_conv_wgrad at run())."""
-        B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad = geom
         _req(dy, torch.bfloat16, "dy"); _req(x, torch.bfloat16, "x"); _req(dw, torch.float32, "dw"); _req(scale, torch.float32, "scale")
-        self.descs.append(ConvWgradDesc(_p(dy), _p(x), _p(dw), _p(scale), B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad, 0, None, 0,
-                                        None, 0, int(bool(overwrite)), int(dil), _sqacc(dw), _g16(dw)))
+        self.descs.append(_wgrad_desc(dy, x, dw, geom, scale=scale, overwrite=int(bool(overwrite)), dil=int(dil)))
         self.keep.append((dy, x, scale))
         self._account(geom)
 
