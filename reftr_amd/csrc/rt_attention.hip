@@ -9,7 +9,7 @@
 //     for ONE query (lane & 15), keys 4g..4g+3 of the tile (g = lane >> 4).  Two such tiles (32 keys) are exactly
 //     the B-operand fragment of the next MFMA  O^T[d][q] += V^T[d][keys] P^T[keys][q]  — no cross-lane traffic for
 //     P; V^T / K^T fragments come from the natural V / K rows through the gfx950 LDS transpose read
-//     (ds_read_b64_tr_b16), with the same key -> k-slot assignment on both operands.
+//     (rt_tr_frag, rt_lds.h), with the same key -> k-slot assignment on both operands.
 //     Softmax: two streaming passes over the keys (pass 1: running max / sum, pass 2: normalised P and PV), so
 //     any S fits without holding S scores in registers; row statistics are combined across the 4 lane groups
 //     with two shuffles.
@@ -18,20 +18,20 @@
 //
 // Dropout acts on the probabilities with the shared counter hash (index ((b*H+h)*Sq + q)*Sk + key); a fully
 // masked row gives NaN like the reference's softmax over -inf.
+//
+// Every inner loop of the two-pass forward and of the backward is ONE function over `rows` staged rows that start at row c0 of the
+// inner axis: fwd_stats_chunk (pass 1), fwd_pv_chunk (pass 2), dq_chunk, dkv_chunk, with stage_kv_bias / stage_qdo_stats filling the
+// LDS they read.  The three bodies (attn_fwd_body, attn_bwd_dq_body, attn_bwd_dkv_body) take LONG as a compile-time parameter: the
+// whole-axis kernels stage the axis once and call each chunk function once (rows = the padded axis, c0 = 0), the long-axis kernels
+// call it per staged chunk.  The arithmetic of the two forms is the same code, which is what makes their results the same bits.
+// The register-kept forward (attn_fwd_reg_kernel) keeps its own fully unrolled loops, pass 2 included, and reads the descriptor
+// fields directly: moving it onto pv-step, staging or store helpers, or handing its descriptor to a helper by reference, changes
+// the instruction stream the compiler emits for it (measured 6 % slower at S = 440); as written it compiles to the code it had.
 #include "rt_common.h"
+#include "rt_lds.h"
 #include <stdlib.h>
 
 namespace {
-
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-
-__device__ __forceinline__ bf16x8 tr_pair(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)p1);
-    union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-    u.s.a = lo; u.s.b = hi;
-    return u.v;
-}
 
 __device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
     bf16x8 o;
@@ -126,102 +126,251 @@ __device__ __forceinline__ f32x4 tile_dot(const unsigned char* sA, int row0, int
     return acc;
 }
 
-// ------------------------------------------------------------------------------------------------ forward
-template <int DH, int NW>
-__global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const rt_attn_desc p) {
-    constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Skp = (p.Sk + 31) & ~31;
-    unsigned char* sK = smem;
-    unsigned char* sV = sK + (size_t)Skp * RS;
-    float* sBias = reinterpret_cast<float*>(sV + (size_t)Skp * RS);
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    stage_rows2<DH>(sK, (const bf16_t*)p.k + (size_t)b * p.Sk * p.ldk + h * DH, p.ldk,
-                    sV, (const bf16_t*)p.v + (size_t)b * p.Sk * p.ldv + h * DH, p.ldv, p.Sk, Skp, threadIdx.x, 64 * NW);
-    for (int j = threadIdx.x; j < Skp; j += 64 * NW)
-        sBias[j] = (j < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + j])) ? 0.f : -INFINITY;
-    __syncthreads();
+// ------------------------------------------------------------------------------------------------ shared pieces
+// (batch, head) of the workgroup, the lane's place in its wave's 16 x 16 tiles (li, lg) and in the transpose reads (tr_r, tr_c)
+struct Lanes { int bh, b, h, lane, wave, li, lg, tr_r, tr_c; };
+__device__ __forceinline__ Lanes lanes(int H) {
+    Lanes t;
+    t.bh = blockIdx.x; t.b = t.bh / H; t.h = t.bh % H;
+    t.lane = threadIdx.x & 63; t.wave = threadIdx.x >> 6;
+    t.li = t.lane & 15; t.lg = t.lane >> 4;
+    t.tr_r = 4 * t.lg + (t.li >> 2); t.tr_c = (t.li & 3) * 8;
+    return t;
+}
+// row 0 of this head's slice of a [B][S][ld] operand
+template <int DH>
+__device__ __forceinline__ const bf16_t* head_rows(const void* base, const Lanes& t, int S, int ld) {
+    return (const bf16_t*)base + (size_t)t.b * S * ld + t.h * DH;
+}
 
-    const int q = blockIdx.y * (16 * NW) + wave * 16 + li;          // this lane's query
-    if (blockIdx.y * (16 * NW) + wave * 16 >= p.Sq) return;
-    bf16x8 qf[Geo<DH>::KH];
-    load_bfrag<DH>((const bf16_t*)p.q + (size_t)b * p.Sq * p.ldq + h * DH, q, p.Sq, p.ldq, lg, qf);
-    const int nblk = Skp >> 4;
+// the dynamic LDS of every kernel here (smem_bytes): two [span][RS] operand slabs -- K, V or Q, dO -- and two rows of span floats
+// (key bias, or lse and delta)
+template <int DH> struct Lds {
+    unsigned char *a, *b;
+    float *f0, *f1;
+    __device__ __forceinline__ explicit Lds(int span) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+        a = smem;
+        b = a + (size_t)span * Geo<DH>::RS;
+        f0 = reinterpret_cast<float*>(b + (size_t)span * Geo<DH>::RS);
+        f1 = f0 + span;
+    }
+};
 
-    // pass 1: running max / sum over this lane's keys (4 per 16-key tile)
-    float m = -INFINITY, l = 0.f;
-    for (int blk = 0; blk < nblk; ++blk) {
-        const f32x4 acc = tile_dot<DH>(sK, blk * 16, li, lg, qf);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(sBias + blk * 16 + lg * 4);
-        float s[4], mx = m;
+// dropout of one attention site: element `idx` is kept (and scaled by ks) iff keep(idx)
+struct Drop {
+    bool on;
+    uint32_t thresh;
+    float ks;
+    uint32_t seed;
+    __device__ __forceinline__ Drop(float drop_p, const uint32_t* seed_dev, uint32_t drop_seed)
+        : on(drop_p > 0.f), thresh(rt_drop_thresh(drop_p)), ks(on ? 1.f / (1.f - drop_p) : 1.f), seed(rt_site_seed(seed_dev, drop_seed)) {}
+    __device__ __forceinline__ bool keep(uint32_t idx) const { return rt_hash32(seed, idx) >= thresh; }
+};
+
+// sum / max over the 4 lane groups that share a query (or key) column
+__device__ __forceinline__ float group_sum(float v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+__device__ __forceinline__ float group_max(float v) {
+    v = fmaxf(v, __shfl_xor(v, 16, 64));
+    return fmaxf(v, __shfl_xor(v, 32, 64));
+}
+// the lane's running (m, l) of pass 1 -> the row's max M (Ms: 0 for a fully masked row), sum l and 1 / l
+__device__ __forceinline__ void softmax_finish(float m, float& l, float& M, float& Ms, float& inv_l) {
+    M = group_max(m);
+    Ms = (M == -INFINITY) ? 0.f : M;
+    l *= __expf(m - Ms);
+    l = group_sum(l);
+    inv_l = 1.f / l;                 // fully masked row: 0 * inf = NaN in pass 2, as the reference
+}
+
+// delta of one query row = sum_d dO[d] * O[d], from the row's DH values in memory
+template <int DH>
+__device__ __forceinline__ float row_delta(const bf16_t* orow, const bf16_t* drow) {
+    float del = 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { s[r] = acc[r] * p.scale + bias[r]; mx = fmaxf(mx, s[r]); }
+    for (int c = 0; c < DH; c += 8) {
+        const bf16x8 ov = *reinterpret_cast<const bf16x8*>(orow + c), dv8 = *reinterpret_cast<const bf16x8*>(drow + c);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) del += (float)dv8[e] * (float)ov[e];
+    }
+    return del;
+}
+
+// the lane's 4 x DT accumulator values -> its row of a bf16 output (columns 16 t + 4 lg ..+3)
+template <int DH>
+__device__ __forceinline__ void store_rows(bf16_t* row, int lg, const f32x4 (&acc)[Geo<DH>::DT]) {
+#pragma unroll
+    for (int t = 0; t < Geo<DH>::DT; ++t) {
+        bf16x4 ov;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)acc[t][r];
+        *reinterpret_cast<bf16x4*>(row + t * 16 + lg * 4) = ov;
+    }
+}
+template <int DH>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[Geo<DH>::DT]) {
+#pragma unroll
+    for (int t = 0; t < Geo<DH>::DT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// Rows c0 .. c0 + rows of the head's K (WITH_V: and V) -> LDS rows 0 .. rows (past Sk: zeros), and their additive key bias
+// (0, or -inf for padded / masked keys)
+struct KvSrc { const void *k, *v; const uint8_t* kpm; int Sk, ldk, ldv; };
+template <int DH, int NW, bool WITH_V>
+__device__ __forceinline__ void stage_kv_bias(const Lds<DH>& s, const KvSrc& p, const Lanes& t, int c0, int rows) {
+    const int valid = (p.Sk - c0 < rows) ? p.Sk - c0 : rows;
+    const bf16_t* k = head_rows<DH>(p.k, t, p.Sk, p.ldk) + (size_t)c0 * p.ldk;
+    if (WITH_V) stage_rows2<DH>(s.a, k, p.ldk, s.b, head_rows<DH>(p.v, t, p.Sk, p.ldv) + (size_t)c0 * p.ldv, p.ldv, valid, rows, threadIdx.x, 64 * NW);
+    else stage_rows<DH>(s.a, k, valid, rows, p.ldk, threadIdx.x, 64 * NW);
+    for (int j = threadIdx.x; j < rows; j += 64 * NW)
+        s.f0[j] = (c0 + j < p.Sk && !(p.kpm && p.kpm[(size_t)t.b * p.Sk + c0 + j])) ? 0.f : -INFINITY;
+}
+
+// Rows c0 .. c0 + rows of the head's Q and dO -> LDS, with their lse (f0) and delta (f1).
+// OWN_DELTA: delta[i] = sum_d dO[i, d] * O[i, d] is recomputed here for the head's query rows (64-128 B of O and dO per row)
+// instead of being read from the dQ kernel's output: the two halves of the backward then do not depend on each other and run
+// as ONE launch (attn_bwd_fused_kernel) -- on the encoder's chain that is a 17 us kernel and a graph-node boundary less per layer.
+template <int DH, int NW, bool OWN_DELTA>
+__device__ __forceinline__ void stage_qdo_stats(const Lds<DH>& s, const rt_attn_bwd_desc& p, const Lanes& t, int c0, int rows) {
+    const int valid = (p.Sq - c0 < rows) ? p.Sq - c0 : rows;
+    const bf16_t* dbase = head_rows<DH>(p.dout, t, p.Sq, p.ldo);
+    stage_rows2<DH>(s.a, head_rows<DH>(p.q, t, p.Sq, p.ldq) + (size_t)c0 * p.ldq, p.ldq, s.b, dbase + (size_t)c0 * p.ldo, p.ldo,
+                    valid, rows, threadIdx.x, 64 * NW);
+    for (int i = threadIdx.x; i < rows; i += 64 * NW) {
+        const int qi = c0 + i;
+        s.f0[i] = (qi < p.Sq) ? p.lse[(size_t)t.bh * p.Sq + qi] : INFINITY;       // padded query rows: p = exp(-inf) = 0
+        float del = 0.f;
+        if (qi < p.Sq) {
+            if (OWN_DELTA) {
+                const size_t row = ((size_t)t.b * p.Sq + qi) * p.ldo + t.h * DH;
+                del = row_delta<DH>((const bf16_t*)p.out + row, (const bf16_t*)p.dout + row);
+            }
+            else del = p.delta[(size_t)t.bh * p.Sq + qi];
+        }
+        s.f1[i] = del;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ forward
+// pass 1 over `rows` staged keys: running max / sum over this lane's keys (4 per 16-key tile)
+template <int DH>
+__device__ __forceinline__ void fwd_stats_chunk(const Lds<DH>& s, int rows, const Lanes& t, const bf16x8 (&qf)[Geo<DH>::KH], float scale,
+                                                float& m, float& l) {
+    for (int blk = 0; blk < (rows >> 4); ++blk) {
+        const f32x4 acc = tile_dot<DH>(s.a, blk * 16, t.li, t.lg, qf);
+        const f32x4 bias = *reinterpret_cast<const f32x4*>(s.f0 + blk * 16 + t.lg * 4);
+        float sc[4], mx = m;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { sc[r] = acc[r] * scale + bias[r]; mx = fmaxf(mx, sc[r]); }
         const float ms = (mx == -INFINITY) ? 0.f : mx;
         float add = 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) add += __expf(s[r] - ms);
+        for (int r = 0; r < 4; ++r) add += __expf(sc[r] - ms);
         l = l * __expf(m - ms) + add;
         m = mx;
     }
-    float M = fmaxf(m, __shfl_xor(m, 16, 64));
-    M = fmaxf(M, __shfl_xor(M, 32, 64));
-    const float Ms = (M == -INFINITY) ? 0.f : M;
-    l *= __expf(m - Ms);
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv_l = 1.f / l;                 // fully masked row: 0 * inf = NaN below, as the reference
+}
 
-    // pass 2: normalised probabilities -> P^T fragments -> O^T += V^T P^T
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
-    const uint32_t drop_row = (uint32_t)(((size_t)bh * p.Sq + q) * p.Sk);
-    f32x4 o[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
-    for (int c = 0; c < (Skp >> 5); ++c) {
+// pass 2 over `rows` staged keys: normalised probabilities -> P^T fragments -> O^T += V^T P^T
+template <int DH>
+__device__ __forceinline__ void fwd_pv_chunk(const Lds<DH>& s, int rows, int c0, const Lanes& t, const bf16x8 (&qf)[Geo<DH>::KH], float scale,
+                                             float Ms, float inv_l, const Drop& drop, uint32_t drop_row, f32x4 (&o)[Geo<DH>::DT]) {
+    constexpr int RS = Geo<DH>::RS;
+    for (int c = 0; c < (rows >> 5); ++c) {
         float pv[8];
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int k0 = c * 32 + half * 16;
-            const f32x4 acc = tile_dot<DH>(sK, k0, li, lg, qf);
-            const f32x4 bias = *reinterpret_cast<const f32x4*>(sBias + k0 + lg * 4);
+            const f32x4 acc = tile_dot<DH>(s.a, k0, t.li, t.lg, qf);
+            const f32x4 bias = *reinterpret_cast<const f32x4*>(s.f0 + k0 + t.lg * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float pr = __expf(acc[r] * p.scale + bias[r] - Ms) * inv_l;
-                if (do_drop) pr = (rt_hash32(dseed, drop_row + (uint32_t)(k0 + lg * 4 + r)) >= thresh) ? pr * ks : 0.f;
+                float pr = __expf(acc[r] * scale + bias[r] - Ms) * inv_l;
+                if (drop.on) pr = drop.keep(drop_row + (uint32_t)(c0 + k0 + t.lg * 4 + r)) ? pr * drop.ks : 0.f;
                 pv[half * 4 + r] = pr;
             }
         }
         const bf16x8 pf = pack8(pv);
-        const unsigned char* v0 = sV + (c * 32 + tr_r) * RS + tr_c;
+        const unsigned char* v0 = s.b + (c * 32 + t.tr_r) * RS + t.tr_c;
 #pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            const bf16x8 vf = tr_pair(v0 + t * 32, v0 + 16 * RS + t * 32);
-            o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[t], 0, 0, 0);
+        for (int d = 0; d < Geo<DH>::DT; ++d) {
+            const bf16x8 vf = rt_tr_frag(v0 + d * 32, v0 + 16 * RS + d * 32);
+            o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[d], 0, 0, 0);
         }
     }
-    if (q < p.Sq) {
-        bf16_t* orow = (bf16_t*)p.out + ((size_t)b * p.Sq + q) * p.ldo + h * DH;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            bf16x4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)o[t][r];
-            *reinterpret_cast<bf16x4*>(orow + t * 16 + lg * 4) = ov;
-        }
-        if (lg == 0 && p.lse) p.lse[(size_t)bh * p.Sq + q] = M + __logf(l);
+}
+
+template <int DH>
+__device__ __forceinline__ void fwd_store(void* out, float* lse, int Sq, int ldo, const Lanes& t, int q, const f32x4 (&o)[Geo<DH>::DT], float M, float l) {
+    if (q < Sq) {
+        store_rows<DH>((bf16_t*)out + ((size_t)t.b * Sq + q) * ldo + t.h * DH, t.lg, o);
+        if (t.lg == 0 && lse) lse[(size_t)t.bh * Sq + q] = M + __logf(l);
     }
+}
+
+// The two-pass forward.  LONG: rows past Sq carry zero fragments and are never stored (no early return: every wave meets the
+// chunk barriers); pass 1 stages K only.
+template <int DH, int NW, bool LONG>
+__device__ __forceinline__ void attn_fwd_body(const rt_attn_desc& p, const int ch) {
+    const Lanes t = lanes(p.H);
+    const int Skp = (p.Sk + 31) & ~31;
+    const Lds<DH> s(LONG ? ch : Skp);
+    const KvSrc kv{p.k, p.v, p.kpm, p.Sk, p.ldk, p.ldv};
+    if constexpr (!LONG) {
+        stage_kv_bias<DH, NW, true>(s, kv, t, 0, Skp);
+        __syncthreads();
+    }
+    const int q = blockIdx.y * (16 * NW) + t.wave * 16 + t.li;          // this lane's query
+    if (!LONG && blockIdx.y * (16 * NW) + t.wave * 16 >= p.Sq) return;
+    bf16x8 qf[Geo<DH>::KH];
+    load_bfrag<DH>(head_rows<DH>(p.q, t, p.Sq, p.ldq), q, p.Sq, p.ldq, t.lg, qf);
+
+    float m = -INFINITY, l = 0.f;
+    if constexpr (!LONG) {
+        fwd_stats_chunk<DH>(s, Skp, t, qf, p.scale, m, l);
+    } else {
+        for (int c0 = 0; c0 < Skp; c0 += ch) {          // one staged chunk at a time, behind a barrier
+            const int rows = (Skp - c0 < ch) ? Skp - c0 : ch;
+            __syncthreads();
+            stage_kv_bias<DH, NW, false>(s, kv, t, c0, rows);
+            __syncthreads();
+            fwd_stats_chunk<DH>(s, rows, t, qf, p.scale, m, l);
+        }
+    }
+    float M, Ms, inv_l;
+    softmax_finish(m, l, M, Ms, inv_l);
+
+    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const uint32_t drop_row = (uint32_t)(((size_t)t.bh * p.Sq + q) * p.Sk);
+    f32x4 o[Geo<DH>::DT];
+    zero_acc<DH>(o);
+    if constexpr (!LONG) {
+        fwd_pv_chunk<DH>(s, Skp, 0, t, qf, p.scale, Ms, inv_l, drop, drop_row, o);
+    } else {
+        for (int c0 = 0; c0 < Skp; c0 += ch) {          // one staged chunk at a time, behind a barrier
+            const int rows = (Skp - c0 < ch) ? Skp - c0 : ch;
+            __syncthreads();
+            stage_kv_bias<DH, NW, true>(s, kv, t, c0, rows);
+            __syncthreads();
+            fwd_pv_chunk<DH>(s, rows, c0, t, qf, p.scale, Ms, inv_l, drop, drop_row, o);
+        }
+    }
+    fwd_store<DH>(p.out, p.lse, p.Sq, p.ldo, t, q, o, M, l);
+}
+
+template <int DH, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(const rt_attn_desc p) {
+    attn_fwd_body<DH, NW, false>(p, 0);
 }
 
 // Forward with the score row kept in registers (NT 16-key tiles, fully unrolled): the NT score MFMAs of a wave are
 // independent and issue back to back, the softmax runs over registers, and the scores are not recomputed for the P V pass.
 // The two-pass kernel above walks 2 x NT dependent [LDS read -> MFMA -> exp] steps per wave and is latency-bound at one
-// workgroup per CU (88 KB of LDS for S = 440).
+// workgroup per CU (88 KB of LDS for S = 440).  Its loops index registers, so they stay its own (see the file header).
 template <int DH, int NW, int NT>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_desc p) {
     constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT;
@@ -258,26 +407,20 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_des
             sc[blk] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         }
     }
-    float M = fmaxf(m, __shfl_xor(m, 16, 64));
-    M = fmaxf(M, __shfl_xor(M, 32, 64));
+    const float M = group_max(m);
     const float Ms = (M == -INFINITY) ? 0.f : M;
     float l = 0.f;
 #pragma unroll
     for (int blk = 0; blk < NT; ++blk)
 #pragma unroll
         for (int r = 0; r < 4; ++r) { sc[blk][r] = __expf(sc[blk][r] - Ms); l += sc[blk][r]; }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
+    l = group_sum(l);
     const float inv_l = 1.f / l;                 // fully masked row: 0 * inf = NaN below, as the reference
 
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
+    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     const uint32_t drop_row = (uint32_t)(((size_t)bh * p.Sq + q) * p.Sk);
     f32x4 o[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc<DH>(o);
     const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
 #pragma unroll
     for (int c = 0; c < NT / 2; ++c) {
@@ -289,7 +432,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_des
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float pr = sc[2 * c + half][r] * inv_l;
-                    if (do_drop) pr = (rt_hash32(dseed, drop_row + (uint32_t)(k0 + lg * 4 + r)) >= thresh) ? pr * ks : 0.f;
+                    if (drop.on) pr = drop.keep(drop_row + (uint32_t)(k0 + lg * 4 + r)) ? pr * drop.ks : 0.f;
                     pv[half * 4 + r] = pr;
                 }
             }
@@ -297,7 +440,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_des
             const unsigned char* v0 = sV + (c * 32 + tr_r) * RS + tr_c;
 #pragma unroll
             for (int t = 0; t < DT; ++t) {
-                const bf16x8 vf = tr_pair(v0 + t * 32, v0 + 16 * RS + t * 32);
+                const bf16x8 vf = rt_tr_frag(v0 + t * 32, v0 + 16 * RS + t * 32);
                 o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[t], 0, 0, 0);
             }
         }
@@ -316,493 +459,195 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_des
 }
 
 // ------------------------------------------------------------------------------------------------ dQ (+ delta)
-template <int DH, int NW>
-__device__ __forceinline__ void attn_bwd_dq_body(const rt_attn_bwd_desc& p, const int by) {
-    constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT, KH = Geo<DH>::KH;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Skp = (p.Sk + 31) & ~31;
-    unsigned char* sK = smem;
-    unsigned char* sV = sK + (size_t)Skp * RS;
-    float* sBias = reinterpret_cast<float*>(sV + (size_t)Skp * RS);
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    stage_rows2<DH>(sK, (const bf16_t*)p.k + (size_t)b * p.Sk * p.ldk + h * DH, p.ldk,
-                    sV, (const bf16_t*)p.v + (size_t)b * p.Sk * p.ldv + h * DH, p.ldv, p.Sk, Skp, threadIdx.x, 64 * NW);
-    for (int j = threadIdx.x; j < Skp; j += 64 * NW)
-        sBias[j] = (j < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + j])) ? 0.f : -INFINITY;
-    __syncthreads();
-
-    const int q = by * (16 * NW) + wave * 16 + li;
-    if (by * (16 * NW) + wave * 16 >= p.Sq) return;
-    bf16x8 qf[KH], dof[KH], of[KH];
-    load_bfrag<DH>((const bf16_t*)p.q + (size_t)b * p.Sq * p.ldq + h * DH, q, p.Sq, p.ldq, lg, qf);
-    load_bfrag<DH>((const bf16_t*)p.dout + (size_t)b * p.Sq * p.ldo + h * DH, q, p.Sq, p.ldo, lg, dof);
-    load_bfrag<DH>((const bf16_t*)p.out + (size_t)b * p.Sq * p.ldo + h * DH, q, p.Sq, p.ldo, lg, of);
-    float delta = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < KH; ++kh)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) delta += (float)dof[kh][e] * (float)of[kh][e];
-    delta += __shfl_xor(delta, 16, 64);
-    delta += __shfl_xor(delta, 32, 64);
-    const float lse = (q < p.Sq) ? p.lse[(size_t)bh * p.Sq + q] : INFINITY;
-    if (lg == 0 && q < p.Sq) p.delta[(size_t)bh * p.Sq + q] = delta;
-
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
-    const uint32_t drop_row = (uint32_t)(((size_t)bh * p.Sq + q) * p.Sk);
-    f32x4 dq[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
-    for (int c = 0; c < (Skp >> 5); ++c) {
+// `rows` staged keys: dS^T from the recomputed probabilities, dQ^T += K^T dS^T
+template <int DH>
+__device__ __forceinline__ void dq_chunk(const Lds<DH>& s, int rows, int c0, const Lanes& t, const bf16x8 (&qf)[Geo<DH>::KH],
+                                         const bf16x8 (&dof)[Geo<DH>::KH], float lse, float delta, float scale, const Drop& drop,
+                                         uint32_t drop_row, f32x4 (&dq)[Geo<DH>::DT]) {
+    constexpr int RS = Geo<DH>::RS;
+    for (int c = 0; c < (rows >> 5); ++c) {
         float dsv[8];
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int k0 = c * 32 + half * 16;
-            const f32x4 s = tile_dot<DH>(sK, k0, li, lg, qf);
-            const f32x4 dp = tile_dot<DH>(sV, k0, li, lg, dof);
-            const f32x4 bias = *reinterpret_cast<const f32x4*>(sBias + k0 + lg * 4);
+            const f32x4 sc = tile_dot<DH>(s.a, k0, t.li, t.lg, qf);
+            const f32x4 dp = tile_dot<DH>(s.b, k0, t.li, t.lg, dof);
+            const f32x4 bias = *reinterpret_cast<const f32x4*>(s.f0 + k0 + t.lg * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float pr = __expf(s[r] * p.scale + bias[r] - lse);
+                const float pr = __expf(sc[r] * scale + bias[r] - lse);
                 float d = dp[r];
-                if (do_drop) d = (rt_hash32(dseed, drop_row + (uint32_t)(k0 + lg * 4 + r)) >= thresh) ? d * ks : 0.f;
-                dsv[half * 4 + r] = pr * (d - delta) * p.scale;
+                if (drop.on) d = drop.keep(drop_row + (uint32_t)(c0 + k0 + t.lg * 4 + r)) ? d * drop.ks : 0.f;
+                dsv[half * 4 + r] = pr * (d - delta) * scale;
             }
         }
         const bf16x8 dsf = pack8(dsv);
-        const unsigned char* k0p = sK + (c * 32 + tr_r) * RS + tr_c;
+        const unsigned char* k0p = s.a + (c * 32 + t.tr_r) * RS + t.tr_c;
 #pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            const bf16x8 kf = tr_pair(k0p + t * 32, k0p + 16 * RS + t * 32);
-            dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, dsf, dq[t], 0, 0, 0);
-        }
-    }
-    if (q < p.Sq) {
-        bf16_t* drow = (bf16_t*)p.dq + ((size_t)b * p.Sq + q) * p.lddq + h * DH;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            bf16x4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)dq[t][r];
-            *reinterpret_cast<bf16x4*>(drow + t * 16 + lg * 4) = ov;
+        for (int d = 0; d < Geo<DH>::DT; ++d) {
+            const bf16x8 kf = rt_tr_frag(k0p + d * 32, k0p + 16 * RS + d * 32);
+            dq[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, dsf, dq[d], 0, 0, 0);
         }
     }
 }
 
-// ------------------------------------------------------------------------------------------------ dK, dV
-// OWN_DELTA: delta[i] = sum_d dO[i, d] * O[i, d] is recomputed here for the head's query rows (64-128 B of O and dO per row)
-// instead of being read from the dQ kernel's output: the two halves of the backward then do not depend on each other and run
-// as ONE launch (attn_bwd_fused_kernel) -- on the encoder's chain that is a 17 us kernel and a graph-node boundary less per layer.
-template <int DH, int NW, bool OWN_DELTA>
-__device__ __forceinline__ void attn_bwd_dkv_body(const rt_attn_bwd_desc& p, const int by) {
-    constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT, KH = Geo<DH>::KH;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Sqp = (p.Sq + 31) & ~31;
-    unsigned char* sQ = smem;
-    unsigned char* sD = sQ + (size_t)Sqp * RS;
-    float* sL = reinterpret_cast<float*>(sD + (size_t)Sqp * RS);
-    float* sDel = sL + Sqp;
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    stage_rows2<DH>(sQ, (const bf16_t*)p.q + (size_t)b * p.Sq * p.ldq + h * DH, p.ldq,
-                    sD, (const bf16_t*)p.dout + (size_t)b * p.Sq * p.ldo + h * DH, p.ldo, p.Sq, Sqp, threadIdx.x, 64 * NW);
-    for (int i = threadIdx.x; i < Sqp; i += 64 * NW) {
-        sL[i] = (i < p.Sq) ? p.lse[(size_t)bh * p.Sq + i] : INFINITY;       // padded query rows: p = exp(-inf) = 0
-        float del = 0.f;
-        if (i < p.Sq) {
-            if (OWN_DELTA) {
-                const bf16_t* orow = (const bf16_t*)p.out + ((size_t)b * p.Sq + i) * p.ldo + h * DH;
-                const bf16_t* drow = (const bf16_t*)p.dout + ((size_t)b * p.Sq + i) * p.ldo + h * DH;
-#pragma unroll
-                for (int c = 0; c < DH; c += 8) {
-                    const bf16x8 ov = *reinterpret_cast<const bf16x8*>(orow + c), dv8 = *reinterpret_cast<const bf16x8*>(drow + c);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) del += (float)dv8[e] * (float)ov[e];
-                }
-            } else {
-                del = p.delta[(size_t)bh * p.Sq + i];
-            }
-        }
-        sDel[i] = del;
+template <int DH, int NW, bool LONG>
+__device__ __forceinline__ void attn_bwd_dq_body(const rt_attn_bwd_desc& p, const int by, const int ch) {
+    constexpr int KH = Geo<DH>::KH;
+    const Lanes t = lanes(p.H);
+    const int Skp = (p.Sk + 31) & ~31;
+    const Lds<DH> s(LONG ? ch : Skp);
+    const KvSrc kv{p.k, p.v, p.kpm, p.Sk, p.ldk, p.ldv};
+    if constexpr (!LONG) {
+        stage_kv_bias<DH, NW, true>(s, kv, t, 0, Skp);
+        __syncthreads();
     }
-    __syncthreads();
-
-    const int key = by * (16 * NW) + wave * 16 + li;         // this lane's key (MFMA column)
-    if (by * (16 * NW) + wave * 16 >= p.Sk) return;
-    bf16x8 kf[KH], vf[KH];
-    load_bfrag<DH>((const bf16_t*)p.k + (size_t)b * p.Sk * p.ldk + h * DH, key, p.Sk, p.ldk, lg, kf);
-    load_bfrag<DH>((const bf16_t*)p.v + (size_t)b * p.Sk * p.ldv + h * DH, key, p.Sk, p.ldv, lg, vf);
-    const float kbias = (key < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + key])) ? 0.f : -INFINITY;
-
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
-    f32x4 dk[DT], dv[DT];
+    const int q = by * (16 * NW) + t.wave * 16 + t.li;
+    if (!LONG && by * (16 * NW) + t.wave * 16 >= p.Sq) return;
+    bf16x8 qf[KH], dof[KH], of[KH];
+    load_bfrag<DH>(head_rows<DH>(p.q, t, p.Sq, p.ldq), q, p.Sq, p.ldq, t.lg, qf);
+    load_bfrag<DH>(head_rows<DH>(p.dout, t, p.Sq, p.ldo), q, p.Sq, p.ldo, t.lg, dof);
+    load_bfrag<DH>(head_rows<DH>(p.out, t, p.Sq, p.ldo), q, p.Sq, p.ldo, t.lg, of);
+    float delta = 0.f;                          // from the fragments: each lane group holds a quarter of the row
 #pragma unroll
-    for (int t = 0; t < DT; ++t) { dk[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
-    for (int c = 0; c < (Sqp >> 5); ++c) {
+    for (int kh = 0; kh < KH; ++kh)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) delta += (float)dof[kh][e] * (float)of[kh][e];
+    delta = group_sum(delta);
+    const float lse = (q < p.Sq) ? p.lse[(size_t)t.bh * p.Sq + q] : INFINITY;
+    if (t.lg == 0 && q < p.Sq) p.delta[(size_t)t.bh * p.Sq + q] = delta;
+
+    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const uint32_t drop_row = (uint32_t)(((size_t)t.bh * p.Sq + q) * p.Sk);
+    f32x4 dq[Geo<DH>::DT];
+    zero_acc<DH>(dq);
+    if constexpr (!LONG) {
+        dq_chunk<DH>(s, Skp, 0, t, qf, dof, lse, delta, p.scale, drop, drop_row, dq);
+    } else {
+        for (int c0 = 0; c0 < Skp; c0 += ch) {          // one staged chunk at a time, behind a barrier
+            const int rows = (Skp - c0 < ch) ? Skp - c0 : ch;
+            __syncthreads();
+            stage_kv_bias<DH, NW, true>(s, kv, t, c0, rows);
+            __syncthreads();
+            dq_chunk<DH>(s, rows, c0, t, qf, dof, lse, delta, p.scale, drop, drop_row, dq);
+        }
+    }
+    if (q < p.Sq) store_rows<DH>((bf16_t*)p.dq + ((size_t)t.b * p.Sq + q) * p.lddq + t.h * DH, t.lg, dq);
+}
+
+// ------------------------------------------------------------------------------------------------ dK, dV
+// `rows` staged queries: P and dS of [query 4g+r][key li], dV^T += dO^T P, dK^T += Q^T dS
+template <int DH>
+__device__ __forceinline__ void dkv_chunk(const Lds<DH>& s, int rows, int c0, const Lanes& t, const bf16x8 (&kf)[Geo<DH>::KH],
+                                          const bf16x8 (&vf)[Geo<DH>::KH], float kbias, float scale, const Drop& drop, int Sq, int Sk, int key,
+                                          f32x4 (&dk)[Geo<DH>::DT], f32x4 (&dv)[Geo<DH>::DT]) {
+    constexpr int RS = Geo<DH>::RS;
+    for (int c = 0; c < (rows >> 5); ++c) {
         float pv[8], dsv[8];
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int q0 = c * 32 + half * 16;
-            const f32x4 s = tile_dot<DH>(sQ, q0, li, lg, kf);          // [query 4g+r][key li]
-            const f32x4 dp = tile_dot<DH>(sD, q0, li, lg, vf);
-            const f32x4 lse = *reinterpret_cast<const f32x4*>(sL + q0 + lg * 4);
-            const f32x4 del = *reinterpret_cast<const f32x4*>(sDel + q0 + lg * 4);
+            const f32x4 sc = tile_dot<DH>(s.a, q0, t.li, t.lg, kf);          // [query 4g+r][key li]
+            const f32x4 dp = tile_dot<DH>(s.b, q0, t.li, t.lg, vf);
+            const f32x4 lse = *reinterpret_cast<const f32x4*>(s.f0 + q0 + t.lg * 4);
+            const f32x4 del = *reinterpret_cast<const f32x4*>(s.f1 + q0 + t.lg * 4);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float pr = __expf(s[r] * p.scale + kbias - lse[r]);
+                const float pr = __expf(sc[r] * scale + kbias - lse[r]);
                 float d = dp[r], pd = pr;
-                if (do_drop) {
-                    const int qq = q0 + lg * 4 + r;
-                    const bool keep = rt_hash32(dseed, (uint32_t)(((size_t)bh * p.Sq + qq) * p.Sk + key)) >= thresh;
-                    d = keep ? d * ks : 0.f; pd = keep ? pr * ks : 0.f;
+                if (drop.on) {
+                    const int qq = c0 + q0 + t.lg * 4 + r;
+                    const bool keep = drop.keep((uint32_t)(((size_t)t.bh * Sq + qq) * Sk + key));
+                    d = keep ? d * drop.ks : 0.f; pd = keep ? pr * drop.ks : 0.f;
                 }
                 pv[half * 4 + r] = pd;
-                dsv[half * 4 + r] = pr * (d - del[r]) * p.scale;
+                dsv[half * 4 + r] = pr * (d - del[r]) * scale;
             }
         }
         const bf16x8 pf = pack8(pv), dsf = pack8(dsv);
-        const unsigned char* d0 = sD + (c * 32 + tr_r) * RS + tr_c;
-        const unsigned char* q0p = sQ + (c * 32 + tr_r) * RS + tr_c;
+        const unsigned char* d0 = s.b + (c * 32 + t.tr_r) * RS + t.tr_c;
+        const unsigned char* q0p = s.a + (c * 32 + t.tr_r) * RS + t.tr_c;
 #pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            const bf16x8 dof = tr_pair(d0 + t * 32, d0 + 16 * RS + t * 32);
-            dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof, pf, dv[t], 0, 0, 0);
-            const bf16x8 qtf = tr_pair(q0p + t * 32, q0p + 16 * RS + t * 32);
-            dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf, dsf, dk[t], 0, 0, 0);
+        for (int d = 0; d < Geo<DH>::DT; ++d) {
+            const bf16x8 dof = rt_tr_frag(d0 + d * 32, d0 + 16 * RS + d * 32);
+            dv[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof, pf, dv[d], 0, 0, 0);
+            const bf16x8 qtf = rt_tr_frag(q0p + d * 32, q0p + 16 * RS + d * 32);
+            dk[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf, dsf, dk[d], 0, 0, 0);
+        }
+    }
+}
+
+template <int DH, int NW, bool LONG, bool OWN_DELTA>
+__device__ __forceinline__ void attn_bwd_dkv_body(const rt_attn_bwd_desc& p, const int by, const int ch) {
+    constexpr int KH = Geo<DH>::KH;
+    const Lanes t = lanes(p.H);
+    const int Sqp = (p.Sq + 31) & ~31;
+    const Lds<DH> s(LONG ? ch : Sqp);
+    if constexpr (!LONG) {
+        stage_qdo_stats<DH, NW, OWN_DELTA>(s, p, t, 0, Sqp);
+        __syncthreads();
+    }
+    const int key = by * (16 * NW) + t.wave * 16 + t.li;         // this lane's key (MFMA column)
+    if (!LONG && by * (16 * NW) + t.wave * 16 >= p.Sk) return;
+    bf16x8 kf[KH], vf[KH];
+    load_bfrag<DH>(head_rows<DH>(p.k, t, p.Sk, p.ldk), key, p.Sk, p.ldk, t.lg, kf);
+    load_bfrag<DH>(head_rows<DH>(p.v, t, p.Sk, p.ldv), key, p.Sk, p.ldv, t.lg, vf);
+    const float kbias = (key < p.Sk && !(p.kpm && p.kpm[(size_t)t.b * p.Sk + key])) ? 0.f : -INFINITY;
+
+    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    f32x4 dk[Geo<DH>::DT], dv[Geo<DH>::DT];
+    zero_acc<DH>(dk);
+    zero_acc<DH>(dv);
+    if constexpr (!LONG) {
+        dkv_chunk<DH>(s, Sqp, 0, t, kf, vf, kbias, p.scale, drop, p.Sq, p.Sk, key, dk, dv);
+    } else {
+        for (int c0 = 0; c0 < Sqp; c0 += ch) {          // one staged chunk at a time, behind a barrier
+            const int rows = (Sqp - c0 < ch) ? Sqp - c0 : ch;
+            __syncthreads();
+            stage_qdo_stats<DH, NW, OWN_DELTA>(s, p, t, c0, rows);
+            __syncthreads();
+            dkv_chunk<DH>(s, rows, c0, t, kf, vf, kbias, p.scale, drop, p.Sq, p.Sk, key, dk, dv);
         }
     }
     if (key < p.Sk) {
-        bf16_t* kro = (bf16_t*)p.dk + ((size_t)b * p.Sk + key) * p.lddk + h * DH;
-        bf16_t* vro = (bf16_t*)p.dv + ((size_t)b * p.Sk + key) * p.lddv + h * DH;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            bf16x4 a, c2;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { a[r] = (bf16_t)dk[t][r]; c2[r] = (bf16_t)dv[t][r]; }
-            *reinterpret_cast<bf16x4*>(kro + t * 16 + lg * 4) = a;
-            *reinterpret_cast<bf16x4*>(vro + t * 16 + lg * 4) = c2;
-        }
+        store_rows<DH>((bf16_t*)p.dk + ((size_t)t.b * p.Sk + key) * p.lddk + t.h * DH, t.lg, dk);
+        store_rows<DH>((bf16_t*)p.dv + ((size_t)t.b * p.Sk + key) * p.lddv + t.h * DH, t.lg, dv);
     }
 }
 
 template <int DH, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dq_kernel(const rt_attn_bwd_desc p) {
-    attn_bwd_dq_body<DH, NW>(p, (int)blockIdx.y);
+    attn_bwd_dq_body<DH, NW, false>(p, (int)blockIdx.y, 0);
 }
 template <int DH, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_dkv_kernel(const rt_attn_bwd_desc p) {
-    attn_bwd_dkv_body<DH, NW, false>(p, (int)blockIdx.y);
+    attn_bwd_dkv_body<DH, NW, false, false>(p, (int)blockIdx.y, 0);
 }
 // both halves in one launch: blockIdx.y < ny_dq -> the dQ row blocks, the rest -> the dK / dV key blocks
 template <int DH, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_fused_kernel(const rt_attn_bwd_desc p, const int ny_dq) {
-    if ((int)blockIdx.y < ny_dq) attn_bwd_dq_body<DH, NW>(p, (int)blockIdx.y);
-    else attn_bwd_dkv_body<DH, NW, true>(p, (int)blockIdx.y - ny_dq);
+    if ((int)blockIdx.y < ny_dq) attn_bwd_dq_body<DH, NW, false>(p, (int)blockIdx.y, 0);
+    else attn_bwd_dkv_body<DH, NW, false, true>(p, (int)blockIdx.y - ny_dq, 0);
 }
 
 // ------------------------------------------------------------------------------------------------ long inner axes
 // Sequences whose K / V (forward, dQ) or Q / dO (dK, dV) rows do not fit the CU's 160 KB at once (--dilation at 640 x 640: c5 at
-// stride 16, S = 1600 + L): the inner axis is walked in chunks of LONG_CH rows, each staged into the same LDS region behind a
-// barrier.  Same lane <-> (query, key) assignment and the same key order per lane as the whole-axis kernels above -- the forward
-// is the two-pass kernel with each pass running over the chunks (pass 1 stages K only) -- so the results are bit-identical to
-// attn_fwd_kernel / the dq / dkv bodies wherever both apply (tests force this path on short sequences with a small chunk).
+// stride 16, S = 1600 + L): the bodies above with LONG = true walk the inner axis in chunks of `ch` <= LongGeo::CH rows, each staged
+// into the same LDS region behind a barrier, and hand every chunk to the SAME chunk functions the whole-axis kernels
+// call once -- same lane <-> (query, key) assignment, same key order per lane, the chunk's offset c0 entering only the dropout
+// index -- so the results are bit-identical to attn_fwd_kernel / the whole-axis dq / dkv bodies wherever both apply (tests force
+// this path on short sequences with a small chunk).  The dK / dV half always recomputes its delta (OWN_DELTA).
 template <int DH> struct LongGeo { static constexpr int CH = DH == 32 ? 768 : 448; };     // 2 * CH * RS + 8 * CH <= 160 KB
 
 template <int DH, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const rt_attn_desc p, const int ch) {
-    constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Skp = (p.Sk + 31) & ~31;
-    unsigned char* sK = smem;
-    unsigned char* sV = sK + (size_t)ch * RS;
-    float* sBias = reinterpret_cast<float*>(sV + (size_t)ch * RS);
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    const bf16_t* kbase = (const bf16_t*)p.k + (size_t)b * p.Sk * p.ldk + h * DH;
-    const bf16_t* vbase = (const bf16_t*)p.v + (size_t)b * p.Sk * p.ldv + h * DH;
-    const int q = blockIdx.y * (16 * NW) + wave * 16 + li;          // this lane's query (rows past Sq: zero fragments, never stored)
-    bf16x8 qf[Geo<DH>::KH];
-    load_bfrag<DH>((const bf16_t*)p.q + (size_t)b * p.Sq * p.ldq + h * DH, q, p.Sq, p.ldq, lg, qf);
-
-    float m = -INFINITY, l = 0.f;
-    for (int c0 = 0; c0 < Skp; c0 += ch) {
-        const int rows = (Skp - c0 < ch) ? Skp - c0 : ch;
-        const int valid = (p.Sk - c0 < rows) ? p.Sk - c0 : rows;
-        __syncthreads();
-        stage_rows<DH>(sK, kbase + (size_t)c0 * p.ldk, valid, rows, p.ldk, threadIdx.x, 64 * NW);
-        for (int j = threadIdx.x; j < rows; j += 64 * NW)
-            sBias[j] = (c0 + j < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + c0 + j])) ? 0.f : -INFINITY;
-        __syncthreads();
-        for (int blk = 0; blk < (rows >> 4); ++blk) {
-            const f32x4 acc = tile_dot<DH>(sK, blk * 16, li, lg, qf);
-            const f32x4 bias = *reinterpret_cast<const f32x4*>(sBias + blk * 16 + lg * 4);
-            float sc[4], mx = m;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { sc[r] = acc[r] * p.scale + bias[r]; mx = fmaxf(mx, sc[r]); }
-            const float ms = (mx == -INFINITY) ? 0.f : mx;
-            float add = 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) add += __expf(sc[r] - ms);
-            l = l * __expf(m - ms) + add;
-            m = mx;
-        }
-    }
-    float M = fmaxf(m, __shfl_xor(m, 16, 64));
-    M = fmaxf(M, __shfl_xor(M, 32, 64));
-    const float Ms = (M == -INFINITY) ? 0.f : M;
-    l *= __expf(m - Ms);
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv_l = 1.f / l;
-
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
-    const uint32_t drop_row = (uint32_t)(((size_t)bh * p.Sq + q) * p.Sk);
-    f32x4 o[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
-    for (int c0 = 0; c0 < Skp; c0 += ch) {
-        const int rows = (Skp - c0 < ch) ? Skp - c0 : ch;
-        const int valid = (p.Sk - c0 < rows) ? p.Sk - c0 : rows;
-        __syncthreads();
-        stage_rows2<DH>(sK, kbase + (size_t)c0 * p.ldk, p.ldk, sV, vbase + (size_t)c0 * p.ldv, p.ldv, valid, rows, threadIdx.x, 64 * NW);
-        for (int j = threadIdx.x; j < rows; j += 64 * NW)
-            sBias[j] = (c0 + j < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + c0 + j])) ? 0.f : -INFINITY;
-        __syncthreads();
-        for (int c = 0; c < (rows >> 5); ++c) {
-            float pv[8];
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int k0 = c * 32 + half * 16;
-                const f32x4 acc = tile_dot<DH>(sK, k0, li, lg, qf);
-                const f32x4 bias = *reinterpret_cast<const f32x4*>(sBias + k0 + lg * 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float pr = __expf(acc[r] * p.scale + bias[r] - Ms) * inv_l;
-                    if (do_drop) pr = (rt_hash32(dseed, drop_row + (uint32_t)(c0 + k0 + lg * 4 + r)) >= thresh) ? pr * ks : 0.f;
-                    pv[half * 4 + r] = pr;
-                }
-            }
-            const bf16x8 pf = pack8(pv);
-            const unsigned char* v0 = sV + (c * 32 + tr_r) * RS + tr_c;
-#pragma unroll
-            for (int t = 0; t < DT; ++t) {
-                const bf16x8 vf = tr_pair(v0 + t * 32, v0 + 16 * RS + t * 32);
-                o[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[t], 0, 0, 0);
-            }
-        }
-    }
-    if (q < p.Sq) {
-        bf16_t* orow = (bf16_t*)p.out + ((size_t)b * p.Sq + q) * p.ldo + h * DH;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            bf16x4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)o[t][r];
-            *reinterpret_cast<bf16x4*>(orow + t * 16 + lg * 4) = ov;
-        }
-        if (lg == 0 && p.lse) p.lse[(size_t)bh * p.Sq + q] = M + __logf(l);
-    }
+    attn_fwd_body<DH, NW, true>(p, ch);
 }
-
-template <int DH, int NW>
-__device__ __forceinline__ void attn_bwd_dq_long_body(const rt_attn_bwd_desc& p, const int by, const int ch) {
-    constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT, KH = Geo<DH>::KH;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Skp = (p.Sk + 31) & ~31;
-    unsigned char* sK = smem;
-    unsigned char* sV = sK + (size_t)ch * RS;
-    float* sBias = reinterpret_cast<float*>(sV + (size_t)ch * RS);
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    const bf16_t* kbase = (const bf16_t*)p.k + (size_t)b * p.Sk * p.ldk + h * DH;
-    const bf16_t* vbase = (const bf16_t*)p.v + (size_t)b * p.Sk * p.ldv + h * DH;
-    const int q = by * (16 * NW) + wave * 16 + li;
-    bf16x8 qf[KH], dof[KH], of[KH];
-    load_bfrag<DH>((const bf16_t*)p.q + (size_t)b * p.Sq * p.ldq + h * DH, q, p.Sq, p.ldq, lg, qf);
-    load_bfrag<DH>((const bf16_t*)p.dout + (size_t)b * p.Sq * p.ldo + h * DH, q, p.Sq, p.ldo, lg, dof);
-    load_bfrag<DH>((const bf16_t*)p.out + (size_t)b * p.Sq * p.ldo + h * DH, q, p.Sq, p.ldo, lg, of);
-    float delta = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < KH; ++kh)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) delta += (float)dof[kh][e] * (float)of[kh][e];
-    delta += __shfl_xor(delta, 16, 64);
-    delta += __shfl_xor(delta, 32, 64);
-    const float lse = (q < p.Sq) ? p.lse[(size_t)bh * p.Sq + q] : INFINITY;
-    if (lg == 0 && q < p.Sq) p.delta[(size_t)bh * p.Sq + q] = delta;
-
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
-    const uint32_t drop_row = (uint32_t)(((size_t)bh * p.Sq + q) * p.Sk);
-    f32x4 dq[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) dq[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
-    for (int c0 = 0; c0 < Skp; c0 += ch) {
-        const int rows = (Skp - c0 < ch) ? Skp - c0 : ch;
-        const int valid = (p.Sk - c0 < rows) ? p.Sk - c0 : rows;
-        __syncthreads();
-        stage_rows2<DH>(sK, kbase + (size_t)c0 * p.ldk, p.ldk, sV, vbase + (size_t)c0 * p.ldv, p.ldv, valid, rows, threadIdx.x, 64 * NW);
-        for (int j = threadIdx.x; j < rows; j += 64 * NW)
-            sBias[j] = (c0 + j < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + c0 + j])) ? 0.f : -INFINITY;
-        __syncthreads();
-        for (int c = 0; c < (rows >> 5); ++c) {
-            float dsv[8];
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int k0 = c * 32 + half * 16;
-                const f32x4 sc = tile_dot<DH>(sK, k0, li, lg, qf);
-                const f32x4 dp = tile_dot<DH>(sV, k0, li, lg, dof);
-                const f32x4 bias = *reinterpret_cast<const f32x4*>(sBias + k0 + lg * 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = __expf(sc[r] * p.scale + bias[r] - lse);
-                    float d = dp[r];
-                    if (do_drop) d = (rt_hash32(dseed, drop_row + (uint32_t)(c0 + k0 + lg * 4 + r)) >= thresh) ? d * ks : 0.f;
-                    dsv[half * 4 + r] = pr * (d - delta) * p.scale;
-                }
-            }
-            const bf16x8 dsf = pack8(dsv);
-            const unsigned char* k0p = sK + (c * 32 + tr_r) * RS + tr_c;
-#pragma unroll
-            for (int t = 0; t < DT; ++t) {
-                const bf16x8 kf = tr_pair(k0p + t * 32, k0p + 16 * RS + t * 32);
-                dq[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, dsf, dq[t], 0, 0, 0);
-            }
-        }
-    }
-    if (q < p.Sq) {
-        bf16_t* drow = (bf16_t*)p.dq + ((size_t)b * p.Sq + q) * p.lddq + h * DH;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            bf16x4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)dq[t][r];
-            *reinterpret_cast<bf16x4*>(drow + t * 16 + lg * 4) = ov;
-        }
-    }
-}
-
-template <int DH, int NW>
-__device__ __forceinline__ void attn_bwd_dkv_long_body(const rt_attn_bwd_desc& p, const int by, const int ch) {
-    constexpr int RS = Geo<DH>::RS, DT = Geo<DH>::DT, KH = Geo<DH>::KH;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int Sqp = (p.Sq + 31) & ~31;
-    unsigned char* sQ = smem;
-    unsigned char* sD = sQ + (size_t)ch * RS;
-    float* sL = reinterpret_cast<float*>(sD + (size_t)ch * RS);
-    float* sDel = sL + ch;
-    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lg = lane >> 4;
-    const bf16_t* qbase = (const bf16_t*)p.q + (size_t)b * p.Sq * p.ldq + h * DH;
-    const bf16_t* dbase = (const bf16_t*)p.dout + (size_t)b * p.Sq * p.ldo + h * DH;
-    const int key = by * (16 * NW) + wave * 16 + li;
-    bf16x8 kf[KH], vf[KH];
-    load_bfrag<DH>((const bf16_t*)p.k + (size_t)b * p.Sk * p.ldk + h * DH, key, p.Sk, p.ldk, lg, kf);
-    load_bfrag<DH>((const bf16_t*)p.v + (size_t)b * p.Sk * p.ldv + h * DH, key, p.Sk, p.ldv, lg, vf);
-    const float kbias = (key < p.Sk && !(p.kpm && p.kpm[(size_t)b * p.Sk + key])) ? 0.f : -INFINITY;
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
-    f32x4 dk[DT], dv[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) { dk[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    const int tr_r = 4 * lg + (li >> 2), tr_c = (li & 3) * 8;
-    for (int c0 = 0; c0 < Sqp; c0 += ch) {
-        const int rows = (Sqp - c0 < ch) ? Sqp - c0 : ch;
-        const int valid = (p.Sq - c0 < rows) ? p.Sq - c0 : rows;
-        __syncthreads();
-        stage_rows2<DH>(sQ, qbase + (size_t)c0 * p.ldq, p.ldq, sD, dbase + (size_t)c0 * p.ldo, p.ldo, valid, rows, threadIdx.x, 64 * NW);
-        for (int i = threadIdx.x; i < rows; i += 64 * NW) {
-            const int qi = c0 + i;
-            sL[i] = (qi < p.Sq) ? p.lse[(size_t)bh * p.Sq + qi] : INFINITY;
-            float del = 0.f;
-            if (qi < p.Sq) {                       // delta recomputed from the head's O / dO rows: independent of the dQ blocks
-                const bf16_t* orow = (const bf16_t*)p.out + ((size_t)b * p.Sq + qi) * p.ldo + h * DH;
-                const bf16_t* drow = dbase + (size_t)qi * p.ldo;
-#pragma unroll
-                for (int c = 0; c < DH; c += 8) {
-                    const bf16x8 ov = *reinterpret_cast<const bf16x8*>(orow + c), dv8 = *reinterpret_cast<const bf16x8*>(drow + c);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) del += (float)dv8[e] * (float)ov[e];
-                }
-            }
-            sDel[i] = del;
-        }
-        __syncthreads();
-        for (int c = 0; c < (rows >> 5); ++c) {
-            float pv[8], dsv[8];
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                const int q0 = c * 32 + half * 16;
-                const f32x4 sc = tile_dot<DH>(sQ, q0, li, lg, kf);
-                const f32x4 dp = tile_dot<DH>(sD, q0, li, lg, vf);
-                const f32x4 lse = *reinterpret_cast<const f32x4*>(sL + q0 + lg * 4);
-                const f32x4 del = *reinterpret_cast<const f32x4*>(sDel + q0 + lg * 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = __expf(sc[r] * p.scale + kbias - lse[r]);
-                    float d = dp[r], pd = pr;
-                    if (do_drop) {
-                        const int qq = c0 + q0 + lg * 4 + r;
-                        const bool keep = rt_hash32(dseed, (uint32_t)(((size_t)bh * p.Sq + qq) * p.Sk + key)) >= thresh;
-                        d = keep ? d * ks : 0.f; pd = keep ? pr * ks : 0.f;
-                    }
-                    pv[half * 4 + r] = pd;
-                    dsv[half * 4 + r] = pr * (d - del[r]) * p.scale;
-                }
-            }
-            const bf16x8 pf = pack8(pv), dsf = pack8(dsv);
-            const unsigned char* d0 = sD + (c * 32 + tr_r) * RS + tr_c;
-            const unsigned char* q0p = sQ + (c * 32 + tr_r) * RS + tr_c;
-#pragma unroll
-            for (int t = 0; t < DT; ++t) {
-                const bf16x8 dof = tr_pair(d0 + t * 32, d0 + 16 * RS + t * 32);
-                dv[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dof, pf, dv[t], 0, 0, 0);
-                const bf16x8 qtf = tr_pair(q0p + t * 32, q0p + 16 * RS + t * 32);
-                dk[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qtf, dsf, dk[t], 0, 0, 0);
-            }
-        }
-    }
-    if (key < p.Sk) {
-        bf16_t* kro = (bf16_t*)p.dk + ((size_t)b * p.Sk + key) * p.lddk + h * DH;
-        bf16_t* vro = (bf16_t*)p.dv + ((size_t)b * p.Sk + key) * p.lddv + h * DH;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) {
-            bf16x4 a, c2;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { a[r] = (bf16_t)dk[t][r]; c2[r] = (bf16_t)dv[t][r]; }
-            *reinterpret_cast<bf16x4*>(kro + t * 16 + lg * 4) = a;
-            *reinterpret_cast<bf16x4*>(vro + t * 16 + lg * 4) = c2;
-        }
-    }
-}
-
 // both halves in one launch, as attn_bwd_fused_kernel: blockIdx.y < ny_dq -> the dQ row blocks, the rest -> the dK / dV key blocks
 template <int DH, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_bwd_long_kernel(const rt_attn_bwd_desc p, const int ny_dq, const int ch) {
-    if ((int)blockIdx.y < ny_dq) attn_bwd_dq_long_body<DH, NW>(p, (int)blockIdx.y, ch);
-    else attn_bwd_dkv_long_body<DH, NW>(p, (int)blockIdx.y - ny_dq, ch);
+    if ((int)blockIdx.y < ny_dq) attn_bwd_dq_body<DH, NW, true>(p, (int)blockIdx.y, ch);
+    else attn_bwd_dkv_body<DH, NW, true, true>(p, (int)blockIdx.y - ny_dq, ch);
 }
 
 // Opt a kernel into the full 160 KiB of dynamic LDS once per kernel (not per launch: keeps launches capturable in a
@@ -924,10 +769,7 @@ __global__ __launch_bounds__(256) void attn_q1_fwd_kernel(const rt_attn_desc p) 
     l = red[4] + red[5] + red[6] + red[7];
     const float inv_l = 1.f / l;                 // fully masked row: NaN below, as the reference
     if (t == 0 && p.lse) p.lse[bh] = ms + __logf(l);
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
+    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     float o[32];
 #pragma unroll
     for (int d = 0; d < 32; ++d) o[d] = 0.f;
@@ -936,7 +778,7 @@ __global__ __launch_bounds__(256) void attn_q1_fwd_kernel(const rt_attn_desc p) 
         const int j = t + i * 256;
         if (j >= p.Sk) continue;
         float pr = sc[i] * inv_l;
-        if (do_drop) pr = (rt_hash32(dseed, (uint32_t)((size_t)bh * p.Sk + j)) >= thresh) ? pr * ks : 0.f;
+        if (drop.on) pr = drop.keep((uint32_t)((size_t)bh * p.Sk + j)) ? pr * drop.ks : 0.f;
         if (pr != 0.f || pr != pr) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -974,10 +816,7 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const rt_attn_bwd_desc
 #pragma unroll
     for (int d = 0; d < 32; ++d) delta += go[d] * ov[d];
     const float lse = p.lse[bh];
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t dseed = rt_site_seed(p.seed_dev, p.drop_seed);
+    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     float dq[32];
 #pragma unroll
     for (int d = 0; d < 32; ++d) dq[d] = 0.f;
@@ -987,7 +826,7 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const rt_attn_bwd_desc
         if (j >= p.Sk) continue;
         const float pr = ok[i] ? __expf(q1_dot(kr[i], q) * p.scale - lse) : 0.f;
         float mk = 1.f;
-        if (do_drop) mk = (rt_hash32(dseed, (uint32_t)((size_t)bh * p.Sk + j)) >= thresh) ? ks : 0.f;
+        if (drop.on) mk = drop.keep((uint32_t)((size_t)bh * p.Sk + j)) ? drop.ks : 0.f;
         const float dp = q1_dot(vr[i], go);
         const float ds = pr * (mk * dp - delta) * p.scale;
         const float pd = pr * mk;

@@ -19,22 +19,11 @@
 // LDS staging pass.  Rounding points are those of the rt_conv_gemm launches it replaces (bf16 h1, h2, downsample output, out;
 // fp32 accumulate, bias, residual, ReLU): the two paths differ by summation order only.
 #include "rt_common.h"
+#include "rt_lds.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-__device__ __forceinline__ i32x4 bk_rsrc(const void* ptr, unsigned bytes) {
-    const uint64_t a = (uint64_t)ptr;
-    return i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)bytes, 0x00020000};
-}
-// 16 B per lane, global -> LDS: lane l lands at lds_base + 16 l (lds_base wave-uniform); out-of-range offsets write zeros
-__device__ __forceinline__ void bk_dma16(const i32x4 rsrc, unsigned lds_base, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 ::"s"(lds_base), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory", "m0");
-}
 // wait until at most n vector-memory operations of this wave are outstanding (n is a compile-time constant after unrolling)
 __device__ __forceinline__ void bk_wait(int n) {
     switch (n) {
@@ -102,28 +91,28 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void bottleneck_fwd_kerne
         w2_off[j] = (ch * 576 + chunk * 8) * 2;
         w3_off[j] = (ch * 64 + chunk * 8) * 2;
     }
-    const i32x4 rs_x = bk_rsrc(p.x, p.x_bytes), rs_w1 = bk_rsrc(p.w1, 64 * CIN * 2), rs_w2 = bk_rsrc(p.w2, 64 * 576 * 2),
-                rs_w3 = bk_rsrc(p.w3, 256 * 64 * 2), rs_wd = bk_rsrc(DOWN ? p.wd : p.w3, 256 * 64 * 2);
+    const i32x4 rs_x = rt_make_rsrc(p.x, p.x_bytes), rs_w1 = rt_make_rsrc(p.w1, 64 * CIN * 2), rs_w2 = rt_make_rsrc(p.w2, 64 * 576 * 2),
+                rs_w3 = rt_make_rsrc(p.w3, 256 * 64 * 2), rs_wd = rt_make_rsrc(DOWN ? p.wd : p.w3, 256 * 64 * 2);
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
 
     auto issue_x = [&](int kc) __attribute__((always_inline)) {
         const unsigned base = lds0 + (kc & 1) * XSLOT;
 #pragma unroll
-        for (int j = 0; j < LX; ++j) bk_dma16(rs_x, base + j * PASS, x_off[j], kc * 128);
+        for (int j = 0; j < LX; ++j) rt_dma16(rs_x, base + j * PASS, x_off[j], kc * 128);
     };
     auto issue_w = [&](int pc) __attribute__((always_inline)) {      // pc is a compile-time constant at every call site
         const unsigned base = lds0 + WR_OFF + (pc & (R - 1)) * BK_WSLOT;
         if (pc < NK1) {
 #pragma unroll
-            for (int j = 0; j < LW; ++j) bk_dma16(rs_w1, base + j * PASS, w1_off[j], pc * 128);
+            for (int j = 0; j < LW; ++j) rt_dma16(rs_w1, base + j * PASS, w1_off[j], pc * 128);
         } else if (pc < NK1 + 9) {
 #pragma unroll
-            for (int j = 0; j < LW; ++j) bk_dma16(rs_w2, base + j * PASS, w2_off[j], (pc - NK1) * 128);
+            for (int j = 0; j < LW; ++j) rt_dma16(rs_w2, base + j * PASS, w2_off[j], (pc - NK1) * 128);
         } else {
             const int i = pc - NK1 - 9, q = DOWN ? i >> 1 : i;
             const bool dn = DOWN && (i & 1);
 #pragma unroll
-            for (int j = 0; j < LW; ++j) bk_dma16(dn ? rs_wd : rs_w3, base + j * PASS, w3_off[j], q * 8192);
+            for (int j = 0; j < LW; ++j) rt_dma16(dn ? rs_wd : rs_w3, base + j * PASS, w3_off[j], q * 8192);
         }
     };
     // A fragments (weights) of piece pc: 4 feature tiles x 2 K halves

@@ -80,6 +80,14 @@ __device__ __forceinline__ float rt_block_sum(float v, float* sm) {
     return r;
 }
 
+// Row map of the grouped / broadcast row layouts (norm and fused-add descriptors):
+// grp_rows > 0: (r / g) * stride + off + r % g;  grp_rows < 0: broadcast (r / -g) * stride + off;  0: identity
+__device__ __forceinline__ int rt_map_row(int r, int grp_rows, int grp_stride, int grp_off) {
+    if (grp_rows > 0) return (r / grp_rows) * grp_stride + grp_off + (r % grp_rows);
+    if (grp_rows < 0) return (r / (-grp_rows)) * grp_stride + grp_off;
+    return r;
+}
+
 // Small fp32 workspaces are cleared with a KERNEL, not hipMemsetAsync: inside a captured hipGraph (ROCm 7.2) memset
 // nodes were observed to race with the kernel nodes that follow them (intermittent garbage statistics / losses),
 // while kernel -> kernel ordering on the captured stream is reliable.

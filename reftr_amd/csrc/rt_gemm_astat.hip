@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void gemm_astat_kernel(const bf16_t* __rest
             for (int i = t; i < 64 * nt; i += 256) {
                 const int m = m0 + (i & 63), n = (jt0 + (i >> 6)) * BN;
                 const int off = (m < p.M && n < p.N) ? (m * p.N + n) * 2 : OOB;
-                asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" ::"s"(scratch), "v"(off), "s"(rs) : "memory", "m0");
+                rt_dma4(rs, scratch, off);
             }
         };
         touch(p.res_bf16);

@@ -2,33 +2,18 @@
 // tile / schedule variants in parallel translation units).  Internal to the library.
 #pragma once
 #include "rt_gemm_common.h"
+#include "rt_lds.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// LDS-DMA variant: operand tiles go global -> LDS directly (buffer_load_dwordx4 ... lds), never through VGPRs, so
+// LDS-DMA variant: operand tiles go global -> LDS directly (rt_dma16, rt_lds.h), never through VGPRs, so
 // the ds_write half of the LDS pipe (~80 B/clk/CU, as expensive as the MFMAs of a 128x128x64 tile) disappears and
-// NS tiles can be in flight without holding staging registers.  The DMA writes lane l of a wave instruction to
-// LDS base + 16*l (lane-linear), so the XOR swizzle is applied on the SOURCE side: lane l (row l>>3 of an 8-row
-// group, slot l&7) fetches K chunk (l&7)^(l>>3) of its row.  Out-of-range offsets make the DMA write zeros.
-// Completion is tracked with explicit counted vmcnt waits (the compiler cannot tell which stage a ds_read aliases).
-template <int N> __device__ __forceinline__ void rt_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-__device__ __forceinline__ i32x4 rt_make_rsrc(const void* ptr, unsigned bytes) {
-    const uint64_t a = (uint64_t)ptr;
-    return i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)bytes, 0x00020000};   // stride 0, raw buffer
-}
-// One 16-B-per-lane global -> LDS DMA: lane l lands at LDS byte address lds_base + 16*l (lds_base wave-uniform).
-// Issued as inline asm so that the compiler's waitcnt pass does not turn every later ds_read into vmcnt(0).
-__device__ __forceinline__ void rt_dma16(const i32x4 rsrc, unsigned lds_base, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 ::"s"(lds_base), "v"(voff), "s"(rsrc), "s"(soff)
-                 : "memory", "m0");
-}
+// NS tiles can be in flight without holding staging registers.  The landing is lane-linear, so the XOR swizzle is
+// applied on the SOURCE side: lane l (row l>>3 of an 8-row group, slot l&7) fetches K chunk (l&7)^(l>>3) of its row.
+// Completion is tracked with the counted waits (rt_wait_vmcnt).
 
 // The body is a device function: it runs as a kernel of its own (conv_gemm_dma_kernel) or as one of up to 12 independent
 // problems of a grouped launch (conv_gemm_dma_grouped_kernel); bx / by / gx stand for blockIdx.x / blockIdx.y / gridDim.x.

@@ -4,13 +4,6 @@
 
 namespace {
 
-// grp_rows > 0: (r / g) * stride + off + r % g;  grp_rows < 0: broadcast (r / -g) * stride + off;  0: identity
-__device__ __forceinline__ int map_row(int r, int grp_rows, int grp_stride, int grp_off) {
-    if (grp_rows > 0) return (r / grp_rows) * grp_stride + grp_off + (r % grp_rows);
-    if (grp_rows < 0) return (r / (-grp_rows)) * grp_stride + grp_off;
-    return r;
-}
-
 // ---------------------------------------------------------------- column sums (bias gradients)
 // db[n] += sum_m dy[m, n]; block = 64 columns x 4 row-lanes, grid.y splits the rows.
 template <typename T>
@@ -38,11 +31,11 @@ __global__ __launch_bounds__(256) void rows_add_kernel(const rt_rows_add_desc p)
         const int c = (int)(i % p.D);
         const int r = (int)(i / p.D);
         float v = 0.f;
-        if (p.a_f32) v += p.a_f32[(size_t)map_row(r, p.a_grp_rows, p.a_grp_stride, p.a_grp_off) * p.D + c];
-        if (p.a_bf16) v += (float)((const bf16_t*)p.a_bf16)[(size_t)map_row(r, p.a_grp_rows, p.a_grp_stride, p.a_grp_off) * p.D + c];
-        if (p.b_f32) v += p.b_f32[(size_t)map_row(r, p.b_grp_rows, p.b_grp_stride, p.b_grp_off) * p.D + c];
+        if (p.a_f32) v += p.a_f32[(size_t)rt_map_row(r, p.a_grp_rows, p.a_grp_stride, p.a_grp_off) * p.D + c];
+        if (p.a_bf16) v += (float)((const bf16_t*)p.a_bf16)[(size_t)rt_map_row(r, p.a_grp_rows, p.a_grp_stride, p.a_grp_off) * p.D + c];
+        if (p.b_f32) v += p.b_f32[(size_t)rt_map_row(r, p.b_grp_rows, p.b_grp_stride, p.b_grp_off) * p.D + c];
         v *= p.alpha;
-        const size_t o = (size_t)map_row(r, p.o_grp_rows, p.o_grp_stride, p.o_grp_off) * p.D + c;
+        const size_t o = (size_t)rt_map_row(r, p.o_grp_rows, p.o_grp_stride, p.o_grp_off) * p.D + c;
         if (p.out_f32) {
             if (p.accumulate == 2) atomicAdd(p.out_f32 + o, v);
             else if (p.accumulate) p.out_f32[o] += v;

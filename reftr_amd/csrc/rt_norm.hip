@@ -9,12 +9,6 @@ namespace {
 constexpr int LN_MAX_PER_LANE = 16;   // D <= 1024
 constexpr int GN_BWD_PIX = 32;        // pixels per workgroup of the backward statistics kernel (8 loads in flight per thread)
 
-__device__ __forceinline__ int map_row(int r, int grp_rows, int grp_stride, int grp_off) {
-    if (grp_rows > 0) return (r / grp_rows) * grp_stride + grp_off + (r % grp_rows);
-    if (grp_rows < 0) return (r / (-grp_rows)) * grp_stride + grp_off;
-    return r;
-}
-
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const rt_layernorm_desc p) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -40,7 +34,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const rt_layernorm_d
     }
     const float rstd = rsqrtf(rt_wave_sum(ss) / D + p.eps);
     if (lane == 0) { if (p.mean) p.mean[row] = mean; if (p.rstd) p.rstd[row] = rstd; }
-    const int orow = map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
+    const int orow = rt_map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
     const bool do_drop = p.drop_p > 0.f;
     const uint32_t thresh = rt_drop_thresh(p.drop_p);
     const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
@@ -80,7 +74,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const rt_layernorm_b
     bf16_t* dxb = (bf16_t*)p.dx_bf16;
 
     for (int row = blockIdx.x * 4 + wave; row < p.M; row += gridDim.x * 4) {
-        const int orow = map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
+        const int orow = rt_map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
         const float mean = p.mean[row], rstd = p.rstd[row];
         const float* xr = p.x + (size_t)row * D;
         float xh[LN_MAX_PER_LANE], g[LN_MAX_PER_LANE];
@@ -150,7 +144,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const rt_layerno
     f32x4 v[V];
     // every load of the kernel is requested up front (one round trip): the affine parameters and the positional rows do not depend
     // on the statistics, but sit behind the mean / rstd stores in program order (possible aliasing), where the compiler leaves them
-    const int orow = map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
+    const int orow = rt_map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
     f32x4 gam_[V], bet_[V], pos_[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) {
@@ -230,7 +224,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const rt_layerno
 
     for (int row = blockIdx.x * 4 + wave; row < p.M; row += gridDim.x * 4) {
 #pragma clang fp contract(off)      // rt_decoder_bwd repeats this arithmetic and must round the same way: no fused multiply-adds
-        const int orow = map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
+        const int orow = rt_map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
         const float mean = p.mean[row], rstd = p.rstd[row];
         const f32x4* xr = reinterpret_cast<const f32x4*>(p.x + (size_t)row * D);
         const f32x4* dyr = reinterpret_cast<const f32x4*>(p.dy + (size_t)orow * D);

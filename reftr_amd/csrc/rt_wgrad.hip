@@ -12,6 +12,7 @@
 // The m axis is split across blockIdx.y; partial tiles are accumulated with fp32 global atomics into the
 // (pre-zeroed) flat gradient buffer.
 #include "rt_common.h"
+#include "rt_lds.h"
 #include <stdlib.h>
 
 namespace {
@@ -24,15 +25,6 @@ struct WgradArgs {
     int overwrite;            // single-writer launches (one split, no workspace) store instead of accumulating
     unsigned dy_bytes, x_bytes;
 };
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base, int off0, int off1) {
-    typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + off0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + off1));
-    union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-    u.s.a = lo; u.s.b = hi;
-    return u.v;
-}
 
 // SIMPLE: 1x1 / stride 1 / pad 0 (x row = m).  NVEC: N % 8 == 0 (16-B dy loads).
 template <int BN, int BC, bool SIMPLE, bool NVEC>
@@ -157,12 +149,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
 #pragma unroll
         for (int a = 0; a < TN; ++a) {
             const int colb = (wn * (BN / 2) + a * 16) * 2 + tr_col;
-            af[a] = tr_frag(bA, tr_row0 * SA + colb, (tr_row0 + 16) * SA + colb);
+            af[a] = rt_tr_frag(bA + tr_row0 * SA + colb, bA + (tr_row0 + 16) * SA + colb);
         }
 #pragma unroll
         for (int b = 0; b < TC; ++b) {
             const int colb = (wc * (BC / 2) + b * 16) * 2 + tr_col;
-            bfr[b] = tr_frag(bB, tr_row0 * SB + colb, (tr_row0 + 16) * SB + colb);
+            bfr[b] = rt_tr_frag(bB + tr_row0 * SB + colb, bB + (tr_row0 + 16) * SB + colb);
         }
 #pragma unroll
         for (int a = 0; a < TN; ++a)
@@ -228,17 +220,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
 // SIMPLE operands are addressed through a buffer descriptor that is re-based per chunk with scalar arithmetic (base +=
 // chunk bytes, num_records -= chunk bytes): the per-lane offsets are loop-invariant and the ragged tail rows fall off
 // the end of the descriptor, i.e. read as zeros.
-template <int N> __device__ __forceinline__ void wg_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-typedef __attribute__((ext_vector_type(4))) int wg_i32x4;
-__device__ __forceinline__ wg_i32x4 wg_make_rsrc(const void* ptr, unsigned bytes) {
-    const uint64_t a = (uint64_t)ptr;
-    return wg_i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)bytes, 0x00020000};
-}
-__device__ __forceinline__ void wg_dma16(const wg_i32x4 rsrc, unsigned lds_base, int voff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                 ::"s"(lds_base), "v"(voff), "s"(rsrc)
-                 : "memory", "m0");
-}
 template <int RB> __device__ __forceinline__ int wg_swz(int row) {      // XOR applied to the 16-B slot index
     return RB >= 256 ? ((row & 7) << 1) : (((row >> 1) & 3) << 1);
 }
@@ -317,21 +298,21 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
     float bsum = 0.f;
 
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
-    const wg_i32x4 rs_x_abs = wg_make_rsrc(xp, p.x_bytes);
+    const i32x4 rs_x_abs = rt_make_rsrc(xp, p.x_bytes);
     int lc = chunk_begin;
 
     auto issue = [&](int stage) __attribute__((always_inline)) {
         const unsigned bA = lds0 + stage * BUF_BYTES, bB = bA + A_BYTES;
         const unsigned aoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.N;
-        const wg_i32x4 rs_dy = wg_make_rsrc(reinterpret_cast<const unsigned char*>(dyp) + aoff, p.dy_bytes - aoff);
+        const i32x4 rs_dy = rt_make_rsrc(reinterpret_cast<const unsigned char*>(dyp) + aoff, p.dy_bytes - aoff);
 #pragma unroll
-        for (int j = 0; j < AJ; ++j) wg_dma16(rs_dy, bA + j * 4096, voff_a[j]);
+        for (int j = 0; j < AJ; ++j) rt_dma16(rs_dy, bA + j * 4096, voff_a[j]);
         const bool last = (lc + 1 >= chunk_end);
         if (SIMPLE) {
             const unsigned xoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.SC;
-            const wg_i32x4 rs_x = wg_make_rsrc(reinterpret_cast<const unsigned char*>(xp) + xoff, p.x_bytes - xoff);
+            const i32x4 rs_x = rt_make_rsrc(reinterpret_cast<const unsigned char*>(xp) + xoff, p.x_bytes - xoff);
 #pragma unroll
-            for (int j = 0; j < BJ; ++j) wg_dma16(rs_x, bB + j * 4096, voff_b[j]);
+            for (int j = 0; j < BJ; ++j) rt_dma16(rs_x, bB + j * 4096, voff_b[j]);
         } else {
 #pragma unroll
             for (int j = 0; j < BJ; ++j) {
@@ -339,7 +320,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
                 const int sy = gy[j] * p.stride - p.pad + kh * p.dil, sx = gx[j] * p.stride - p.pad + kw * p.dil;
                 const bool ok = m < p.M && (unsigned)sy < (unsigned)p.SH && (unsigned)sx < (unsigned)p.SW && voff_b[j] != OOB;
                 const int pix = (gb[j] * p.SH + sy) * p.SW + sx;
-                wg_dma16(rs_x_abs, bB + j * 4096, ok ? pix * p.SC * 2 + voff_b[j] : OOB);
+                rt_dma16(rs_x_abs, bB + j * 4096, ok ? pix * p.SC * 2 + voff_b[j] : OOB);
                 if (!last) {
                     gx[j] += CR;
                     while (gx[j] >= p.DW) { gx[j] -= p.DW; if (++gy[j] >= p.DH) { gy[j] = 0; ++gb[j]; } }
@@ -370,9 +351,9 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
         for (int kk = 0; kk < KS; ++kk) {
             bf16x8 af[TN], bfr[TC];
 #pragma unroll
-            for (int a = 0; a < TN; ++a) af[a] = tr_frag(bA, addr_a[a] + kk * 32 * RBA, addr_a[a] + (kk * 32 + 16) * RBA);
+            for (int a = 0; a < TN; ++a) af[a] = rt_tr_frag(bA + addr_a[a] + kk * 32 * RBA, bA + addr_a[a] + (kk * 32 + 16) * RBA);
 #pragma unroll
-            for (int b = 0; b < TC; ++b) bfr[b] = tr_frag(bB, addr_b[b] + kk * 32 * RBB, addr_b[b] + (kk * 32 + 16) * RBB);
+            for (int b = 0; b < TC; ++b) bfr[b] = rt_tr_frag(bB + addr_b[b] + kk * 32 * RBB, bB + addr_b[b] + (kk * 32 + 16) * RBB);
 #pragma unroll
             for (int a = 0; a < TN; ++a)
 #pragma unroll
@@ -397,7 +378,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
     if (p.early) {          // issue-before-wait (see rt_gemm.hip): NS-1 chunks in flight while parked, two barriers per chunk
         for (int c = 0; c < nch; ++c) {
             issue(lbuf);
-            wg_wait_vmcnt<(NS - 1) * LPT>();
+            rt_wait_vmcnt<(NS - 1) * LPT>();
             __syncthreads();
             compute(cbuf);
             __syncthreads();
@@ -406,7 +387,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
         }
     } else {
         for (int c = 0; c < nch; ++c) {
-            wg_wait_vmcnt<(NS - 2) * LPT>();
+            rt_wait_vmcnt<(NS - 2) * LPT>();
             __syncthreads();
             issue(lbuf);
             compute(cbuf);
@@ -414,7 +395,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
             lbuf = lbuf + 1 == NS ? 0 : lbuf + 1;
         }
     }
-    wg_wait_vmcnt<0>();
+    rt_wait_vmcnt<0>();
 
     if (do_bias) {
         const int n = n0 + t % BN;

@@ -27,13 +27,13 @@
 // (ds_read_b64_tr_b16).  The DMA cannot scatter, so the bank swizzle (16-B slot ^= (row & 3) << 2: the four rows x 64 B a
 // 32-lane half of the transpose read touches land on four different 64-B bank groups) is applied to the SOURCE address.
 #include "rt_common.h"
+#include "rt_lds.h"
 #include <stdlib.h>
 #include <stdio.h>
 
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) int w2_i32x4;
 
 struct W2Prob {
     const bf16_t* dy; const bf16_t* x; float* dw; const float* scale; float* dbias; float* part; float* sqacc; bf16_t* g16;
@@ -46,35 +46,7 @@ constexpr int W2_MAXP = 20;
 // cum[x][i]: workgroups of problems 0 .. i-1 that run on XCD x (block id b -> XCD b & 7, position b >> 3 in its order)
 struct W2Group { W2Prob p[W2_MAXP]; int cum[8][W2_MAXP + 1]; int n; int xcd; int abl; int pf; int remap; };
 
-template <int N> __device__ __forceinline__ void w2_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ w2_i32x4 w2_rsrc(const void* ptr, unsigned bytes) {
-    const uint64_t a = (uint64_t)ptr;
-    return w2_i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)bytes, 0x00020000};
-}
-__device__ __forceinline__ w2_i32x4 w2_rsrc_uniform(const void* ptr, unsigned bytes) {     // forces the descriptor into SGPRs
-    const uint64_t a = (uint64_t)ptr;
-    return w2_i32x4{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)),
-                    __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-}
-__device__ __forceinline__ void w2_dma16(const w2_i32x4 rsrc, unsigned lds_base, int voff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-                 ::"s"(lds_base), "v"(voff), "s"(rsrc)
-                 : "memory", "m0");
-}
-__device__ __forceinline__ void w2_dma4(const w2_i32x4 rsrc, unsigned lds_base, int voff) {      // 4 B per lane: the L2 prefetch touch
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds"
-                 ::"s"(lds_base), "v"(voff), "s"(rsrc)
-                 : "memory", "m0");
-}
 __device__ __forceinline__ int w2_swz(int row) { return (row & 3) << 2; }
-__device__ __forceinline__ bf16x8 w2_frag2(const unsigned char* base, int off0, int off1) {
-    typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + off0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + off1));
-    union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-    u.s.a = lo; u.s.b = hi;
-    return u.v;
-}
 
 // BN x BC output tile, WN x WC waves (WN * WC == 8), CR contraction rows per stage, NS stages.
 // TAPS = 3 (3x3, stride 1, pad 1 only): a workgroup accumulates the three kw taps of ONE kernel row kh of its output tile.  For a
@@ -208,15 +180,15 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
 
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)(wave & 3) * 1024u;
     const unsigned lds_pf = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)(NS * BUF_BYTES) + (unsigned)(wave & 3) * 256u;
-    const w2_i32x4 rs_x_abs = w2_rsrc(p.x, p.x_bytes);
+    const i32x4 rs_x_abs = rt_make_rsrc(p.x, p.x_bytes);
     int lc = chunk_begin;
 
     auto issue_dma = [&](int stage) __attribute__((always_inline)) {             // waves 0-3
         const unsigned bA = lds0 + stage * BUF_BYTES, bB = bA + A_BYTES;
         const unsigned aoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.N;
-        const w2_i32x4 rs_dy = w2_rsrc(reinterpret_cast<const unsigned char*>(p.dy) + aoff, p.dy_bytes - aoff);
+        const i32x4 rs_dy = rt_make_rsrc(reinterpret_cast<const unsigned char*>(p.dy) + aoff, p.dy_bytes - aoff);
 #pragma unroll
-        for (int j = 0; j < AJ; ++j) w2_dma16(rs_dy, bA + j * 4096, voff_a[j]);
+        for (int j = 0; j < AJ; ++j) rt_dma16(rs_dy, bA + j * 4096, voff_a[j]);
         const bool last = (lc + 1 >= chunk_end);
         if (FUSED) {
             // rows g0 .. g0 + 33 of x (flat pixel index, may start before the tensor / end behind it: those rows read as zero)
@@ -225,13 +197,13 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
             for (int j = 0; j < BJ; ++j) {
                 int off = voff_b[j] == OOB ? OOB : base + voff_b[j];
                 if (off < 0) off = OOB;
-                w2_dma16(rs_x_abs, bB + j * 4096, off);
+                rt_dma16(rs_x_abs, bB + j * 4096, off);
             }
         } else if (SIMPLE) {
             const unsigned xoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.SC;
-            const w2_i32x4 rs_x = w2_rsrc(reinterpret_cast<const unsigned char*>(p.x) + xoff, p.x_bytes - xoff);
+            const i32x4 rs_x = rt_make_rsrc(reinterpret_cast<const unsigned char*>(p.x) + xoff, p.x_bytes - xoff);
 #pragma unroll
-            for (int j = 0; j < BJ; ++j) w2_dma16(rs_x, bB + j * 4096, voff_b[j]);
+            for (int j = 0; j < BJ; ++j) rt_dma16(rs_x, bB + j * 4096, voff_b[j]);
         } else {
 #pragma unroll
             for (int j = 0; j < BJ; ++j) {
@@ -239,7 +211,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
                 const int sy = gy[j] * p.stride - p.pad + kh * p.dil, sx = gx[j] * p.stride - p.pad + kw * p.dil;
                 const bool ok = m < p.M && (unsigned)sy < (unsigned)p.SH && (unsigned)sx < (unsigned)p.SW && voff_b[j] != OOB;
                 const int pix = (gb[j] * p.SH + sy) * p.SW + sx;
-                w2_dma16(rs_x_abs, bB + j * 4096, ok ? pix * p.SC * 2 + voff_b[j] : OOB);
+                rt_dma16(rs_x_abs, bB + j * 4096, ok ? pix * p.SC * 2 + voff_b[j] : OOB);
                 if (!last) {
                     gx[j] += CR;
                     while (gx[j] >= p.DW) { gx[j] -= p.DW; if (++gy[j] >= p.DH) { gy[j] = 0; ++gb[j]; } }
@@ -253,13 +225,13 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
         const bool on = pc < chunk_end;                     // wave-uniform: the descriptor below must live in SGPRs
         if (pf_is_a) {
             const unsigned off = (unsigned)pc * (unsigned)(CR * 2) * (unsigned)p.N;
-            const w2_i32x4 rs = w2_rsrc_uniform(reinterpret_cast<const unsigned char*>(p.dy) + (on ? off : 0u), on ? p.dy_bytes - off : 0u);
-            w2_dma4(rs, lds_pf, voff_pf);
+            const i32x4 rs = rt_make_rsrc_uniform(reinterpret_cast<const unsigned char*>(p.dy) + (on ? off : 0u), on ? p.dy_bytes - off : 0u);
+            rt_dma4(rs, lds_pf, voff_pf);
         } else {
             const long long off = (long long)pc * (CR * 2) * p.SC + pf_shift;
             const bool in = on && off >= 0 && off < (long long)p.x_bytes;
-            const w2_i32x4 rs = w2_rsrc_uniform(reinterpret_cast<const unsigned char*>(p.x) + (in ? off : 0), in ? p.x_bytes - (unsigned)off : 0u);
-            w2_dma4(rs, lds_pf, voff_pf);
+            const i32x4 rs = rt_make_rsrc_uniform(reinterpret_cast<const unsigned char*>(p.x) + (in ? off : 0), in ? p.x_bytes - (unsigned)off : 0u);
+            rt_dma4(rs, lds_pf, voff_pf);
         }
         if (lc + 1 < chunk_end) ++lc;
     };
@@ -311,7 +283,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
         const unsigned char* bA = smem + stage * BUF_BYTES;
         const unsigned char* bB = bA + A_BYTES;
 #pragma unroll
-        for (int a = 0; a < TN; ++a) af[a] = w2_frag2(bA, addr_a[a][0] + kk * 16 * RBA, addr_a[a][1] + kk * 16 * RBA);
+        for (int a = 0; a < TN; ++a) af[a] = rt_tr_frag(bA + addr_a[a][0] + kk * 16 * RBA, bA + addr_a[a][1] + kk * 16 * RBA);
         if (FUSED) {
 #pragma unroll
             for (int q = 0; q < TAPS; ++q) {
@@ -320,14 +292,14 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
 #pragma unroll
                 for (int b = 0; b < TC; ++b) {
                     union { bf16x8 v; uint4 u; } f;
-                    f.v = w2_frag2(bB, addr_b3[q][b][0] + kk * 16 * RBB, addr_b3[q][b][1] + kk * 16 * RBB);
+                    f.v = rt_tr_frag(bB + addr_b3[q][b][0] + kk * 16 * RBB, bB + addr_b3[q][b][1] + kk * 16 * RBB);
                     f.u.x &= mk.x; f.u.y &= mk.y; f.u.z &= mk.z; f.u.w &= mk.w;
                     bfr[q][b] = f.v;
                 }
             }
         } else {
 #pragma unroll
-            for (int b = 0; b < TC; ++b) bfr[0][b] = w2_frag2(bB, addr_b[b][0] + kk * 16 * RBB, addr_b[b][1] + kk * 16 * RBB);
+            for (int b = 0; b < TC; ++b) bfr[0][b] = rt_tr_frag(bB + addr_b[b][0] + kk * 16 * RBB, bB + addr_b[b][1] + kk * 16 * RBB);
         }
     };
     auto mma = [&](const bf16x8 (&af)[TN], const bf16x8 (&bfr)[TAPS][TC]) __attribute__((always_inline)) {
@@ -360,7 +332,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
 #pragma unroll
     for (int s0 = 0; s0 < NS; ++s0) issue(s0);
     bf16x8 fa0[TN], fb0[TAPS][TC], fa1[TN], fb1[TAPS][TC];
-    if (dma_wave) w2_wait_vmcnt<(NS - 1) * LPT>();
+    if (dma_wave) rt_wait_vmcnt<(NS - 1) * LPT>();
     __syncthreads();
     if (FUSED) row_masks();
     load_frags(0, 0, fa0, fb0);
@@ -372,7 +344,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
             if (do_bias) bias_rows(cbuf);
             mma(fa0, fb0);
         }
-        if (dma_wave && !(abl & 1)) w2_wait_vmcnt<(NS - 2) * LPT>();      // this thread's pieces of chunk c+1 have landed
+        if (dma_wave && !(abl & 1)) rt_wait_vmcnt<(NS - 2) * LPT>();      // this thread's pieces of chunk c+1 have landed
         __syncthreads();
         if (!(abl & 1)) issue(cbuf);                           // chunk c + NS
         if (FUSED) { next_rows(); row_masks(); }               // masks of chunk c + 1
@@ -382,7 +354,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
         }
         cbuf = nbuf;
     }
-    w2_wait_vmcnt<0>();
+    rt_wait_vmcnt<0>();
 
     if (do_bias) {
         const int n = n0 + t % BN;

@@ -130,24 +130,34 @@ _CHUNK_SCRIPT = r"""
 import sys, torch
 sys.path.insert(0, sys.argv[1])
 from reftr_amd import hip
-B, H, Sq, Sk, dh = 2, 8, 200, 600, 32
-E = H * dh
-g = torch.Generator().manual_seed(3)
-q = torch.randn(B * Sq, E, generator=g).bfloat16().cuda(); k = torch.randn(B * Sk, E, generator=g).bfloat16().cuda()
-v = torch.randn(B * Sk, E, generator=g).bfloat16().cuda(); do = torch.randn(B * Sq, E, generator=g).bfloat16().cuda()
-kpm = torch.zeros(B, Sk, dtype=torch.uint8); kpm[1, 500:] = 1; kpm[0, ::5] = 1
 hip.set_seed_dev(None)
-o, lse = hip.attn_fwd(q, k, v, kpm.cuda(), B=B, H=H, Sq=Sq, Sk=Sk, dh=dh, scale=dh ** -0.5, drop_p=0.1, drop_seed=77)
-dq, dk, dv = hip.attn_bwd(q, k, v, o, do, lse, kpm.cuda(), B=B, H=H, Sq=Sq, Sk=Sk, dh=dh, scale=dh ** -0.5, drop_p=0.1, drop_seed=77)
-torch.cuda.synchronize()
-torch.save({"o": o.cpu(), "lse": lse.cpu(), "dq": dq.cpu(), "dk": dk.cpu(), "dv": dv.cpu()}, sys.argv[2])
+out = {}
+for prefix, (B, H, Sq, Sk, dh), seed in (("", (2, 8, 200, 600, 32), 3), ("b_", (1, 2, 70, 470, 64), 4)):
+    E = H * dh
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randn(B * Sq, E, generator=g).bfloat16().cuda(); k = torch.randn(B * Sk, E, generator=g).bfloat16().cuda()
+    v = torch.randn(B * Sk, E, generator=g).bfloat16().cuda(); do = torch.randn(B * Sq, E, generator=g).bfloat16().cuda()
+    kpm = torch.zeros(B, Sk, dtype=torch.uint8)
+    if prefix == "":
+        kpm[1, 500:] = 1; kpm[0, ::5] = 1
+    else:                                   # a masked tail and a few scattered keys; no fully masked row (NaN in lse)
+        kpm[0, 440:] = 1; kpm[0, [3, 64, 65, 223, 300]] = 1
+    o, lse = hip.attn_fwd(q, k, v, kpm.cuda(), B=B, H=H, Sq=Sq, Sk=Sk, dh=dh, scale=dh ** -0.5, drop_p=0.1, drop_seed=77)
+    dq, dk, dv = hip.attn_bwd(q, k, v, o, do, lse, kpm.cuda(), B=B, H=H, Sq=Sq, Sk=Sk, dh=dh, scale=dh ** -0.5, drop_p=0.1, drop_seed=77)
+    torch.cuda.synchronize()
+    out.update({prefix + "o": o.cpu(), prefix + "lse": lse.cpu(), prefix + "dq": dq.cpu(), prefix + "dk": dk.cpu(), prefix + "dv": dv.cpu()})
+torch.save(out, sys.argv[2])
 """
 
 
 def test_attention_long_axis_kernels_are_bit_identical_to_the_whole_axis_kernels(hip, tmp_path):
     """REFTR_ATTN_CHUNK forces the chunked kernels (inner axis staged 64 rows at a time) on a shape the whole-axis kernels handle
     (Sk = 600: the two-pass forward, the fused backward): same lane <-> element assignment, same key order per lane, dropout and
-    key-padding mask included -> identical bits.  One process per setting (the library reads the variable once)."""
+    key-padding mask included -> identical bits.  One process per setting (the library reads the variable once).
+    Each process also runs B, H, Sq, Sk, dh = 1, 2, 70, 470, 64 (keys "b_*"): the dh = 64 instantiations, whole waves past the outer
+    axis (70 of 128 rows: the whole-axis kernels return early there, the chunked ones do not) and a padded chunk tail on both axes
+    (Skp = 480 = 7 x 64 + 32 = 2 x 224 + 32, Sqp = 96 = 64 + 32); 30 key tiles keep the forward on the two-pass kernel, 157 440 B of
+    LDS keep chunk 0 on the whole-axis fused backward."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
@@ -157,9 +167,11 @@ def test_attention_long_axis_kernels_are_bit_identical_to_the_whole_axis_kernels
         subprocess.run([sys.executable, "-c", _CHUNK_SCRIPT, root, str(f)], check=True, env=env, timeout=600)
         outs.append(torch.load(f))
     for other in outs[1:]:
-        for key in ("o", "lse", "dq", "dk", "dv"):
-            a, b = outs[0][key], other[key]
-            assert torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a, b.view(torch.int16) if b.dtype == torch.bfloat16 else b), key
+        for prefix in ("", "b_"):
+            for key in ("o", "lse", "dq", "dk", "dv"):
+                a, b = outs[0][prefix + key], other[prefix + key]
+                assert not torch.isnan(a.float()).any(), prefix + key
+                assert torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a, b.view(torch.int16) if b.dtype == torch.bfloat16 else b), prefix + key
 
 
 def test_attention_dropout_mask(hip):
