@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void ksplit_gemm_kernel(const bf16_t* __res
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the over-issued tail: nothing of ours stays in flight past here
 
-    // the four K-partials of the tile meet in LDS; then every thread owns 16-B pieces of ONE output row (epilogue8)
+    // the four K-partials of the tile meet in LDS; then every thread owns 16-B pieces of ONE output row (epilogue<8>)
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void ksplit_gemm_kernel(const bf16_t* __res
             lo += *reinterpret_cast<const f32x4*>(red + ((size_t)(w * 64 + rl)) * EP_LD + cl);
             hi += *reinterpret_cast<const f32x4*>(red + ((size_t)(w * 64 + rl)) * EP_LD + cl + 4);
         }
-        epilogue8(p, m, n, f32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+        epilogue<8>(p, m, n, f32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
     }
 }
 

@@ -21,15 +21,16 @@ namespace {
 template <int BM, int BN, int MODE>
 __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const bf16_t* __restrict__ src,
                                                         const bf16_t* __restrict__ wgt, const GemmArgs p) {
-    constexpr int TM = BM / 32, TN = BN / 32;      // 16x16 MFMA tiles per wave along m / n
+    typedef WaveTile<BM, BN, 2> WT;
+    constexpr int TM = WT::TM, TN = WT::TN;        // 16x16 MFMA tiles per wave along m / n
     constexpr int AJ = BN / 32, BJ = BM / 32;      // 16-B staging chunks per thread
-    constexpr int A_BYTES = BN * 128, B_BYTES = BM * 128, BUF_BYTES = A_BYTES + B_BYTES;
+    constexpr int A_BYTES = WT::A_BYTES, BUF_BYTES = WT::BUF_BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
     const int wn = wave & 1, wm = wave >> 1;
-    const int li = lane & 15, lg = lane >> 4;
+    const WT wt{wn, wm, lane & 15, lane >> 4};
 
     const int n_tiles = (p.N + BN - 1) / BN;
     const int tile_n = blockIdx.x % n_tiles, tile_m = blockIdx.x / n_tiles;
@@ -137,30 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const bf16_t* __restr
             *reinterpret_cast<uint4*>(bB + row * 128 + ((chunk ^ (row & 7)) << 4)) = rb[j];
         }
     };
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-        const unsigned char* bA = smem + buf * BUF_BYTES;
-        const unsigned char* bB = bA + A_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 af[TN], bfr[TM];
-            const int slot = ((kk * 4 + lg) ^ (li & 7)) << 4;
-#pragma unroll
-            for (int a = 0; a < TN; ++a) {
-                const int row = wn * (BN / 2) + a * 16 + li;
-                af[a] = *reinterpret_cast<const bf16x8*>(bA + row * 128 + slot);
-            }
-#pragma unroll
-            for (int b = 0; b < TM; ++b) {
-                const int row = wm * (BM / 2) + b * 16 + li;
-                bfr[b] = *reinterpret_cast<const bf16x8*>(bB + row * 128 + slot);
-            }
-#pragma unroll
-            for (int a = 0; a < TN; ++a)
-#pragma unroll
-                for (int b = 0; b < TM; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
-        }
-    };
+    auto compute = [&](int buf) __attribute__((always_inline)) { wt.compute(smem + buf * BUF_BYTES, acc); };
 
     load_tiles(ra0, rb0);                 // tile 0
     load_tiles(ra1, rb1);                 // tile 1 (or tile 0 again when nk == 1)
@@ -183,13 +161,13 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const bf16_t* __restr
     // ---- epilogue (shared with the skinny kernel) ----
 #pragma unroll
     for (int a = 0; a < TN; ++a) {
-        const int n = n0 + wn * (BN / 2) + a * 16 + lg * 4;
+        const int n = n0 + wn * (BN / 2) + a * 16 + wt.lg * 4;
         if (n >= p.N) continue;
 #pragma unroll
         for (int b = 0; b < TM; ++b) {
-            const int m = m0 + wm * (BM / 2) + b * 16 + li;
+            const int m = m0 + wm * (BM / 2) + b * 16 + wt.li;
             if (m >= p.M) continue;
-            epilogue4(p, m, n, acc[a][b]);
+            epilogue<4>(p, m, n, acc[a][b]);
         }
     }
 }
@@ -200,6 +178,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const bf16_t* __restr
 // tables): the q/k and v projections of an encoder layer, the twelve cross-attention K / V projections of the decoder, pairs
 // of backward-data products.  On the latency-bound transformer chains every launch costs ~4.5 us whatever it computes.
 struct GemmGroup { GemmArgs j[12]; int first[13]; int n; };
+struct GroupTile { static constexpr int BM = 64, BN = 64, NS = 2, MINB = 4; };      // the tile of hint 31: one place for both launches
 template <int BM, int BN, int NS, int MINB>
 __global__ __launch_bounds__(256, MINB) void conv_gemm_dma_grouped_kernel(const GemmGroup g) {
     int lo = 0;
@@ -229,8 +208,8 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(const bf16_t* __restri
     const int nrow = n0 + li;
     const int n = n0 + lg * 4;
     const bool out_ok = wave == 0 && n < p.N && li < p.M;
-    Epi4Pre pre;
-    if (out_ok) pre = epi4_prefetch(p, li, n);
+    EpiPre<4> pre;
+    if (out_ok) pre = epi_prefetch<4>(p, (size_t)li * p.N + n, n);
     constexpr int OOB = 0x7fffffff;
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(wgt), 0, p.wgt_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(src), 0, p.src_bytes, 0x00020000);
@@ -257,9 +236,10 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(const bf16_t* __restri
     __syncthreads();
     if (wave != 0) return;
     acc = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-    if (out_ok) epilogue4<true>(p, li, n, acc, &pre);
+    if (out_ok) epilogue<4, true>(p, li, n, acc, &pre);
 }
 
+#ifdef RT_LAB
 // round-2 form, kept as the A/B baseline (REFTR_SKINNY_V=1): 4 k-steps in flight, epilogue operands loaded after the reduction
 __global__ __launch_bounds__(256) void skinny_gemm_kernel_v1(const bf16_t* __restrict__ src, const bf16_t* __restrict__ wgt,
                                                              const GemmArgs p) {
@@ -289,17 +269,15 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel_v1(const bf16_t* __res
     if (wave != 0) return;
     acc = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
     const int n = n0 + lg * 4;
-    if (n < p.N && li < p.M) epilogue4(p, li, n, acc);
+    if (n < p.N && li < p.M) epilogue<4>(p, li, n, acc);
 }
 
-#ifdef RT_LAB
 template <int BM, int BN>
 int launch_gemm(const GemmArgs& a, hipStream_t s) {
     const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
     const size_t smem = 2 * (size_t)(BM + BN) * 128;
     const dim3 grid((unsigned)(mt * nt)), block(256);
-    const bool dense = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW);
-    if (dense)
+    if (gemm_dense(a))
         hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 0>), grid, block, smem, s, a.src, a.wgt, a);
     else if (!a.transposed)
         hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 1>), grid, block, smem, s, a.src, a.wgt, a);
@@ -355,104 +333,59 @@ static int fill_gemm_args(const rt_conv_gemm_desc* d, GemmArgs& a) {
     return RT_OK;
 }
 
-extern "C" int rt_conv_gemm(const rt_conv_gemm_desc* d, rt_stream_t stream) {
-    GemmArgs a;
-    const int frc = fill_gemm_args(d, a);
-    if (frc != RT_OK) return frc;
-    hipStream_t s = (hipStream_t)stream;
+// the M <= 16 dense products (the decoder / query-encoder / box-head Linears over B * n_q tokens): skinny_gemm_kernel
+static bool gemm_skinny(const GemmArgs& a) { return gemm_dense(a) && a.M <= 16; }
+enum { GEMM_ROUTE_SKINNY = -1 };
 
-    const bool dense = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW);
-    if (d->tile_hint == 0 && dense && a.M <= 16) {
-        const dim3 grid((unsigned)((a.N + 15) / 16));
-        const int per = ((a.K >> 5) + 3) >> 2;          // k-steps per wave: the whole slice in flight when it fits 8 steps
-        static const int skinny_v = RT_TUNE("REFTR_SKINNY_V", 2);
-        if (skinny_v == 1) hipLaunchKernelGGL(skinny_gemm_kernel_v1, grid, dim3(256), 0, s, a.src, a.wgt, a);
-        else if (per <= 2) hipLaunchKernelGGL(skinny_gemm_kernel<2>, grid, dim3(256), 0, s, a.src, a.wgt, a);
-        else if (per <= 4) hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, s, a.src, a.wgt, a);
-        else hipLaunchKernelGGL(skinny_gemm_kernel<8>, grid, dim3(256), 0, s, a.src, a.wgt, a);
-        RT_CHECK_LAUNCH();
-        return RT_OK;
-    }
-    int hint = d->tile_hint;
-    if (a.dil > 1 && hint >= 1 && hint <= 3) return RT_ERR_UNSUPPORTED;      // the register-staged tiles have no dilation
-    if (hint == 0) {
-        // Tile choice from the in-step sweeps (benchmarks/tile_sweep.py, profiles/r01e_tile_sweep.txt): small K streams
-        // best through many 64x64 workgroups; 128x128 needs >= 1.5 waves of tiles over the 256 CUs to pay off.
-        const long long t128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-        const long long t12864 = (long long)((a.M + 127) / 128) * ((a.N + 63) / 64);
-        static const int smallk = RT_TUNE("REFTR_SMALLK", 256);
-        static const int dma = RT_TUNE("REFTR_DMA", 1);
-        if (a.K <= smallk) hint = 3;
-        else if (a.N > 64 && t128 >= 384) hint = 1;
-        else if (t12864 >= 256) hint = 2;
-        else hint = 3;
-        static const int tilev = RT_TUNE("REFTR_TILEV", 3);
-        if (dma && tilev >= 3) {
-            // round 3 (profiles/r03_tile_sweep_warm.txt / _cold.txt, r03_instep_ab.txt).  Two lessons: (1) back-to-back launches of
-            // one shape on warm caches are a misleading yardstick -- the software-pipelined K loop (hints 2xx: fragments of tile
-            // kt+1 read under the MFMAs of tile kt, one barrier per K tile) wins 8-20 % there and LOSES in the step, where the
-            // weights come from HBM and the kernels are bound by bytes in flight per CU; the sweep now has a cold mode (FLUSH=1)
-            // and only what wins in both is adopted: the pipelined 3-stage forms (64 x 64 on the layer4-sized 3x3 convolutions,
-            // 128 x 128 at ONE workgroup per CU where the tiles do not fill two per CU anyway: layer3's 3x3).  (2) The M = B * L
-            // Linears of the language branch (<= 96 tiles of 64 x 64: 60 CUs pulling at ~50 GB/s each) run on 32 x 32 tiles
-            // (4x the workgroups), the other few-tile products on the 3-stage 64 x 64 tile also for K < 1024.
-            static const int smallt = RT_TUNE("REFTR_SMALLT", 1);
-            static const int pipe = RT_TUNE("REFTR_PIPE", 3);         // bit 0: 128x128 / 3 stages, bit 1: 64x64 / 3 stages
-            const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-            const long long t256 = (long long)((a.M + 255) / 256) * ((a.N + 127) / 128);
-            // round 4 (profiles/r04o_deep_stage_cold.txt): at <= 1 workgroup per CU the 32 x 32 form is bound by the K tiles it keeps in
-            // flight -- 6 stages instead of 3 take the cold K >= 768 products from 17.3 / 14.6 / 7.8 us to 11.1 / 9.9 / 5.8 (8 stages: no better)
-            static const int deep = RT_TUNE("REFTR_DEEP", 1);
-            static const int k1024 = RT_TUNE("REFTR_K1024", 1);
-            if (dense && smallt && a.M <= 1024 && t64 < 256 && (a.N & 7) == 0) hint = t64 <= 96 ? ((deep && a.K >= 512) ? 285 : 281) : 33;
-            else if (a.K < 1024) hint = (a.N >= 128 && t128 >= 384 && t128 <= 512) ? 51 : 31;
-            else if (dense && a.K >= 2048 && a.N >= 128 && t256 >= 512) hint = 262;     // big products only; none in the step
-            else if (a.N > 64 && (t128 >= 384 || (a.K >= 2048 && t128 >= 192))) hint = (!dense && (pipe & 1) && a.K >= 2048 && t128 <= 256) ? 252 : 51;
-            else if (k1024 && dense && a.N > 64 && a.K >= 1024 && t128 >= 192) hint = 51;      // layer3's 1024 -> 256 (200 tiles): 18.6-19.1 us cold against 21.7-22.9 on hint 21
-            else if (t12864 >= 256) hint = 21;
-            else hint = (!dense && (pipe & 2)) ? 233 : 33;
-            // round 6 (profiles/r06c_sweep_*.txt): the K-parity ping-pong 128 x 128 form where ONE round of <= 256 tiles walks a long
-            // reduction -- layer3's 3 x 3 convolutions (K = 2304: 252 before) and its 1024 -> 256 products (K = 1024, 200 tiles: 21 before)
-            static const int pp = RT_TUNE("REFTR_PP", 0);      // off: loses 0.07-0.2 ms inside the step (profiles/r06_pingpong_gemm.txt)
-            if ((a.N & 7) == 0 && a.epi_lds && a.N >= 128) {
-                if ((pp & 1) && hint == 252) hint = (pp & 4) ? 351 : 352;
-                else if ((pp & 2) && dense && a.K >= 1024 && t128 >= 128 && t128 <= 256) hint = (pp & 4) ? 351 : 352;
-            }
+// The variant a product runs on: tile_hint itself when the caller names one (lab sweeps, tests), else the heuristic's choice.
+static int gemm_route(const GemmArgs& a, int tile_hint) {
+    if (tile_hint != 0) return tile_hint;
+    if (gemm_skinny(a)) return GEMM_ROUTE_SKINNY;
+    const bool dense = gemm_dense(a);
+    int hint;
+    // Tile choice from the in-step sweeps (benchmarks/tile_sweep.py, profiles/r01e_tile_sweep.txt): small K streams
+    // best through many 64x64 workgroups; 128x128 needs >= 1.5 waves of tiles over the 256 CUs to pay off.
+    const long long t128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
+    const long long t12864 = (long long)((a.M + 127) / 128) * ((a.N + 63) / 64);
+    // round 3 (profiles/r03_tile_sweep_warm.txt / _cold.txt, r03_instep_ab.txt).  Two lessons: (1) back-to-back launches of
+    // one shape on warm caches are a misleading yardstick -- the software-pipelined K loop (hints 2xx: fragments of tile
+    // kt+1 read under the MFMAs of tile kt, one barrier per K tile) wins 8-20 % there and LOSES in the step, where the
+    // weights come from HBM and the kernels are bound by bytes in flight per CU; the sweep now has a cold mode (FLUSH=1)
+    // and only what wins in both is adopted: the pipelined 3-stage forms (64 x 64 on the layer4-sized 3x3 convolutions,
+    // 128 x 128 at ONE workgroup per CU where the tiles do not fill two per CU anyway: layer3's 3x3).  (2) The M = B * L
+    // Linears of the language branch (<= 96 tiles of 64 x 64: 60 CUs pulling at ~50 GB/s each) run on 32 x 32 tiles
+    // (4x the workgroups), the other few-tile products on the 3-stage 64 x 64 tile also for K < 1024.
+    static const int smallt = RT_TUNE("REFTR_SMALLT", 1);
+    static const int pipe = RT_TUNE("REFTR_PIPE", 3);         // bit 0: 128x128 / 3 stages, bit 1: 64x64 / 3 stages
+    const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
+    const long long t256 = (long long)((a.M + 255) / 256) * ((a.N + 127) / 128);
+    // round 4 (profiles/r04o_deep_stage_cold.txt): at <= 1 workgroup per CU the 32 x 32 form is bound by the K tiles it keeps in
+    // flight -- 6 stages instead of 3 take the cold K >= 768 products from 17.3 / 14.6 / 7.8 us to 11.1 / 9.9 / 5.8 (8 stages: no better)
+    static const int deep = RT_TUNE("REFTR_DEEP", 1);
+    static const int k1024 = RT_TUNE("REFTR_K1024", 1);
+    if (dense && smallt && a.M <= 1024 && t64 < 256 && (a.N & 7) == 0) hint = t64 <= 96 ? ((deep && a.K >= 512) ? 285 : 281) : 33;
+    else if (a.K < 1024) hint = (a.N >= 128 && t128 >= 384 && t128 <= 512) ? 51 : 31;
+    else if (dense && a.K >= 2048 && a.N >= 128 && t256 >= 512) hint = 262;     // big products only; none in the step
+    else if (a.N > 64 && (t128 >= 384 || (a.K >= 2048 && t128 >= 192))) hint = (!dense && (pipe & 1) && a.K >= 2048 && t128 <= 256) ? 252 : 51;
+    else if (k1024 && dense && a.N > 64 && a.K >= 1024 && t128 >= 192) hint = 51;      // layer3's 1024 -> 256 (200 tiles): 18.6-19.1 us cold against 21.7-22.9 on hint 21
+    else if (t12864 >= 256) hint = 21;
+    else hint = (!dense && (pipe & 2)) ? 233 : 33;
 #ifdef RT_LAB
-            // round 6: the short-K / wide-N dense products (a bottleneck's conv3 and the backward-data of its conv1, the encoder's
-            // linear1 and the backward-data of its linear2) are epilogue-bound; the activation-stationary form (rt_gemm_astat.hip) was
-            // built for them and is SLOWER (28.2 vs 25.0 us cold on layer3's 256 -> 1024, +0.17 ms in the step): lab switch, off
-            static const int astat = RT_TUNE("REFTR_ASTAT", 0);
-            if (astat && rt_gemm_astat_ok(a) && a.M >= 1024 && a.N >= 2 * a.K && a.N >= 256) hint = 501;
-#endif
-        } else if (dma && tilev >= 2) {
-            // round 2 (profiles/r02_tile_sweep_8wave.txt): the 128x128 tile runs on 8-wave workgroups (2 x 4 waves, 16 waves per CU
-            // at two workgroups: beats the 4-wave form on every shape); it takes over the long reductions with >= 1.5 rounds of
-            // tiles (or >= 0.75 rounds from K = 2048 up) and the short ones whose tiles fill exactly one round of 2 per CU
-            const long long t256 = (long long)((a.M + 255) / 256) * ((a.N + 127) / 128);
-            if (a.K < 1024) hint = (a.N >= 128 && t128 >= 384 && t128 <= 512) ? 51 : 31;
-            else if (a.K >= 2048 && a.N >= 128 && t256 >= 512) hint = 62;     // big products only (4096^3: 898 TF/s); none in the step
-            else if (a.N > 64 && (t128 >= 384 || (a.K >= 2048 && t128 >= 192))) hint = 51;
-            else if (t12864 >= 256) hint = 21;
-            else hint = 33;
-        } else if (dma && tilev) {
-            // with the issue-before-wait schedule (profiles/r01g_tile_sweep_early.txt): short K streams best through
-            // 64x64 workgroups; 128x128 pays off from K >= 1024 with >= 1.5 waves of tiles; 128x64 in between
-            if (a.K < 1024) hint = 31;
-            else if (a.N > 64 && t128 >= 384) hint = 11;
-            else if (t12864 >= 256) hint = 21;
-            else hint = 33;
-        } else if (dma) {   // previous choice (A/B)
-            if (hint == 1) hint = 11;
-            else if (hint == 2) hint = a.K >= 1024 ? 22 : 21;
-            else hint = a.K >= 1024 ? 33 : 31;
-        }
+    // round 6 (profiles/r06c_sweep_*.txt): the K-parity ping-pong 128 x 128 form where ONE round of <= 256 tiles walks a long
+    // reduction -- layer3's 3 x 3 convolutions (K = 2304: 252 before) and its 1024 -> 256 products (K = 1024, 200 tiles: 21 before)
+    static const int pp = RT_TUNE("REFTR_PP", 0);      // off: loses 0.07-0.2 ms inside the step (profiles/r06_pingpong_gemm.txt)
+    if ((a.N & 7) == 0 && a.epi_lds && a.N >= 128) {
+        if ((pp & 1) && hint == 252) hint = (pp & 4) ? 351 : 352;
+        else if ((pp & 2) && dense && a.K >= 1024 && t128 >= 128 && t128 <= 256) hint = (pp & 4) ? 351 : 352;
     }
-    if (a.dil > 1 && hint >= 1 && hint <= 3) return RT_ERR_UNSUPPORTED;      // (REFTR_DMA=0)
-#ifdef RT_LAB
+    // round 6: the short-K / wide-N dense products (a bottleneck's conv3 and the backward-data of its conv1, the encoder's
+    // linear1 and the backward-data of its linear2) are epilogue-bound; the activation-stationary form (rt_gemm_astat.hip) was
+    // built for them and is SLOWER (28.2 vs 25.0 us cold on layer3's 256 -> 1024, +0.17 ms in the step): lab switch, off
+    static const int astat = RT_TUNE("REFTR_ASTAT", 0);
+    if (astat && rt_gemm_astat_ok(a) && a.M >= 1024 && a.N >= 2 * a.K && a.N >= 256) hint = 501;
     // in-step autotune (benchmarks/instep_autotune.py): REFTR_HINT_OVERRIDE = "transposed,KH,stride,M,K,N=hint;..." replaces the heuristic's
     // choice for exactly those launches; read on every call so that the script can re-capture the step with another table
-    if (d->tile_hint == 0) {
+    {
         const char* ov = getenv("REFTR_HINT_OVERRIDE");
         while (ov && *ov) {
             int t_, kh_, s_, m_, k_, n_, h_, used = 0;
@@ -465,13 +398,38 @@ extern "C" int rt_conv_gemm(const rt_conv_gemm_desc* d, rt_stream_t stream) {
         }
     }
 #endif
+    return hint;
+}
+
+static int launch_skinny(const GemmArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.N + 15) / 16));
+    const int per = ((a.K >> 5) + 3) >> 2;          // k-steps per wave: the whole slice in flight when it fits 8 steps
+#ifdef RT_LAB
+    static const int skinny_v = RT_TUNE("REFTR_SKINNY_V", 2);
+    if (skinny_v == 1) { hipLaunchKernelGGL(skinny_gemm_kernel_v1, grid, dim3(256), 0, s, a.src, a.wgt, a); RT_CHECK_LAUNCH(); return RT_OK; }
+#endif
+    if (per <= 2) hipLaunchKernelGGL(skinny_gemm_kernel<2>, grid, dim3(256), 0, s, a.src, a.wgt, a);
+    else if (per <= 4) hipLaunchKernelGGL(skinny_gemm_kernel<4>, grid, dim3(256), 0, s, a.src, a.wgt, a);
+    else hipLaunchKernelGGL(skinny_gemm_kernel<8>, grid, dim3(256), 0, s, a.src, a.wgt, a);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
+
+extern "C" int rt_conv_gemm(const rt_conv_gemm_desc* d, rt_stream_t stream) {
+    GemmArgs a;
+    const int frc = fill_gemm_args(d, a);
+    if (frc != RT_OK) return frc;
+    hipStream_t s = (hipStream_t)stream;
+    const int hint = gemm_route(a, d->tile_hint);
+    if (a.dil > 1 && hint >= 1 && hint <= 3) return RT_ERR_UNSUPPORTED;      // the register-staged tiles have no dilation
     // The product library instantiates only the variants its (constant) heuristics can choose; every other tile / stage / schedule
     // variant that was built and measured (LAB_NOTES.md, profiles/*tile_sweep*) lives in the LAB library (-DRT_LAB), where the
     // sweeps and tests/test_gemm_gpu.py reach it through tile_hint.  (Round 6: libreftr_hip.so 16.3 MB -> see DESIGN.md section 5.)
     switch (hint) {
+        case GEMM_ROUTE_SKINNY: return launch_skinny(a, s);
         // LDS-DMA variants (tile, stages, min workgroups / CU[, waves])
         case 21: return launch_gemm_dma<128, 64, 2, 2>(a, s);
-        case 31: return launch_gemm_dma<64, 64, 2, 4>(a, s);
+        case 31: return launch_gemm_dma<GroupTile::BM, GroupTile::BN, GroupTile::NS, GroupTile::MINB>(a, s);      // <64, 64, 2, 4>
         case 33: return launch_gemm_dma<64, 64, 3, 3>(a, s);
         case 51: return launch_gemm_dma<128, 128, 2, 2, 8>(a, s);
         case 233: case 252: case 262: case 281: case 285: return rt_launch_gemm_pipe(a, hint, s);
@@ -504,7 +462,7 @@ extern "C" int rt_conv_gemm_grouped(const rt_conv_gemm_desc* descs, int n, rt_st
     if (!descs || n <= 0) return RT_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     static const int grp_env = RT_TUNE("REFTR_GEMM_GROUP", 1);
-    // groupable: dense products the single-launch heuristic would give the 64x64 / 2-stage / 4-per-CU variant (K < 1024, M > 16)
+    // groupable: dense products with M > 16 and K < 1024 whose tile is left to the library; they run on GroupTile
     bool ok = grp_env && n >= 2 && n <= 12;
     GemmGroup g;
     int blocks = 0;
@@ -513,10 +471,9 @@ extern "C" int rt_conv_gemm_grouped(const rt_conv_gemm_desc* descs, int n, rt_st
         GemmArgs a;
         const int rc = fill_gemm_args(&d, a);
         if (rc != RT_OK) return rc;
-        const bool dense = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW);
-        if (!dense || a.M <= 16 || a.K >= 1024 || d.tile_hint != 0) { ok = false; break; }
+        if (d.tile_hint != 0 || !gemm_dense(a) || gemm_skinny(a) || a.K >= 1024) { ok = false; break; }
         g.j[i] = a; g.first[i] = blocks;
-        blocks += ((a.M + 63) / 64) * ((a.N + 63) / 64);
+        blocks += ((a.M + GroupTile::BM - 1) / GroupTile::BM) * ((a.N + GroupTile::BN - 1) / GroupTile::BN);
     }
     if (!ok) {                                   // anything else: the same products as single launches, in order
         for (int i = 0; i < n; ++i) { const int rc = rt_conv_gemm(descs + i, stream); if (rc != RT_OK) return rc; }
@@ -524,8 +481,8 @@ extern "C" int rt_conv_gemm_grouped(const rt_conv_gemm_desc* descs, int n, rt_st
     }
     g.first[n] = blocks; g.n = n;
     for (int i = n + 1; i < 13; ++i) g.first[i] = blocks;
-    constexpr size_t smem = (size_t)2 * (64 + 64) * 128;
-    hipLaunchKernelGGL((conv_gemm_dma_grouped_kernel<64, 64, 2, 4>), dim3((unsigned)blocks), dim3(256), smem, s, g);
+    hipLaunchKernelGGL((conv_gemm_dma_grouped_kernel<GroupTile::BM, GroupTile::BN, GroupTile::NS, GroupTile::MINB>), dim3((unsigned)blocks), dim3(256),
+                       gemm_dma_lds_bytes(GroupTile::BM, GroupTile::BN, GroupTile::NS), s, g);
     RT_CHECK_LAUNCH();
     return RT_OK;
 }

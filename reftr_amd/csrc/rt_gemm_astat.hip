@@ -87,35 +87,30 @@ __global__ __launch_bounds__(256, 2) void gemm_astat_kernel(const bf16_t* __rest
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int slot = ((kk * 4 + lg) ^ (li & 7)) << 4;
+            for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-                for (int b = 0; b < 2; ++b)
-                    xf[kb][kk][b] = *reinterpret_cast<const bf16x8*>(xs + kb * 8192 + (wm * 32 + b * 16 + li) * 128 + slot);
-            }
+                for (int b = 0; b < 2; ++b) xf[kb][kk][b] = *rt_frag(xs + kb * 8192, wm * 32 + b * 16 + li, rt_frag_slot(kk, li, lg));
     }
     __syncthreads();                                           // stage 1 may be overwritten
 
     // epilogue pieces of this lane: rows wm * 32 + (lane >> 2) + 16 * i, 8 columns at wn * 32 + (lane & 3) * 8
     const int er = lane >> 2, ec = (lane & 3) * 8;
     unsigned char* etile = smem + 2 * STAGE + wave * EPI;
-    const bool want_res = p.res_bf16 != nullptr, want_gate = p.gate != nullptr, want_bias = p.bias != nullptr;
-    struct EpiPre { bf16x8 res[2], gate[2]; f32x4 b0, b1; };
-    auto prefetch_epi = [&](int jt, EpiPre& e) __attribute__((always_inline)) {
+    const bool want_bias = p.bias != nullptr;
+    struct TilePre { EpiPre<8> e[2]; f32x4 b0, b1; };
+    auto prefetch_epi = [&](int jt, TilePre& e) __attribute__((always_inline)) {
         const int n = jt * BN + wn * 32 + ec;
         const bool nok = n < p.N;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = m0 + wm * 32 + er + 16 * i;
-            const size_t o = (m < p.M && nok) ? (size_t)m * p.N + n : 0;
-            e.res[i] = want_res ? *reinterpret_cast<const bf16x8*>(p.res_bf16 + o) : bf16x8{};
-            e.gate[i] = want_gate ? *reinterpret_cast<const bf16x8*>(p.gate + o) : bf16x8{};
+            e.e[i] = epi_prefetch<8>(p, (m < p.M && nok) ? (size_t)m * p.N + n : 0, n);
         }
         const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
         e.b0 = want_bias ? *reinterpret_cast<const f32x4*>(p.bias + (nok ? n : 0)) : z;
         e.b1 = want_bias ? *reinterpret_cast<const f32x4*>(p.bias + (nok ? n : 0) + 4) : z;
     };
-    EpiPre cur, nxt;
+    TilePre cur, nxt;
     prefetch_epi(jt0, cur);
     GemmArgs pe = p;                                           // the epilogue proper: the bias is added here from the prefetched words
     pe.bias = nullptr;
@@ -136,10 +131,9 @@ __global__ __launch_bounds__(256, 2) void gemm_astat_kernel(const bf16_t* __rest
         for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
-                const int slot = ((kk * 4 + lg) ^ (li & 7)) << 4;
                 bf16x8 wf[2];
 #pragma unroll
-                for (int a = 0; a < 2; ++a) wf[a] = *reinterpret_cast<const bf16x8*>(ws + kb * 8192 + (wn * 32 + a * 16 + li) * 128 + slot);
+                for (int a = 0; a < 2; ++a) wf[a] = *rt_frag(ws + kb * 8192, wn * 32 + a * 16 + li, rt_frag_slot(kk, li, lg));
 #pragma unroll
                 for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void gemm_astat_kernel(const bf16_t* __rest
             lo4 += cur.b0; hi4 += cur.b1;
             const int m = m0 + wm * 32 + row, n = jt * BN + wn * 32 + ec;
             if (m < p.M && n < p.N)
-                epilogue8<true>(pe, m, n, f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]}, cur.res[i], cur.gate[i]);
+                epilogue<8, true>(pe, m, n, f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]}, &cur.e[i]);
         }
         if (more) cur = nxt;
     }
@@ -195,8 +189,7 @@ int launch_astat(const GemmArgs& a, hipStream_t s) {
 // dense rows, K = 128 / 256, N a multiple of 8 (16-B row pieces), bf16 residual / gate operands prefetched (the other epilogue operands
 // are read in place)
 bool rt_gemm_astat_ok(const GemmArgs& a) {
-    const bool dense = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW);
-    return dense && (a.K == 128 || a.K == 256) && (a.N & 7) == 0;
+    return gemm_dense(a) && (a.K == 128 || a.K == 256) && (a.N & 7) == 0;
 }
 int rt_launch_gemm_astat(const GemmArgs& a, hipStream_t s) {
     if (!rt_gemm_astat_ok(a)) return RT_ERR_UNSUPPORTED;

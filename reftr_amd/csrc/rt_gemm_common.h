@@ -14,172 +14,123 @@ struct GemmArgs {
     const uint32_t* seed_dev;
 };
 
-// epilogue of one lane's 4 consecutive output features of row m:
-// +bias -> [+res] -> act -> dropout -> [+res] -> *gate -> *gelu'(preact) -> *(1 - dtanh^2) -> store
-// The operands epilogue4 reads, fetched ahead of the reduction (skinny kernel: the M <= 16 launches are pure latency chains --
-// launch -> operand loads -> MFMA -> LDS reduce -> EPILOGUE LOADS -> stores -- and the epilogue's loads depend on nothing the
-// kernel computes, so they are requested first and cost no round trip of their own).
-struct Epi4Pre { f32x4 bias, res; bf16x4 resb, gate, preact, dtanh; };
-static __device__ __forceinline__ Epi4Pre epi4_prefetch(const GemmArgs& p, int m, int n) {
-    Epi4Pre e;
-    const size_t o = (size_t)m * p.N + n;
-    const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-    e.bias = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + n) : z;
-    e.res = p.res_f32 ? *reinterpret_cast<const f32x4*>(p.res_f32 + o) : z;
-    e.resb = p.res_bf16 ? *reinterpret_cast<const bf16x4*>(p.res_bf16 + o) : bf16x4{};
-    e.gate = p.gate ? *reinterpret_cast<const bf16x4*>(p.gate + o) : bf16x4{};
-    e.preact = p.preact ? *reinterpret_cast<const bf16x4*>(p.preact + o) : bf16x4{};
-    e.dtanh = p.dtanh ? *reinterpret_cast<const bf16x4*>(p.dtanh + o) : bf16x4{};
+// dense rows: a 1x1 / stride 1 / pad 0 product whose output pixels are its input pixels (every Linear, most bottleneck convs)
+static inline bool gemm_dense(const GemmArgs& a) {
+    return a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW;
+}
+
+// The fused epilogue on W consecutive output features of row m:
+// +bias -> store preact -> [+res] -> act -> dropout -> [+res] -> *gate -> *gelu'(preact) -> *(1 - dtanh^2) -> stores
+// W = 4: one lane's piece of the MFMA C/D layout.  W = 8: the LDS-staged, row-coalesced path, where every global access is a full
+// 16-B (bf16) piece of one output row and an fp32 operand is two 16-B accesses.
+template <int W> using epi_f32 = __attribute__((ext_vector_type(W))) float;
+template <int W> using epi_bf16 = __attribute__((ext_vector_type(W))) __bf16;
+typedef epi_f32<8> f32x8;
+// The operands the epilogue reads, fetched ahead of the reduction: they depend on nothing the kernel computes.  (Skinny kernel: the
+// M <= 16 launches are pure latency chains -- launch -> operand loads -> MFMA -> LDS reduce -> EPILOGUE LOADS -> stores -- so they are
+// requested first and cost no round trip of their own; tile kernels: their HBM latency runs under the K loop.)
+// The 8-wide form holds PIECES of them per thread for a whole K loop, so it holds the bf16 residual and gate only.
+template <int W> struct EpiPre { epi_bf16<W> resb, gate; };
+template <> struct EpiPre<4> { f32x4 bias, res; epi_bf16<4> resb, gate, preact, dtanh; };
+template <int W> static __device__ __forceinline__ epi_bf16<W> epi_ld(const bf16_t* q) { return *reinterpret_cast<const epi_bf16<W>*>(q); }
+template <int W> static __device__ __forceinline__ epi_f32<W> epi_ld(const float* q) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(q);
+    if constexpr (W == 4) return lo;
+    else {
+        const f32x4 hi = *reinterpret_cast<const f32x4*>(q + 4);
+        return f32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+}
+// o: element offset of the piece in the output (0 for a piece that will not be stored), n: its first feature
+template <int W> static __device__ __forceinline__ EpiPre<W> epi_prefetch(const GemmArgs& p, size_t o, int n) {
+    EpiPre<W> e;
+    if constexpr (W == 4) {
+        e.bias = p.bias ? epi_ld<W>(p.bias + n) : epi_f32<W>{};
+        e.res = p.res_f32 ? epi_ld<W>(p.res_f32 + o) : epi_f32<W>{};
+    }
+    e.resb = p.res_bf16 ? epi_ld<W>(p.res_bf16 + o) : epi_bf16<W>{};
+    e.gate = p.gate ? epi_ld<W>(p.gate + o) : epi_bf16<W>{};
+    if constexpr (W == 4) {
+        e.preact = p.preact ? epi_ld<W>(p.preact + o) : epi_bf16<W>{};
+        e.dtanh = p.dtanh ? epi_ld<W>(p.dtanh + o) : epi_bf16<W>{};
+    }
     return e;
 }
 
-template <bool PRE = false>
-static __device__ __forceinline__ void epilogue4(const GemmArgs& p, int m, int n, f32x4 v, const Epi4Pre* e = nullptr) {
-    if (p.bias) v += PRE ? e->bias : *reinterpret_cast<const f32x4*>(p.bias + n);
-    const size_t o = (size_t)m * p.N + n;
-    if (p.out_preact) {
-        bf16x4 pv;
+// PRE (compile-time): the operands EpiPre<W> can hold come from *e, fetched at the start of the workgroup.
+template <int W, bool PRE = false>
+static __device__ __forceinline__ void epilogue(const GemmArgs& p, int m, int n, epi_f32<W> v, const EpiPre<W>* e = nullptr) {
+    // an operand only EpiPre<4> holds: prefetched there, loaded here otherwise
+    auto pre4_or_ld = [&](auto field, auto* q) __attribute__((always_inline)) {
+        if constexpr (PRE && W == 4) return field(*e);
+        else return epi_ld<W>(q);
+    };
+    auto to_bf16 = [&]() __attribute__((always_inline)) {
+        epi_bf16<W> b;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) pv[r] = (bf16_t)v[r];
-        *reinterpret_cast<bf16x4*>(p.out_preact + o) = pv;
-    }
-    if (p.res_first) {
-        if (p.res_f32) v += PRE ? e->res : *reinterpret_cast<const f32x4*>(p.res_f32 + o);
-        if (p.res_bf16) {
-            const bf16x4 rr = PRE ? e->resb : *reinterpret_cast<const bf16x4*>(p.res_bf16 + o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += (float)rr[r];
-        }
-    }
-    if (p.act == RT_ACT_RELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-    } else if (p.act == RT_ACT_GELU) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = rt_gelu(v[r]);
-    } else if (p.act == RT_ACT_TANH) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
-    }
-    if (p.drop_p > 0.f) {
-        const uint32_t thresh = rt_drop_thresh(p.drop_p);
-        const float keep_scale = 1.0f / (1.0f - p.drop_p);
-        const uint32_t seed = rt_site_seed(p.seed_dev, p.drop_seed);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            v[r] = (rt_hash32(seed, (uint32_t)((o + r) >> p.drop_shift)) >= thresh) ? v[r] * keep_scale : 0.f;
-    }
-    if (!p.res_first) {
-        if (p.res_f32) v += PRE ? e->res : *reinterpret_cast<const f32x4*>(p.res_f32 + o);
-        if (p.res_bf16) {
-            const bf16x4 rr = PRE ? e->resb : *reinterpret_cast<const bf16x4*>(p.res_bf16 + o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] += (float)rr[r];
-        }
-    }
-    if (p.gate) {
-        const bf16x4 gg = PRE ? e->gate : *reinterpret_cast<const bf16x4*>(p.gate + o);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = ((float)gg[r] > 0.f) ? v[r] * p.gate_scale : 0.f;
-    }
-    if (p.preact) {
-        const bf16x4 uu = PRE ? e->preact : *reinterpret_cast<const bf16x4*>(p.preact + o);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= rt_gelu_grad((float)uu[r]);
-    }
-    if (p.dtanh) {
-        const bf16x4 tt = PRE ? e->dtanh : *reinterpret_cast<const bf16x4*>(p.dtanh + o);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= (1.f - (float)tt[r] * (float)tt[r]);
-    }
-    if (p.out_f32) *reinterpret_cast<f32x4*>(p.out_f32 + o) = v;
-    if (p.acc2_f32) *reinterpret_cast<f32x4*>(p.acc2_f32 + o) += v;          // a second, accumulating destination (one owner per element)
-    if (p.out_bf16) {
-        bf16x4 ov;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)v[r];
-        *reinterpret_cast<bf16x4*>(p.out_bf16 + o) = ov;
-    }
-}
-
-// Same epilogue on 8 consecutive output features of row m (the LDS-staged, row-coalesced path of the DMA kernel):
-// every global access is a full 16-B (bf16) / 32-B (fp32) contiguous piece of one output row.
-typedef __attribute__((ext_vector_type(8))) float f32x8;
-// `pre` (compile-time): the bf16 residual / gate pieces of this row piece were fetched at the start of the workgroup (pres, pgate).
-template <bool PRE = false>
-static __device__ __forceinline__ void epilogue8(const GemmArgs& p, int m, int n, f32x8 v, const bf16x8 pres = bf16x8{}, const bf16x8 pgate = bf16x8{}) {
-    const size_t o = (size_t)m * p.N + n;
+        for (int r = 0; r < W; ++r) b[r] = (bf16_t)v[r];
+        return b;
+    };
     if (p.bias) {
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.bias + n), b1 = *reinterpret_cast<const f32x4*>(p.bias + n + 4);
+        const epi_f32<W> bb = pre4_or_ld([](auto& x) { return x.bias; }, p.bias + n);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { v[r] += b0[r]; v[4 + r] += b1[r]; }
+        for (int r = 0; r < W; ++r) v[r] += bb[r];
     }
-    if (p.out_preact) {
-        bf16x8 pv;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) pv[r] = (bf16_t)v[r];
-        *reinterpret_cast<bf16x8*>(p.out_preact + o) = pv;
-    }
+    const size_t o = (size_t)m * p.N + n;
+    if (p.out_preact) *reinterpret_cast<epi_bf16<W>*>(p.out_preact + o) = to_bf16();
     auto add_res = [&]() __attribute__((always_inline)) {
-        if (p.res_f32) {
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(p.res_f32 + o), r1 = *reinterpret_cast<const f32x4*>(p.res_f32 + o + 4);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { v[r] += r0[r]; v[4 + r] += r1[r]; }
-        }
+        if (p.res_f32) v += pre4_or_ld([](auto& x) { return x.res; }, p.res_f32 + o);
         if (p.res_bf16) {
-            const bf16x8 rr = PRE ? pres : *reinterpret_cast<const bf16x8*>(p.res_bf16 + o);
+            const epi_bf16<W> rr = PRE ? e->resb : epi_ld<W>(p.res_bf16 + o);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] += (float)rr[r];
+            for (int r = 0; r < W; ++r) v[r] += (float)rr[r];
         }
     };
     if (p.res_first) add_res();
     if (p.act == RT_ACT_RELU) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], 0.f);
+        for (int r = 0; r < W; ++r) v[r] = fmaxf(v[r], 0.f);
     } else if (p.act == RT_ACT_GELU) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = rt_gelu(v[r]);
+        for (int r = 0; r < W; ++r) v[r] = rt_gelu(v[r]);
     } else if (p.act == RT_ACT_TANH) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = tanhf(v[r]);
+        for (int r = 0; r < W; ++r) v[r] = tanhf(v[r]);
     }
     if (p.drop_p > 0.f) {
         const uint32_t thresh = rt_drop_thresh(p.drop_p);
         const float keep_scale = 1.0f / (1.0f - p.drop_p);
         const uint32_t seed = rt_site_seed(p.seed_dev, p.drop_seed);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = (rt_hash32(seed, (uint32_t)((o + r) >> p.drop_shift)) >= thresh) ? v[r] * keep_scale : 0.f;
+        for (int r = 0; r < W; ++r)
+            v[r] = (rt_hash32(seed, (uint32_t)((o + r) >> p.drop_shift)) >= thresh) ? v[r] * keep_scale : 0.f;
     }
     if (!p.res_first) add_res();
     if (p.gate) {
-        const bf16x8 gg = PRE ? pgate : *reinterpret_cast<const bf16x8*>(p.gate + o);
+        const epi_bf16<W> gg = PRE ? e->gate : epi_ld<W>(p.gate + o);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = ((float)gg[r] > 0.f) ? v[r] * p.gate_scale : 0.f;
+        for (int r = 0; r < W; ++r) v[r] = ((float)gg[r] > 0.f) ? v[r] * p.gate_scale : 0.f;
     }
     if (p.preact) {
-        const bf16x8 uu = *reinterpret_cast<const bf16x8*>(p.preact + o);
+        const epi_bf16<W> uu = pre4_or_ld([](auto& x) { return x.preact; }, p.preact + o);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] *= rt_gelu_grad((float)uu[r]);
+        for (int r = 0; r < W; ++r) v[r] *= rt_gelu_grad((float)uu[r]);
     }
     if (p.dtanh) {
-        const bf16x8 tt = *reinterpret_cast<const bf16x8*>(p.dtanh + o);
+        const epi_bf16<W> tt = pre4_or_ld([](auto& x) { return x.dtanh; }, p.dtanh + o);
 #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] *= (1.f - (float)tt[r] * (float)tt[r]);
+        for (int r = 0; r < W; ++r) v[r] *= (1.f - (float)tt[r] * (float)tt[r]);
     }
+    auto quad = [&](int h) __attribute__((always_inline)) { return f32x4{v[h], v[h + 1], v[h + 2], v[h + 3]}; };
     if (p.out_f32) {
-        *reinterpret_cast<f32x4*>(p.out_f32 + o) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p.out_f32 + o + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
-    if (p.acc2_f32) {
-        *reinterpret_cast<f32x4*>(p.acc2_f32 + o) += f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p.acc2_f32 + o + 4) += f32x4{v[4], v[5], v[6], v[7]};
-    }
-    if (p.out_bf16) {
-        bf16x8 ov;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) ov[r] = (bf16_t)v[r];
-        *reinterpret_cast<bf16x8*>(p.out_bf16 + o) = ov;
+        for (int h = 0; h < W; h += 4) *reinterpret_cast<f32x4*>(p.out_f32 + o + h) = quad(h);
     }
+    if (p.acc2_f32) {                                // a second, accumulating destination (one owner per element)
+#pragma unroll
+        for (int h = 0; h < W; h += 4) *reinterpret_cast<f32x4*>(p.acc2_f32 + o + h) += quad(h);
+    }
+    if (p.out_bf16) *reinterpret_cast<epi_bf16<W>*>(p.out_bf16 + o) = to_bf16();
 }
 
 

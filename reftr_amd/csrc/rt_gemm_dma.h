@@ -15,6 +15,62 @@ namespace {
 // applied on the SOURCE side: lane l (row l>>3 of an 8-row group, slot l&7) fetches K chunk (l&7)^(l>>3) of its row.
 // Completion is tracked with the counted waits (rt_wait_vmcnt).
 
+// One wave's view of a staged K tile (64 k of A = BN weight rows, then of B = BM pixel rows; 128-B rows, 16-B slot ^= row & 7) and of
+// the fp32 output tile: waves are arranged 2(n) x WM(m), a wave owns TN x TM MFMA tiles of 16 x 16, lane = (li, lg).
+// Shared by gemm_dma_body, the register-staged lab kernel and (rt_frag) the activation-stationary kernel.
+__device__ __forceinline__ int rt_frag_slot(int kk, int li, int lg) { return ((kk * 4 + lg) ^ (li & 7)) << 4; }    // li & 7 == row & 7
+__device__ __forceinline__ const bf16x8* rt_frag(const unsigned char* slab, int row, int slot) {
+    return reinterpret_cast<const bf16x8*>(slab + slot + row * 128);
+}
+template <int BM, int BN, int WM>
+struct WaveTile {
+    static constexpr int TN = BN / 32, TM = BM / (16 * WM), A_BYTES = BN * 128, BUF_BYTES = (BM + BN) * 128;
+    int wn, wm, li, lg;
+    // fragment of A row-block a / B row-block b at k-step kk (32 k) of the stage at `st`
+    __device__ __forceinline__ const bf16x8* frag_a(const unsigned char* st, int a, int kk) const {
+        const int slot = rt_frag_slot(kk, li, lg);
+        return rt_frag(st, wn * (BN / 2) + a * 16 + li, slot);
+    }
+    __device__ __forceinline__ const bf16x8* frag_b(const unsigned char* st, int b, int kk) const {
+        const int slot = rt_frag_slot(kk, li, lg);
+        return rt_frag(st + A_BYTES, wm * (BM / WM) + b * 16 + li, slot);
+    }
+    __device__ __forceinline__ void read_frags_k(const unsigned char* st, int kk, bf16x8 (&fa)[TN], bf16x8 (&fb)[TM]) const {
+#pragma unroll
+        for (int a = 0; a < TN; ++a) fa[a] = *frag_a(st, a, kk);
+#pragma unroll
+        for (int b = 0; b < TM; ++b) fb[b] = *frag_b(st, b, kk);
+    }
+    static __device__ __forceinline__ void mma_k(const bf16x8 (&fa)[TN], const bf16x8 (&fb)[TM], f32x4 (&acc)[TN][TM]) {
+#pragma unroll
+        for (int a = 0; a < TN; ++a)
+#pragma unroll
+            for (int b = 0; b < TM; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+    }
+    __device__ __forceinline__ void read_frags(const unsigned char* st, bf16x8 (&fa)[2][TN], bf16x8 (&fb)[2][TM]) const {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) read_frags_k(st, kk, fa[kk], fb[kk]);
+    }
+    static __device__ __forceinline__ void mma(const bf16x8 (&fa)[2][TN], const bf16x8 (&fb)[2][TM], f32x4 (&acc)[TN][TM]) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) mma_k(fa[kk], fb[kk], acc);
+    }
+    // one K tile, a k-step at a time (one fragment set live)
+    __device__ __forceinline__ void compute(const unsigned char* st, f32x4 (&acc)[TN][TM]) const {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            bf16x8 fa[TN], fb[TM];
+            read_frags_k(st, kk, fa, fb);
+            mma_k(fa, fb, acc);
+        }
+    }
+    // accumulator (a, b), the lane's 4 consecutive features of one row (C/D layout of the MFMA), in an fp32 tile of row length ld
+    // in which this wave's rows are wave row wr's
+    __device__ __forceinline__ f32x4* acc_at(float* tile, int ld, int wr, int a, int b) const {
+        return reinterpret_cast<f32x4*>(tile + (wr * (BM / WM) + b * 16 + li) * ld + wn * (BN / 2) + a * 16 + lg * 4);
+    }
+};
+
 // The body is a device function: it runs as a kernel of its own (conv_gemm_dma_kernel) or as one of up to 12 independent
 // problems of a grouped launch (conv_gemm_dma_grouped_kernel); bx / by / gx stand for blockIdx.x / blockIdx.y / gridDim.x.
 // NW = 4 waves arranged 2(n) x 2(m), or 8 waves 2(n) x 4(m): the same tile with smaller wave tiles and twice the waves per CU
@@ -28,11 +84,12 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
     constexpr bool PP = PIPE == 2;                                 // the ping-pong form
     constexpr int NWG = PP ? NW / 2 : NW;                  // waves of one compute group
     constexpr int NT = 64 * NW, GT = 64 * NWG, WM = NWG / 2, RPP = GT / 8;   // threads, group threads, waves along m, rows one DMA pass covers
-    constexpr int TM = BM / (16 * WM), TN = BN / 32;
+    typedef WaveTile<BM, BN, WM> WT;
+    constexpr int TM = WT::TM, TN = WT::TN;
     constexpr int AJ = BN / RPP, BJ = BM / RPP;
     static_assert(NW == 4 || NW == 8, "4 or 8 waves"); static_assert(AJ >= 1 && BJ >= 1 && TM >= 1, "tile too small for the wave count");
     static_assert(!PP || (NW == 8 && (NS == 3 || NS == 4)), "ping-pong form: 8 waves, 3 or 4 stages");
-    constexpr int A_BYTES = BN * 128, B_BYTES = BM * 128, BUF_BYTES = A_BYTES + B_BYTES;
+    constexpr int A_BYTES = WT::A_BYTES, BUF_BYTES = WT::BUF_BYTES;
     constexpr int LPT = AJ + BJ;                   // DMA instructions per thread per K tile
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -42,6 +99,7 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
     const int grp = PP ? __builtin_amdgcn_readfirstlane(t >> 6) / NWG : 0;
     const int wn = wave & 1, wm = wave >> 1;
     const int li = lane & 15, lg = lane >> 4;
+    const WT wt{wn, wm, li, lg};
 
     const int n_tiles = (p.N + BN - 1) / BN;
     const int bid = rt_xcd_remap(bx, gx, p.xcd);
@@ -154,30 +212,9 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
         for (int i = 0; i < LPT; ++i) issue_piece(buf, i);
     };
     auto issue_tile = [&](int buf) __attribute__((always_inline)) { issue_only(buf); advance_k(); };
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-        const unsigned char* bA = smem + buf * BUF_BYTES;
-        const unsigned char* bB = bA + A_BYTES;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            bf16x8 af[TN], bfr[TM];
-            const int slot = ((kk * 4 + lg) ^ (li & 7)) << 4;
-#pragma unroll
-            for (int a = 0; a < TN; ++a) {
-                const int row = wn * (BN / 2) + a * 16 + li;
-                af[a] = *reinterpret_cast<const bf16x8*>(bA + row * 128 + slot);
-            }
-#pragma unroll
-            for (int b = 0; b < TM; ++b) {
-                const int row = wm * (BM / WM) + b * 16 + li;
-                bfr[b] = *reinterpret_cast<const bf16x8*>(bB + row * 128 + slot);
-            }
-#pragma unroll
-            for (int a = 0; a < TN; ++a)
-#pragma unroll
-                for (int b = 0; b < TM; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
-        }
-    };
+    auto read_frags = [&](int buf, bf16x8 (&fa)[2][TN], bf16x8 (&fb)[2][TM]) __attribute__((always_inline)) { wt.read_frags(smem + buf * BUF_BYTES, fa, fb); };
+    auto mma = [&](const bf16x8 (&fa)[2][TN], const bf16x8 (&fb)[2][TM]) __attribute__((always_inline)) { WT::mma(fa, fb, acc); };
+    auto compute = [&](int buf) __attribute__((always_inline)) { wt.compute(smem + buf * BUF_BYTES, acc); };
 
     // Epilogue operands first: the bf16 residual / ReLU-gate pieces this thread will need in the row-coalesced epilogue are
     // requested BEFORE the first operand tile, so that their HBM latency runs under the K loop instead of in front of the
@@ -193,25 +230,25 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
     constexpr bool CAN_PRE = HALVES == 1 && PIECES <= 4;
     const bool epi_lds = p.epi_lds && (p.N & 7) == 0;
     const bool pre = CAN_PRE && epi_lds && p.prefetch && (p.res_bf16 || p.gate);
-    bf16x8 pre_res[CAN_PRE ? PIECES : 1], pre_gate[CAN_PRE ? PIECES : 1];
+    EpiPre<8> epre[CAN_PRE ? PIECES : 1];
+    auto out_row = [&](int m) __attribute__((always_inline)) -> int {      // MODE 3: class-local row -> pixel row of the NHWC output
+        if (MODE != 3) return m;
+        const int xx = m % nx, tmp = m / nx, yy = tmp % ny, bb = tmp / ny;
+        return (bb * p.DH + 2 * yy + cy) * p.DW + 2 * xx + cx;
+    };
     auto out_piece = [&](int idx, int& m, int& n) __attribute__((always_inline)) -> bool {
         const int rl = idx / CPR, cl = (idx - rl * CPR) * 8;
         m = m0 + rl; n = n0 + cl;
         if (m >= Mloc || n >= p.N) return false;
-        if (MODE == 3) {
-            const int xx = m % nx, tmp = m / nx, yy = tmp % ny, bb = tmp / ny;
-            m = (bb * p.DH + 2 * yy + cy) * p.DW + 2 * xx + cx;
-        }
+        m = out_row(m);
         return true;
     };
     if (CAN_PRE && pre) {
 #pragma unroll
         for (int i = 0; i < PIECES; ++i) {
-            int m, n;
+            int m = 0, n = 0;
             const bool ok = (!RAGGED_PIECES || i * NT + t < ROWS * CPR) && out_piece(i * NT + t, m, n);
-            const size_t o = ok ? (size_t)m * p.N + n : 0;
-            pre_res[i] = p.res_bf16 ? *reinterpret_cast<const bf16x8*>(p.res_bf16 + o) : bf16x8{};
-            pre_gate[i] = p.gate ? *reinterpret_cast<const bf16x8*>(p.gate + o) : bf16x8{};
+            epre[i] = epi_prefetch<8>(p, ok ? (size_t)m * p.N + n : 0, n);
         }
     }
 
@@ -276,8 +313,7 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
         int rs = grp, ws = (grp + DEPTH) % NS;                                 // stage of tile j / of tile j + DEPTH
         for (int it = 0, j = grp; it < iters; ++it, j += 2) {
             if (j < nk) {                                                      // M(j)
-                const unsigned char* rA = smem + rs * BUF_BYTES;
-                const unsigned char* rB = rA + A_BYTES;
+                const unsigned char* st = smem + rs * BUF_BYTES;
                 auto m_body = [&](auto with_dma) __attribute__((always_inline)) {
 #pragma unroll
                     for (int i = 0; i < LPT; ++i) {
@@ -286,9 +322,8 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
 #pragma unroll
                             for (int r = 2 * i; r < 2 * i + 2; ++r) {          // read r of the tile: kk-major, weights then activations
                                 const int kk = r / LPT, q = r % LPT;
-                                const int slot = ((kk * 4 + lg) ^ (li & 7)) << 4;
-                                if (q < TN) fa[kk][q] = *reinterpret_cast<const bf16x8*>(rA + (wn * (BN / 2) + q * 16 + li) * 128 + slot);
-                                else fb[kk][q - TN] = *reinterpret_cast<const bf16x8*>(rB + (wm * (BM / WM) + (q - TN) * 16 + li) * 128 + slot);
+                                if (q < TN) fa[kk][q] = *wt.frag_a(st, q, kk);
+                                else fb[kk][q - TN] = *wt.frag_b(st, q - TN, kk);
                             }
                         }
                     }
@@ -302,13 +337,7 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
             if (j < nk) {                                                      // X(j)
                 if (!PP_ABL(2)) {
                     if (!PP_ABL(32)) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                        for (int a = 0; a < TN; ++a)
-#pragma unroll
-                            for (int b = 0; b < TM; ++b)
-                                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][a], fb[kk][b], acc[a][b], 0, 0, 0);
+                    mma(fa, fb);
                     if (!PP_ABL(32)) __builtin_amdgcn_s_setprio(0);
                 } else {
 #pragma unroll
@@ -336,27 +365,6 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
         // The barrier orders three things at once: tile kt+1's bytes are visible to every wave; every wave's reads of tile kt's
         // stage have returned (they are consumed by MFMAs issued before it) so the stage may be overwritten; and the reads of
         // tile kt+1 are issued one full MFMA phase before their first use.
-        auto read_frags = [&](int buf, bf16x8 (&fa)[2][TN], bf16x8 (&fb)[2][TM]) __attribute__((always_inline)) {
-            const unsigned char* bA = smem + buf * BUF_BYTES;
-            const unsigned char* bB = bA + A_BYTES;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int slot = ((kk * 4 + lg) ^ (li & 7)) << 4;
-#pragma unroll
-                for (int a = 0; a < TN; ++a) fa[kk][a] = *reinterpret_cast<const bf16x8*>(bA + (wn * (BN / 2) + a * 16 + li) * 128 + slot);
-#pragma unroll
-                for (int b = 0; b < TM; ++b) fb[kk][b] = *reinterpret_cast<const bf16x8*>(bB + (wm * (BM / WM) + b * 16 + li) * 128 + slot);
-            }
-        };
-        auto mma = [&](const bf16x8 (&fa)[2][TN], const bf16x8 (&fb)[2][TM]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int a = 0; a < TN; ++a)
-#pragma unroll
-                    for (int b = 0; b < TM; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][a], fb[kk][b], acc[a][b], 0, 0, 0);
-        };
 #pragma unroll
         for (int s = 0; s < NS; ++s) issue_tile(s);          // tiles 0 .. NS-1 (past the end: the last tile again, never consumed)
         bf16x8 fa0[2][TN], fb0[2][TM], fa1[2][TN], fb1[2][TM];
@@ -431,7 +439,7 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
                 for (int a = 0; a < TN; ++a)
 #pragma unroll
                     for (int b = 0; b < TM; ++b)
-                        *reinterpret_cast<f32x4*>(tile + (wm * (BM / WM) + b * 16 + li) * EP_LD + wn * (BN / 2) + a * 16 + lg * 4) = acc[a][b];
+                        *wt.acc_at(tile, EP_LD, wm, a, b) = acc[a][b];
             }
             __syncthreads();
             if (grp == 0) {
@@ -439,7 +447,7 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
                 for (int a = 0; a < TN; ++a)
 #pragma unroll
                     for (int b = 0; b < TM; ++b)
-                        acc[a][b] += *reinterpret_cast<const f32x4*>(tile + (wm * (BM / WM) + b * 16 + li) * EP_LD + wn * (BN / 2) + a * 16 + lg * 4);
+                        acc[a][b] += *wt.acc_at(tile, EP_LD, wm, a, b);
             }
         }
 #pragma unroll
@@ -450,7 +458,7 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
                 for (int a = 0; a < TN; ++a)
 #pragma unroll
                     for (int b = 0; b < TM; ++b)
-                        *reinterpret_cast<f32x4*>(tile + ((HALVES == 1 ? wm : wm % (WM / 2)) * (BM / WM) + b * 16 + li) * EP_LD + wn * (BN / 2) + a * 16 + lg * 4) = acc[a][b];
+                        *wt.acc_at(tile, EP_LD, HALVES == 1 ? wm : wm % (WM / 2), a, b) = acc[a][b];
             }
             __syncthreads();
 #pragma unroll
@@ -460,10 +468,9 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
                 int m, n;
                 if (RAGGED_PIECES && idx >= ROWS * CPR) continue;
                 if (!out_piece(h * ROWS * CPR + idx, m, n)) continue;
-                const f32x4 lo4 = *reinterpret_cast<const f32x4*>(tile + rl * EP_LD + cl), hi4 = *reinterpret_cast<const f32x4*>(tile + rl * EP_LD + cl + 4);
-                const f32x8 v8 = f32x8{lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-                if (CAN_PRE && pre) epilogue8<true>(p, m, n, v8, pre_res[CAN_PRE ? i : 0], pre_gate[CAN_PRE ? i : 0]);
-                else epilogue8(p, m, n, v8);
+                const f32x8 v8 = epi_ld<8>(tile + rl * EP_LD + cl);
+                if (CAN_PRE && pre) epilogue<8, true>(p, m, n, v8, &epre[CAN_PRE ? i : 0]);
+                else epilogue<8>(p, m, n, v8);
             }
         }
         return;
@@ -475,13 +482,9 @@ __device__ __forceinline__ void gemm_dma_body(const bf16_t* __restrict__ src, co
         if (n >= p.N) continue;
 #pragma unroll
         for (int b = 0; b < TM; ++b) {
-            int m = m0 + wm * (BM / WM) + b * 16 + li;
+            const int m = m0 + wm * (BM / WM) + b * 16 + li;
             if (m >= Mloc) continue;
-            if (MODE == 3) {            // class-local row -> pixel row of the NHWC output
-                const int xx = m % nx, tmp = m / nx, yy = tmp % ny, bb = tmp / ny;
-                m = (bb * p.DH + 2 * yy + cy) * p.DW + 2 * xx + cx;
-            }
-            epilogue4(p, m, n, acc[a][b]);
+            epilogue<4>(p, out_row(m), n, acc[a][b]);
         }
     }
 }
@@ -492,58 +495,55 @@ __global__ __launch_bounds__(64 * NW, MINB) void conv_gemm_dma_kernel(const bf16
     gemm_dma_body<BM, BN, MODE, NS, NW, PIPE>(src, wgt, p, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
 }
 
-template <int BM, int BN, int NS, int MINB, int NW = 4, int PIPE = 0>
-int launch_gemm_dma(const GemmArgs& a, hipStream_t s) {
+constexpr size_t gemm_dma_lds_bytes(int BM, int BN, int NS) { return (size_t)NS * (BM + BN) * 128; }
+
+// MODE 0 launch: LDS attribute, tile order, launch
+template <int BM, int BN, int NS, int MINB, int NW, int PIPE>
+void launch_gemm_dma_mode0(const GemmArgs& a, hipStream_t s) {
     const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    const size_t smem = (size_t)NS * (BM + BN) * 128;
-    const dim3 grid((unsigned)(mt * nt)), block(64 * NW);
-    const bool dense = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW);
-    static const int par_env = RT_TUNE("REFTR_S2PARITY", 1);
-    auto set_smem = [&](const void* f) {
-        if (smem > 65536) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    };
-    if (dense) {
-        set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 0, NS, MINB, NW, PIPE>);
-        // distinct operand slabs an XCD's run of R tiles touches: R / n_tiles + min(R, n_tiles) (n fastest) vs the same with m_tiles
-        static const int mfast_env = RT_TUNE("REFTR_MFAST", 1);
-        GemmArgs am = a;
-        const double R = (double)(mt * nt) / 8.0;
-        const double cn = R / nt + (R < nt ? R : nt), cm = R / mt + (R < mt ? R : mt);
-        am.mfast = (mfast_env && a.xcd && mt * nt >= 16 && cm < cn) ? 1 : 0;
-        hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 0, NS, MINB, NW, PIPE>), grid, block, smem, s, a.src, a.wgt, am);
-    } else if (!a.transposed) {
-        set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 1, NS, MINB, NW, PIPE>);
-        hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 1, NS, MINB, NW, PIPE>), grid, block, smem, s, a.src, a.wgt, a);
-    } else if (a.stride == 2 && par_env) {
-        const int m_cls = a.B * ((a.DH + 1) / 2) * ((a.DW + 1) / 2);           // largest parity class
-        // grid.x padded to a multiple of 8: block (x, y) has linear id y * gridDim.x + x, so only then do the four parity classes
-        // of a tile range (they gather from the same dy rows) sit on the same XCD as the tile map assumes (surplus blocks exit)
-        const dim3 grid3((unsigned)(((((m_cls + BM - 1) / BM) * nt) + 7) / 8 * 8), 4);
-        set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 3, NS, MINB, NW, PIPE>);
-        hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 3, NS, MINB, NW, PIPE>), grid3, block, smem, s, a.src, a.wgt, a);
+    const size_t smem = gemm_dma_lds_bytes(BM, BN, NS);
+    const auto kern = conv_gemm_dma_kernel<BM, BN, 0, NS, MINB, NW, PIPE>;
+    if (smem > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    // distinct operand slabs an XCD's run of R tiles touches: R / n_tiles + min(R, n_tiles) (n fastest) vs the same with m_tiles
+    static const int mfast_env = RT_TUNE("REFTR_MFAST", 1);
+    GemmArgs am = a;
+    const double R = (double)(mt * nt) / 8.0;
+    const double cn = R / nt + (R < nt ? R : nt), cm = R / mt + (R < mt ? R : mt);
+    am.mfast = (mfast_env && a.xcd && mt * nt >= 16 && cm < cn) ? 1 : 0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(mt * nt)), dim3(64 * NW), smem, s, a.src, a.wgt, am);
+}
+
+// DENSE_ONLY (the small-tile variants for the M = B * L products of the language branch): the gather modes are not instantiated
+template <int BM, int BN, int NS, int MINB, int NW = 4, int PIPE = 0, bool DENSE_ONLY = false>
+int launch_gemm_dma(const GemmArgs& a, hipStream_t s) {
+    if (gemm_dense(a)) {
+        launch_gemm_dma_mode0<BM, BN, NS, MINB, NW, PIPE>(a, s);
+    } else if constexpr (DENSE_ONLY) {
+        return RT_ERR_UNSUPPORTED;
     } else {
-        set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 2, NS, MINB, NW, PIPE>);
-        hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 2, NS, MINB, NW, PIPE>), grid, block, smem, s, a.src, a.wgt, a);
+        const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
+        const size_t smem = gemm_dma_lds_bytes(BM, BN, NS);
+        const dim3 grid((unsigned)(mt * nt)), block(64 * NW);
+        static const int par_env = RT_TUNE("REFTR_S2PARITY", 1);
+        auto set_smem = [&](const void* f) {
+            if (smem > 65536) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        };
+        if (!a.transposed) {
+            set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 1, NS, MINB, NW, PIPE>);
+            hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 1, NS, MINB, NW, PIPE>), grid, block, smem, s, a.src, a.wgt, a);
+        } else if (a.stride == 2 && par_env) {
+            const int m_cls = a.B * ((a.DH + 1) / 2) * ((a.DW + 1) / 2);           // largest parity class
+            // grid.x padded to a multiple of 8: block (x, y) has linear id y * gridDim.x + x, so only then do the four parity classes
+            // of a tile range (they gather from the same dy rows) sit on the same XCD as the tile map assumes (surplus blocks exit)
+            const dim3 grid3((unsigned)(((((m_cls + BM - 1) / BM) * nt) + 7) / 8 * 8), 4);
+            set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 3, NS, MINB, NW, PIPE>);
+            hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 3, NS, MINB, NW, PIPE>), grid3, block, smem, s, a.src, a.wgt, a);
+        } else {
+            set_smem((const void*)conv_gemm_dma_kernel<BM, BN, 2, NS, MINB, NW, PIPE>);
+            hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 2, NS, MINB, NW, PIPE>), grid, block, smem, s, a.src, a.wgt, a);
+        }
     }
     RT_CHECK_LAUNCH();
     return RT_OK;
 }
-
-// dense rows only (Linears): the small-tile variants for the M = B * L products of the language branch
-template <int BM, int BN, int NS, int MINB, int NW = 4, int PIPE = 0>
-int launch_gemm_dma_dense(const GemmArgs& a, hipStream_t s) {
-    const int mt = (a.M + BM - 1) / BM, nt = (a.N + BN - 1) / BN;
-    const size_t smem = (size_t)NS * (BM + BN) * 128;
-    const bool dense = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.SH == a.DH && a.SW == a.DW);
-    if (!dense) return RT_ERR_UNSUPPORTED;
-    if (smem > 65536) (void)hipFuncSetAttribute((const void*)conv_gemm_dma_kernel<BM, BN, 0, NS, MINB, NW, PIPE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    GemmArgs am = a;
-    const double R = (double)(mt * nt) / 8.0;
-    const double cn = R / nt + (R < nt ? R : nt), cm = R / mt + (R < mt ? R : mt);
-    am.mfast = (a.xcd && mt * nt >= 16 && cm < cn) ? 1 : 0;
-    hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 0, NS, MINB, NW, PIPE>), dim3((unsigned)(mt * nt)), dim3(64 * NW), smem, s, a.src, a.wgt, am);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
-}
-
 }  // namespace

@@ -118,15 +118,31 @@ def test_linear_fwd(hip, M, K, N, hint):
     assert torch.allclose(of.cpu()[M - 1, N - 1], ref[M - 1, N - 1], rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("hint", [0, 501, 351, 331, 321, 352, 332])
+PP_ASTAT_HINTS = (501, 351, 331, 321, 352, 332)        # forms whose partial sums / row pieces need N % 8 == 0
+# M, K, N, hints that take the shape.  192: the 8-wide LDS-staged epilogue; 196 (N % 8 == 4): the 4-wide epilogue of the same tile
+# kernels; 12 rows: the skinny kernel with its prefetched epilogue operands (tile_hint 0 only).
+EPILOGUE_SHAPES = [
+    (333, 128, 192, None),
+    (333, 128, 196, (0, 21, 31, 33, 51)),
+    (12, 128, 192, (0,)),
+]
+
+
+@pytest.mark.parametrize("hint", [0, 21, 31, 33, 51, 233, 252, 262, 281, 285, 501, 351, 331, 321, 352, 332])
 def test_linear_epilogue(hip, hint):
+    """Every epilogue field against the fp32 torch expression, on every variant that takes the shape."""
     with lib_for(hip, hint):
-        _linear_epilogue(hip, hint)
+        for M, K, N, hints in EPILOGUE_SHAPES:
+            if hints is None or hint in hints:
+                _linear_epilogue(hip, hint, M, K, N)
+            elif N % 8 and hint in PP_ASTAT_HINTS:
+                x = torch.zeros(M, K, dtype=torch.bfloat16, device="cuda"); w = torch.zeros(N, K, dtype=torch.bfloat16, device="cuda")
+                with pytest.raises(RuntimeError):
+                    hip.linear(x, w, tile_hint=hint)
 
 
-def _linear_epilogue(hip, hint):
+def _linear_epilogue(hip, hint, M=333, K=128, N=192):
     g = torch.Generator().manual_seed(5)
-    M, K, N = 333, 128, 192
     x = bf(torch.randn(M, K, generator=g)); w = bf(torch.randn(N, K, generator=g) / K ** 0.5)
     b = torch.randn(N, generator=g)
     rf = torch.randn(M, N, generator=g); rb = bf(torch.randn(M, N, generator=g))
@@ -149,7 +165,28 @@ def _linear_epilogue(hip, hint):
     _, of = hip.linear(xc, wc, bias=bc, drop_p=p, drop_seed=seed, out_bf16=False, out_f32=True, tile_hint=hint)
     keep = torch.from_numpy(hash_keep(seed, np.arange(M * N, dtype=np.uint64), p).reshape(M, N))
     assert rel(of, lin * keep / (1 - np.float32(p))) < TOL_F32
-    assert abs(float(keep.float().mean()) - 0.9) < 0.01
+    if M * N >= 60000:      # the keep rate of the hash itself: 0.01 is > 8 sigma of a 60 000-element sample, not of the 12-row one
+        assert abs(float(keep.float().mean()) - 0.9) < 0.01
+    # ... shared by 4 neighbours with drop_shift = 2
+    _, of = hip.linear(xc, wc, bias=bc, drop_p=p, drop_seed=seed, drop_shift=2, out_bf16=False, out_f32=True, tile_hint=hint)
+    keep4 = torch.from_numpy(hash_keep(seed, np.arange(M * N, dtype=np.uint64) >> np.uint64(2), p).reshape(M, N))
+    assert rel(of, lin * keep4 / (1 - np.float32(p))) < TOL_F32
+    # residual BEFORE the activation (differs from residual-last: relu(lin) + res)
+    res = rf + rb.float()
+    _, of = hip.linear(xc, wc, bias=bc, res_f32=rf.cuda(), res_bf16=rb.cuda(), res_first=True, act=hip.ACT_RELU, out_bf16=False, out_f32=True,
+                       tile_hint=hint)
+    assert rel(of, torch.relu(lin + res)) < TOL_F32
+    assert rel(torch.relu(lin) + res, torch.relu(lin + res)) > 0.1
+    # * (1 - t^2) of a stored tanh output
+    _, of = hip.linear(xc, wc, bias=bc, dtanh=pre.cuda(), out_bf16=False, out_f32=True, tile_hint=hint)
+    assert rel(of, lin * (1 - pre.float() ** 2)) < TOL_F32
+    # the bf16 pre-activation (bias added, nothing else) beside the activated output
+    _, of, op = hip.linear(xc, wc, bias=bc, act=hip.ACT_RELU, out_bf16=False, out_f32=True, out_preact=True, tile_hint=hint)
+    assert rel(of, torch.relu(lin)) < TOL_F32 and rel(op, lin) < TOL_BF16
+    # the second, accumulating fp32 destination
+    acc2 = torch.full((M, N), 0.5, device="cuda")
+    _, of = hip.linear(xc, wc, bias=bc, acc2_f32=acc2, out_bf16=False, out_f32=True, tile_hint=hint)
+    assert rel(of, lin) < TOL_F32 and rel(acc2, lin + 0.5) < TOL_F32
 
 
 CONV_CASES = [
