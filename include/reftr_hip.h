@@ -575,6 +575,20 @@ int rt_adamw_flat(const rt_adamw_desc* d, rt_stream_t stream);
  * buffers and with the same descriptor: m = momentum buffer (zero-initialised), beta1 = momentum, v / beta2 / eps / step unused:
  *   g' = clip * grad_scale * g + wd * p;  m = beta1 * m + g';  p -= lr * m.   Clip coefficient and 1/world as in rt_adamw_flat. */
 int rt_sgd_flat(const rt_adamw_desc* d, rt_stream_t stream);
+/* rt_grad_accum — gradient accumulation over the micro-batches of one window (one update per k backward passes: the published
+ * global batch on one GPU), over the flat fp32 gradient buffer `g` and an accumulator `acc` of the same size (both 4-byte aligned;
+ * 16-byte accesses wherever the two reach a 16-byte boundary together, coalesced 4-byte accesses over the same grid where they never do):
+ *   RT_ACCUM_FIRST   acc = g                        (first micro-batch: no clear of the accumulator is ever needed)
+ *   RT_ACCUM_ADD     acc += g
+ *   RT_ACCUM_FINISH  g = (acc + g) * s  and  out_sq[0] = sum of the squares of the values written -- what rt_sqnorm would return for
+ *                    the averaged buffer, so the clip norm costs no further pass.  s = scale, or scale_dev[0] when `scale_dev` (DEVICE
+ *                    float, optional) is given: one captured launch serves any window length, like lr_dev of rt_adamw_desc.
+ * `partials` (FINISH only): RT_GRAD_ACCUM_SLOTS floats of workspace, one per workgroup; a second one-workgroup launch adds them in a
+ * fixed order (no atomics: the same bits from run to run).  Nothing is allocated; FIRST / ADD are one launch. */
+enum { RT_ACCUM_FIRST = 0, RT_ACCUM_ADD = 1, RT_ACCUM_FINISH = 2 };
+#define RT_GRAD_ACCUM_SLOTS 2048
+int rt_grad_accum(int mode, float* g, float* acc, int64_t n, float scale, const float* scale_dev, float* partials, float* out_sq,
+                  rt_stream_t stream);
 /* rt_zero_chunks — clears `n` chunks of an fp32 buffer in one launch: table (DEVICE, static) = n x {int64 element offset, int64
  * element count (<= 16384)}.  Used for the gradient tensors that are accumulated with atomics (biases, norm parameters,
  * embeddings) when the weight matrices are produced in overwrite mode and the full clear of the gradient buffer is skipped. */

@@ -2,6 +2,7 @@
 //   rt_sqnorm      global L2 norm^2 of the flat gradient (clip_grad_norm_'s total norm)
 //   rt_adamw_flat  gradient scale (1/world) + clip coefficient + decoupled-weight-decay AdamW, 28 B/param of
 //                  HBM traffic in a single streaming pass, per-range learning rates (param groups)
+//   rt_grad_accum  the gradients of k micro-batches averaged in a second flat buffer before the one clip + update of the window
 #include "rt_common.h"
 #include <stdlib.h>
 
@@ -418,6 +419,65 @@ __global__ void finish_stats_kernel(const rt_finish_desc d) {
     }
 }
 
+// ---- gradient accumulation over micro-batches (rt_grad_accum): acc = g | acc += g | g = (acc + g) * s with sum g^2 of what was written.
+// A pure streaming pass: 16-byte accesses over the part of the buffers where g and acc are both 16-byte aligned, the (at most 3 + 3)
+// elements in front of / behind it one by one; buffers whose two misalignments differ go one element at a time altogether (head == n),
+// grid-strided over as many workgroups as the vector path would use per element -- coalesced 4-byte accesses, not one workgroup's walk.
+// FINISH adds and scales in double: the value written is then ONE fp32 rounding away from (acc + g) * s, whatever s is.  Its squared
+// norm leaves no atomics behind: every workgroup stores its partial sum into its own slot and grad_accum_sum_kernel adds the slots in
+// a fixed order, so the clip norm of a window is the same from run to run.
+constexpr int GA_FIRST = 0, GA_ADD = 1, GA_FINISH = 2;
+template <int MODE>
+__device__ __forceinline__ float grad_accum_elem(float gv, float av, float s) {
+    if (MODE == GA_FIRST) return gv;
+    if (MODE == GA_ADD) return av + gv;
+    return (float)(((double)av + (double)gv) * (double)s);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ g, float* __restrict__ acc, size_t n, size_t head,
+                                                         float scale, const float* __restrict__ scale_dev, float* __restrict__ partials) {
+    __shared__ float sm[16];
+    const float s = (MODE == GA_FINISH && scale_dev) ? scale_dev[0] : scale;
+    const size_t n4 = (n - head) >> 2;
+    f32x4* G4 = reinterpret_cast<f32x4*>(g + head);
+    f32x4* A4 = reinterpret_cast<f32x4*>(acc + head);
+    float sq = 0.f;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const f32x4 gv = __builtin_nontemporal_load(G4 + i);
+        f32x4 av = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (MODE != GA_FIRST) av = __builtin_nontemporal_load(A4 + i);
+        f32x4 r;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) r[c] = grad_accum_elem<MODE>(gv[c], av[c], s);
+        if (MODE == GA_FINISH) { G4[i] = r; sq += (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]); }
+        else __builtin_nontemporal_store(r, A4 + i);
+    }
+    {                                                   // the unaligned head and the tail: fewer than 8 elements unless head == n
+        const size_t tail0 = head + (n4 << 2), rest = head + (n - tail0);
+        for (size_t j = blockIdx.x * (size_t)256 + threadIdx.x; j < rest; j += (size_t)gridDim.x * 256) {
+            const size_t i = j < head ? j : tail0 + (j - head);
+            const float r = grad_accum_elem<MODE>(g[i], MODE != GA_FIRST ? acc[i] : 0.f, s);
+            if (MODE == GA_FINISH) { g[i] = r; sq += r * r; } else acc[i] = r;
+        }
+    }
+    if (MODE == GA_FINISH) {
+        sq = rt_block_sum(sq, sm);
+        if (threadIdx.x == 0) partials[blockIdx.x] = sq;
+    }
+}
+__global__ __launch_bounds__(256) void grad_accum_sum_kernel(const float* __restrict__ partials, int n, float* __restrict__ out) {
+    __shared__ double sd[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += (double)partials[i];
+    sd[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sd[threadIdx.x] += sd[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)sd[0];
+}
+
 }  // namespace
 
 extern "C" int rt_counter_add(int32_t* ctr, int32_t inc, rt_stream_t stream) {
@@ -579,5 +639,29 @@ extern "C" int rt_sgd_flat(const rt_adamw_desc* d, rt_stream_t stream) {
     int blocks = (int)(((size_t)(a.span_end - a.span_begin) / 4 + 255) / 256); if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     RT_CHECK_LAUNCH();
+    return RT_OK;
+}
+
+extern "C" int rt_grad_accum(int mode, float* g, float* acc, int64_t n, float scale, const float* scale_dev, float* partials,
+                             float* out_sq, rt_stream_t stream) {
+    if (!g || !acc || n <= 0) return RT_ERR_BADARG;
+    if (mode != GA_FIRST && mode != GA_ADD && mode != GA_FINISH) return RT_ERR_UNSUPPORTED;
+    if (mode == GA_FINISH && (!partials || !out_sq)) return RT_ERR_BADARG;
+    if (((uintptr_t)g & 3) || ((uintptr_t)acc & 3)) return RT_ERR_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    // elements in front of the first 16-byte boundary; the vector part needs g and acc to reach it together
+    size_t head = ((16 - ((uintptr_t)g & 15)) & 15) >> 2;
+    if (((uintptr_t)g & 15) != ((uintptr_t)acc & 15) || head > (size_t)n) head = (size_t)n;
+    const size_t n4 = ((size_t)n - head) >> 2;
+    const size_t work = n4 ? n4 : (size_t)n;            // 16-byte accesses, or (n4 == 0) single elements over the whole grid
+    int blocks = (int)((work + 255) / 256); if (blocks > RT_GRAD_ACCUM_SLOTS) blocks = RT_GRAD_ACCUM_SLOTS;
+    if (mode == GA_FIRST) hipLaunchKernelGGL(grad_accum_kernel<GA_FIRST>, dim3(blocks), dim3(256), 0, s, g, acc, (size_t)n, head, scale, scale_dev, partials);
+    else if (mode == GA_ADD) hipLaunchKernelGGL(grad_accum_kernel<GA_ADD>, dim3(blocks), dim3(256), 0, s, g, acc, (size_t)n, head, scale, scale_dev, partials);
+    else hipLaunchKernelGGL(grad_accum_kernel<GA_FINISH>, dim3(blocks), dim3(256), 0, s, g, acc, (size_t)n, head, scale, scale_dev, partials);
+    RT_CHECK_LAUNCH();
+    if (mode == GA_FINISH) {
+        hipLaunchKernelGGL(grad_accum_sum_kernel, dim3(1), dim3(256), 0, s, partials, blocks, out_sq);
+        RT_CHECK_LAUNCH();
+    }
     return RT_OK;
 }

@@ -150,9 +150,35 @@ def _coop_fallback(model):
               "is discarded and run again; the decoder uses the launched chain (REFTR_DEC_COOP=0) from here on.", file=sys.stderr)
 
 
-def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0):
+def _require_accumulation(optimizer):
+    """accum_steps > 1 needs the fused optimizer's accumulator, on a single-process fp32 gradient buffer."""
+    if not hasattr(optimizer, "finish_accumulation"):
+        raise NotImplementedError("accum_steps > 1 needs reftr_amd.optim.FusedAdamW / FusedSGD (the gradient buffer is assigned, not "
+                                  "added to, by each backward: a foreign optimizer cannot accumulate it)")
+    optimizer.check_accumulation()
+
+
+def _window_last(optimizer, accum_steps, window_end):
+    """Whether the micro-batch about to run closes its accumulation window: the caller says so (`window_end`, e.g. the last batch
+    of an epoch), or it is the accum_steps-th one since the last update."""
+    if window_end is not None:
+        return bool(window_end)
+    return optimizer.accum_count + 1 >= accum_steps
+
+
+def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, accum_steps=1, window_end=None):
     """The loop body, engine_vg.py:40-72.  Returns (loss_value, reduced scaled dict, reduced unscaled dict,
-    grad_norm tensor)."""
+    grad_norm tensor).
+
+    accum_steps = k > 1 (gradient accumulation: the published 8 x 8 global batch on one GPU): the call is ONE micro-batch of a
+    window of k.  Micro-batches 1 ... k-1 run forward, criterion, the fast zero_grad, backward and optimizer.accumulate(); they
+    neither clip, update nor step the scheduler, and return None as their gradient norm.  The k-th (or any call with
+    window_end=True: a window cut short by the end of the epoch holds r < k micro-batches) averages the window's gradients
+    (optimizer.finish_accumulation(), s = 1 / r), then clips, updates and steps the scheduler ONCE and returns the norm of the
+    averaged gradient.  The non-finite-loss stop and the cooperative decoder's re-run act on every micro-batch."""
+    accum_steps = int(accum_steps)
+    if accum_steps > 1:
+        _require_accumulation(optimizer)
     if hasattr(optimizer, "veto") and hasattr(_inner(model), "coop_failure_word"):
         optimizer.veto = _inner(model).coop_failure_word()
     outputs = model(samples)
@@ -185,6 +211,11 @@ def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None,
         loss_value = sum(scaled.values()).item()
         _zero_grad(optimizer)
         losses.backward()
+    if accum_steps > 1:
+        if not _window_last(optimizer, accum_steps, window_end):
+            optimizer.accumulate()
+            return loss_value, scaled, unscaled, None
+        optimizer.finish_accumulation()
     if hasattr(optimizer, "clip_grad_norm_"):
         grad_total_norm = optimizer.clip_grad_norm_(max_norm)
     elif max_norm > 0:
@@ -273,10 +304,16 @@ class CapturedTrainStep:
     between (`model(...)` outside the replay, `state_dict()`, `optimizer.step()`) first gets the pending update applied
     (`flush()`).  The learning rates are device words (`optimizer.lr_dev`): the update of iteration i uses the rates that
     were current when iteration i ran, and schedule changes need no re-capture.
+
+    `accumulate=True` (gradient accumulation, begin_train_step(accum_steps > 1)): the graph is forward + loss + backward ONLY -- no
+    optimizer node of any kind, so no update can run between the micro-batches of a window.  The caller launches
+    optimizer.accumulate(), or finish_accumulation() + clip + update, eagerly between replays.
     """
 
-    def __init__(self, model, criterion, optimizer, max_norm, samples, targets, warmup=2, force_two_phase=False, force_phases=None):
+    def __init__(self, model, criterion, optimizer, max_norm, samples, targets, warmup=2, force_two_phase=False, force_phases=None,
+                 accumulate=False):
         self.model, self.criterion, self.optimizer, self.max_norm = model, criterion, optimizer, max_norm
+        self.accumulate = bool(accumulate)
         self.inner = getattr(model, "module", model)
         self.ddp = model if model is not self.inner else None
         self.s, self.t = _clone_batch(samples, targets)
@@ -309,6 +346,7 @@ class CapturedTrainStep:
         self.two_phase = bool(self.phases)
         inner._stops = frozenset(self.phases)
         can_defer = hasattr(optimizer, "enable_deferred") and os.environ.get("REFTR_DEFER_OPT", "1") == "1"
+        can_defer = can_defer and not self.accumulate
         self.deferred = can_defer and not self.two_phase and not self._post
         # data parallel (round 3): the same deferred schedule across the segment graphs -- the AdamW pass of iteration i sits at
         # the head of iteration i+1's FIRST graph (its BERT slice on the language stream under the ResNet forward, reading the
@@ -320,12 +358,17 @@ class CapturedTrainStep:
         if self.deferred:
             self._init_deferred(warmup)
             return
-        if hasattr(optimizer, "enable_device_lr"):
+        if hasattr(optimizer, "enable_device_lr") and not self.accumulate:
             optimizer.enable_device_lr()
         if self.deferred_dp:
             self._deferred_hooks()
         head = self._head_deferred if self.deferred_dp else self._fwd_bwd
         tail = self._tail_deferred if self.deferred_dp else self._opt
+        if self.accumulate:
+            assert not self.phases and not self._post, "accumulation is a single-process schedule"
+            head = self._fwd_bwd_stats               # the stats vector is packed inside the graph, as _opt / _tail_deferred do
+            tail = lambda: None                      # noqa: E731  (the optimizer's launches stay outside the graph)
+            self.grad_norm = None                    # (the window's norm is the eager clip's: _AccumInFlight)
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -349,9 +392,11 @@ class CapturedTrainStep:
                 self.g_seg.append(g)
             assert inner._bwd_gen is None, "backward did not run to its end during capture"
             self.g_bb = self.g_seg[-1] if self.g_seg else None
-            self.g_opt = torch.cuda.CUDAGraph()
-            with _capture(self.g_opt, pool=self.g_fb.pool()):
-                tail()
+            self.g_opt = None
+            if not self.accumulate:
+                self.g_opt = torch.cuda.CUDAGraph()
+                with _capture(self.g_opt, pool=self.g_fb.pool()):
+                    tail()
             if self.deferred_dp:
                 self.grad_norm = optimizer.grad_norm
                 self._pending = True                   # the last warm-up iteration's update
@@ -538,6 +583,12 @@ class CapturedTrainStep:
         self._last = (losses.detach(), {k: v.detach() for k, v in loss_dict.items()})
         return self._last
 
+    def _fwd_bwd_stats(self):
+        """The whole graph of an accumulating capture: forward + loss + backward, then the losses packed for the host."""
+        out = self._fwd_bwd()
+        self._pack_stats()
+        return out
+
     def _stats_spec(self):
         """The stats vector as rt_finish_stats writes it (deferred single-process schedule): (loss scalars sorted by name, whether the
         failure word rides along, the static output vector) -- or None when a loss is not an fp32 device scalar (then _pack_stats)."""
@@ -564,8 +615,10 @@ class CapturedTrainStep:
         ld = self._last[1]
         self.stat_names = tuple(sorted(ld))
         # layout: [losses (sorted by name) | cooperative-launch failure word (when the model can raise one) | gradient norm]
+        # (an accumulating capture has no norm of its own: its graph ends with the backward)
         fw = [self.fail_word.reshape(()).float()] if self.fail_word is not None else []
-        self.stats = torch.stack([ld[k].reshape(()).float() for k in self.stat_names] + fw + [self.grad_norm.reshape(()).float()])
+        gn = [self.grad_norm.reshape(()).float()] if self.grad_norm is not None else []
+        self.stats = torch.stack([ld[k].reshape(()).float() for k in self.stat_names] + fw + gn)
 
     def queue_stats(self, stats=None):
         """Enqueues the device -> host copy of this iteration's stats vector behind the replay, into one of TWO pinned buffers used
@@ -622,6 +675,15 @@ class CapturedTrainStep:
             self.inner.refresh_now()          # snapshot): the graph no longer carries an operand refresh of its own
         if hasattr(self.optimizer, "check_sparse_state"):
             self.optimizer.check_sparse_state()      # moments restored from outside: the sparse-state bytes go back to 'unknown'
+        if self.accumulate:
+            self._stage_in(samples, targets)
+            self.g_fb.replay()                # forward + loss + backward; what happens to the gradients is the caller's next launch
+            # the replayed backward cleared and refilled the clip-norm accumulator like an eager one (zero_for_backward): say so on the
+            # host, where that bookkeeping only ran at capture time
+            st = self.inner.store
+            st.norm_valid = bool(getattr(st, "fused_norm", False))
+            self.inner._norm_split = None
+            return self.out[0], self.out[1], None
         if self.deferred:
             self._stage_in(samples, targets)
             self.g_fb.replay()                # applies iteration i-1's update with the rates synced at iteration i-1
@@ -706,6 +768,36 @@ class _EagerResult:
         return self.res
 
 
+def _read_stats(cap, criterion, slot, retry):
+    """The host read-out of a replayed iteration, shared by every in-flight handle: waits for the stats copy and returns
+    (host vector, (loss_value, scaled dict, unscaled dict)).  A raised cooperative-decoder failure word re-runs the iteration
+    instead -- (None, what `retry` returned) -- and a non-finite loss stops the run (engine_vg.py:55-58)."""
+    host_buf, event = slot
+    event.synchronize()
+    host = host_buf.tolist()
+    k = len(cap.stat_names)
+    if cap.fail_word is not None and host[k] != 0:
+        # A stage hand-off of the cooperative decoder launches timed out in this iteration (under data parallelism: on any
+        # rank -- the word was summed with the losses).  Its AdamW update was never armed (optimizer.finish_step's device-side
+        # veto; an accumulating micro-batch has not reached the accumulator yet), so no parameter has changed; the launches are
+        # switched off, the captures dropped, and the SAME batch is run again on the launched chain with the dropout seeds and
+        # learning rates it had.
+        if retry is None:
+            _coop_fallback(cap.model)
+            raise RuntimeError("rt_decoder_fwd: a stage hand-off timed out and the iteration cannot be re-run from here "
+                               "(replayed without begin_train_step); the launches are now off (REFTR_DEC_COOP=0)")
+        return None, retry()
+    weight_dict = criterion.weight_dict
+    unscaled = {f"{n}_unscaled": v for n, v in zip(cap.stat_names, host)}
+    scaled = {n: v * weight_dict[n] for n, v in zip(cap.stat_names, host) if n in weight_dict}
+    loss_value = sum(scaled.values())
+    if not math.isfinite(loss_value):
+        print("Loss is {}, stopping training".format(loss_value))
+        print(unscaled)
+        sys.exit(1)
+    return host, (loss_value, scaled, unscaled)
+
+
 class _ReplayInFlight:
     """A replayed step between its launch and its host read-out (`finish`)."""
 
@@ -714,33 +806,87 @@ class _ReplayInFlight:
         self.slot = slot if slot is not None else (cap._stats_host[0], cap._stats_event[0])
 
     def finish(self):
-        cap = self.cap
-        host_buf, event = self.slot
-        event.synchronize()
-        host = host_buf.tolist()
-        k = len(cap.stat_names)
-        if cap.fail_word is not None and host[k] != 0:
-            # A stage hand-off of the cooperative decoder launches timed out in this iteration (under data parallelism: on any
-            # rank -- the word was summed with the losses).  Its AdamW update was never armed (optimizer.finish_step's device-side
-            # veto), so no parameter has changed; the launches are switched off, the captures dropped, and the SAME batch is run
-            # again on the launched chain with the dropout seeds and learning rates it had.
-            if self.retry is None:
-                _coop_fallback(cap.model)
-                raise RuntimeError("rt_decoder_fwd: a stage hand-off timed out and the iteration cannot be re-run from here "
-                                   "(replayed without begin_train_step); the launches are now off (REFTR_DEC_COOP=0)")
-            return self.retry()
-        weight_dict = self.criterion.weight_dict
-        unscaled = {f"{n}_unscaled": v for n, v in zip(cap.stat_names, host)}
-        scaled = {n: v * weight_dict[n] for n, v in zip(cap.stat_names, host) if n in weight_dict}
-        loss_value = sum(scaled.values())
-        if not math.isfinite(loss_value):
-            print("Loss is {}, stopping training".format(loss_value))
-            print(unscaled)
-            sys.exit(1)
-        return loss_value, scaled, unscaled, host[-1]
+        host, res = _read_stats(self.cap, self.criterion, self.slot, self.retry)
+        if host is None:
+            return res
+        return (*res, host[-1])
 
 
-def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None):
+class _AccumInFlight:
+    """A replayed micro-batch of an accumulation window between its launch and its read-out.  `finish` reads the micro-batch's
+    losses first -- the non-finite stop and the cooperative decoder's re-run come BEFORE its gradients go anywhere, as in the eager
+    loop body -- and then launches what follows the backward: accumulate(), or the window's average + clip + update."""
+
+    def __init__(self, cap, criterion, optimizer, lr_scheduler, max_norm, last, retry, slot):
+        self.cap, self.criterion, self.optimizer, self.lr_scheduler, self.max_norm = cap, criterion, optimizer, lr_scheduler, max_norm
+        self.last, self.retry, self.slot = last, retry, slot
+
+    def finish(self):
+        opt = self.optimizer
+        host, res = _read_stats(self.cap, self.criterion, self.slot, self.retry)
+        if host is None:
+            return res
+        if not self.last:
+            opt.accumulate()
+            return (*res, None)
+        opt.finish_accumulation()
+        if getattr(opt, "lr_dev", None) is not None:
+            opt.sync_lr()                    # another capture of this optimizer switched the kernel to device learning rates
+        gnorm = opt.clip_grad_norm_(self.max_norm)
+        opt.step()
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+        return (*res, gnorm)
+
+
+def _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead, accum_steps,
+                      window_end):
+    """begin_train_step for accum_steps > 1: forward + loss + backward replayed from one hipGraph per input shape
+    (CapturedTrainStep(accumulate=True)); accumulate / average + clip + update launched eagerly behind it (_AccumInFlight)."""
+    _require_accumulation(optimizer)
+    inner = _inner(model)
+    caps = inner.__dict__.setdefault("_captured_steps", {})
+    dist_on = utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1
+    img = samples.get("img")
+    ok = (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and not dist_on and model is inner
+          and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1")
+    key = None
+    if ok:
+        key = (CapturedTrainStep.shape_key(samples, targets), id(criterion), id(optimizer), "accumulate", model.training)
+        ok = key in caps or len(caps) < max_shapes
+    for k_, other in caps.items():                # a pending (deferred) update of a plain capture lands before anything else runs
+        if k_ != key:
+            other.flush()
+    inner.__dict__["_staged_cap"] = None
+    if not ok:
+        return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end))
+    cap = caps.get(key)
+    if cap is None:
+        # the capture's warm-up iterations are forward + backward only: no weight or optimizer state moves, but the dropout seed does
+        snap = (inner.seed_dev.clone(), inner._step)
+        cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, accumulate=True)
+        cap.training = model.training
+        inner.seed_dev.copy_(snap[0]); inner._step = snap[1]
+    last = _window_last(optimizer, accum_steps, window_end)
+    seed_back = (1 if model.training else 0, 1)
+    cap(samples, targets)
+    slot = cap.queue_stats()
+    if lookahead is not None:
+        nxt = lookahead()
+        if nxt is not None and nxt[0] is not None:
+            cap.stage(*nxt)
+
+    def _retry():
+        # nothing of the failed micro-batch has reached the accumulator, the weights or the scheduler: the same call, eagerly wired
+        _coop_fallback(model)
+        _restore_seed(model, seed_back)
+        return _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, None,
+                                 accum_steps, last).finish()
+    return _AccumInFlight(cap, criterion, optimizer, lr_scheduler, max_norm, last, _retry, slot)
+
+
+def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None,
+                     accum_steps=1, window_end=None):
     """Launches one iteration of the loop body and returns a handle; `handle.finish()` waits for it and returns what
     `train_step` returns.  Between the two the caller may do host work (the epoch loop books the previous iteration's meters).
 
@@ -751,7 +897,15 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
 
     Everything the host does between an iteration's read-out and the next launch is device idle time, so the steady state is
     short: a batch that the previous iteration already staged is recognised by identity (no shape key, no lookups), the
-    scheduler step and the stats copy are issued right behind the launch."""
+    scheduler step and the stats copy are issued right behind the launch.
+
+    accum_steps > 1 (see train_step): one micro-batch of an accumulation window.  The replayed graph is forward + loss + backward
+    alone; `finish` reads the losses and then launches accumulate() -- or, for the window's last micro-batch, the average, the clip,
+    the update and the scheduler step -- eagerly, so the update of a window is applied at its end and never between two of its
+    micro-batches."""
+    if int(accum_steps) > 1:
+        return _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead,
+                                 int(accum_steps), window_end)
     inner = getattr(model, "module", model)
     caps = inner.__dict__.setdefault("_captured_steps", {})
     dist_on = utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1
@@ -859,9 +1013,11 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
     return _ReplayInFlight(cap, criterion, retry=_retry, slot=slot)
 
 
-def captured_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None):
+def captured_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None,
+                        accum_steps=1, window_end=None):
     """`train_step` with the same return value, on `begin_train_step` (launch) + `finish` (read-out)."""
-    return begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead).finish()
+    return begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead,
+                            accum_steps, window_end).finish()
 
 
 def _check_cooperative(model):
@@ -873,7 +1029,17 @@ def _check_cooperative(model):
         raise RuntimeError("rt_decoder_fwd: a stage hand-off timed out (workgroups not co-resident?) -- set REFTR_DEC_COOP=0")
 
 
-def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, device, epoch, max_norm=0):
+def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, device, epoch, max_norm=0, accum_steps=1):
+    """engine_vg.py:22-79.  accum_steps = k > 1: every k batches of the loader form one accumulation window -- one clip, one update
+    and one lr_scheduler.step() per window, on the mean of its gradients (see train_step).  The last window of an epoch may be cut
+    short: it is finished with the r < k batches it has (s = 1 / r); no batch is dropped and nothing is carried into the next epoch.
+    The stats board receives one row per micro-batch (its loss terms and the learning rate); `grad_norm` -- the norm of the window's
+    averaged gradient -- is booked once per window, on the row of its last micro-batch."""
+    accum_steps = int(accum_steps)
+    if accum_steps > 1:
+        _require_accumulation(optimizer)
+        optimizer.accum_count = 0                 # a window never spans two epochs
+    n_batches = len(data_loader)
     model.train()
     criterion.train()
     board = utils.StatBoard()
@@ -891,13 +1057,21 @@ def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, devi
         loss_value, scaled, unscaled, gnorm = step.finish()
         if torch.is_tensor(gnorm):               # the eager step hands back the optimizer's device scalar, which the next step overwrites
             gnorm = float(gnorm)
-        return dict(loss=loss_value, **scaled, **unscaled, lr=step.lr_logged, grad_norm=gnorm)
+        # what the reference's meter shows: the rate after this iteration's scheduler step (a window's last micro-batch steps it in finish)
+        row = dict(loss=loss_value, **scaled, **unscaled, lr=optimizer.param_groups[0]["lr"] if accum_steps > 1 else step.lr_logged)
+        if gnorm is not None:                    # (a micro-batch inside an accumulation window has none)
+            row["grad_norm"] = gnorm
+        return row
 
-    for _ in board.log_every(range(len(data_loader)), 50, header):
+    for it in board.log_every(range(n_batches), 50, header):
         # the loop body of engine_vg.py:40-72 -- replayed from hipGraphs for fixed-shape data (RefCOCO: 640 x 640, L = 40);
         # the replayed path hands back host numbers (one stacked copy per iteration), the eager one device scalars.
         ahead = Lookahead(prefetcher.next)
-        step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead)
+        if accum_steps > 1:
+            step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead,
+                                    accum_steps=accum_steps, window_end=(it + 1) % accum_steps == 0 or it + 1 == n_batches)
+        else:
+            step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead)
         step.lr_logged = optimizer.param_groups[0]["lr"]      # what the reference's meter shows: the rate after this iteration's scheduler step
         if booked is not None:
             board.add(**booked)

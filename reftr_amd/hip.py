@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2, 3
 _c_float_p = POINTER(c_float)
@@ -344,6 +344,7 @@ _SIGNATURES = {
     "rt_round_chunks": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "rt_adamw_flat": (c_int, [POINTER(AdamWDesc), c_void_p]),
     "rt_sgd_flat": (c_int, [POINTER(AdamWDesc), c_void_p]),
+    "rt_grad_accum": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_zero_chunks": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "rt_counter_add": (c_int, [c_void_p, c_int32, c_void_p]),
     "rt_ln_param_grad_grouped": (c_int, [POINTER(LnPgJob), c_int, c_void_p]),
@@ -1214,6 +1215,22 @@ def sqnorm(g, out):
         _check(lib().rt_sqnorm_bf16(_p(g), g.numel(), _p(out), _stream()), "rt_sqnorm_bf16")
     else:
         _check(lib().rt_sqnorm(_p(g), g.numel(), _p(out), _stream()), "rt_sqnorm")
+
+
+ACCUM_FIRST, ACCUM_ADD, ACCUM_FINISH = 0, 1, 2
+GRAD_ACCUM_SLOTS = 2048
+
+
+def grad_accum(mode, g, acc, scale=1.0, scale_dev=None, partials=None, out_sq=None):
+    """rt_grad_accum over the fp32 buffers g / acc (same element count): ACCUM_FIRST acc = g, ACCUM_ADD acc += g, ACCUM_FINISH
+    g = (acc + g) * scale with out_sq[0] = sum g^2 (`partials`: GRAD_ACCUM_SLOTS floats of workspace; `scale_dev`: a device float
+    read instead of `scale`)."""
+    _req(g, torch.float32, "g"); _req(acc, torch.float32, "acc")
+    _req(scale_dev, torch.float32, "scale_dev"); _req(partials, torch.float32, "partials"); _req(out_sq, torch.float32, "out_sq")
+    assert g.is_contiguous() and acc.is_contiguous() and g.numel() == acc.numel()
+    assert partials is None or partials.numel() >= GRAD_ACCUM_SLOTS
+    _check(lib().rt_grad_accum(int(mode), _p(g), _p(acc), g.numel(), float(scale), _p(scale_dev), _p(partials), _p(out_sq), _stream()),
+           "rt_grad_accum")
 
 
 def adamw_flat(p, g, m, v, *, step, ranges, gnorm_sq=None, gnorm_out=None, grad_scale=1.0, max_norm=0.0,

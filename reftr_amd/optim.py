@@ -81,6 +81,12 @@ class FusedAdamW(torch.optim.Optimizer):
         self._mv_version = None
         # device word that vetoes an iteration's update (the cooperative decoder's failure word): see finish_step / step
         self.veto = None
+        # gradient accumulation (accumulate / finish_accumulation): a second flat buffer, allocated by the first accumulate() only --
+        # a run that never accumulates does not pay for it; `accum_count` = micro-batches added since the window opened
+        self.accum = None
+        self.accum_count = 0
+        self._accum_ws = None
+        self._window_sq = False       # self.sq holds the squared norm of the window's averaged gradient (finish_accumulation)
 
     def zero_grad(self, set_to_none=False, fast=False):
         """One memset of the flat gradient buffer (param.grad views are kept).  fast=True (the training loops of
@@ -88,6 +94,9 @@ class FusedAdamW(torch.optim.Optimizer):
         matrices -- 96 % of the 607 MB -- are overwritten by their first weight-gradient launch (ParamStore.arm_overwrite);
         REFTR_OVERWRITE=0 keeps the full clear."""
         self.model.store.zero_for_backward(fast)
+        # a finish_accumulation() that no clip / step consumed: its norm is not the norm of what the next backward writes (and a
+        # capture started in that state would leave its own norm launch out of the graph for good)
+        self._window_sq = False
 
     def _grad_buffer(self):
         """The buffer the update reads: the fp32 gradients, or -- in a data-parallel run that exchanges bf16 -- the bf16 copy
@@ -95,9 +104,65 @@ class FusedAdamW(torch.optim.Optimizer):
         g16 = getattr(self.model.store, "flat_g16", None)
         return g16 if g16 is not None else self.model.store.flat_g
 
+    # ---- gradient accumulation: [backward, accumulate()] x (k - 1), backward, finish_accumulation(), then clip + step as usual ----
+    def check_accumulation(self):
+        """Accumulation averages the fp32 gradient buffer of ONE process: refused under the data-parallel schedules."""
+        if getattr(self.model, "dp_mode", False) or getattr(self.model.store, "flat_g16", None) is not None:
+            raise NotImplementedError("gradient accumulation is not implemented under the data-parallel wrapper or the bf16 gradient "
+                                      "exchange (accum_steps > 1 needs a single-process fp32 gradient buffer)")
+
+    def _drop_backward_norm(self):
+        # what the weight-gradient epilogues (and the language stream) collected is the norm of the LAST micro-batch only
+        self.model.store.norm_valid = False
+        self.model._norm_split = None
+
+    @torch.no_grad()
+    def accumulate(self):
+        """After the backward of a micro-batch that is not the window's last, INSTEAD of clip_grad_norm_ / step: the gradient
+        buffer goes into the accumulator (assigned by the window's first micro-batch, added by the others: rt_grad_accum).  No
+        clip, no update, no step counter.  Returns the number of micro-batches the window holds now."""
+        self.check_accumulation()
+        st = self.model.store
+        if self.accum is None:
+            self.accum = torch.empty_like(st.flat_g)
+        H.grad_accum(H.ACCUM_FIRST if self.accum_count == 0 else H.ACCUM_ADD, st.flat_g, self.accum)
+        self.accum_count += 1
+        self._drop_backward_norm()
+        return self.accum_count
+
+    @torch.no_grad()
+    def finish_accumulation(self):
+        """After the backward of the window's last micro-batch: the gradient buffer becomes the MEAN over the window's r micro-batches
+        (what DDP over r ranks leaves there, main_vg.py:290-296) and self.sq its squared norm, from the same pass -- the
+        clip_grad_norm_ / step (or finish_step) that follows does not read the buffer again.  Returns s = 1 / r.  A window of one
+        micro-batch (nothing accumulated) is left to the plain step, untouched."""
+        r = self.accum_count + 1
+        if r == 1:
+            return 1.0
+        self.check_accumulation()
+        st = self.model.store
+        if self._accum_ws is None:
+            self._accum_ws = torch.empty(H.GRAD_ACCUM_SLOTS, dtype=torch.float32, device=st.device)
+        H.grad_accum(H.ACCUM_FINISH, st.flat_g, self.accum, scale=1.0 / r, partials=self._accum_ws, out_sq=self.sq)
+        self.accum_count = 0
+        self._window_sq = True
+        self._drop_backward_norm()
+        return 1.0 / r
+
+    def _take_window_sq(self):
+        had, self._window_sq = self._window_sq, False
+        return had
+
+    def _refuse_mid_window(self, what):
+        if self.accum_count:
+            raise RuntimeError(f"{what} inside an accumulation window ({self.accum_count} micro-batch(es) accumulated, no update yet): "
+                               "checkpoints are taken between windows")
+
     def _sqnorm_all(self):
         """Squared norm of the whole gradient buffer into self.sq.  When the backward already reduced the BERT slice on the
         language stream (model._norm_split, single-process fp32 gradients only), only the rest is read here."""
+        if self._take_window_sq():        # finish_accumulation left it there
+            return
         g = self._grad_buffer()
         split = getattr(self.model, "_norm_split", None)
         st = self.model.store
@@ -202,7 +267,7 @@ class FusedAdamW(torch.optim.Optimizer):
         st = self.model.store
         self.step_count += 1
         H.counter_add(self.step_dev, 1, unless=self.veto)      # a vetoed iteration does not advance the device counter either
-        if not self._have_sq:
+        if not self._have_sq and not self._take_window_sq():
             H.sqnorm(self._grad_buffer(), self.sq)
         act, self.active = self.active, None          # an immediate step is never conditional ...
         if self.veto is not None:                     # ... except on the cooperative decoder's failure word (see finish_step)
@@ -305,6 +370,7 @@ class FusedAdamW(torch.optim.Optimizer):
         """torch.optim.AdamW's format (what the reference writes into checkpoint['optimizer'], main_vg.py:377-384):
         per-parameter `step`, `exp_avg`, `exp_avg_sq` keyed by the parameter's index in the reference's group order, so a
         checkpoint written here resumes under the reference and vice versa."""
+        self._refuse_mid_window("state_dict()")
         if self._flush_pending is not None:
             self._flush_pending()
         st = self.model.store
@@ -362,6 +428,7 @@ class FusedSGD(FusedAdamW):
 
     def state_dict(self):
         """torch.optim.SGD's format: per-parameter `momentum_buffer` keyed by the parameter's index in the reference's group order."""
+        self._refuse_mid_window("state_dict()")
         if self._flush_pending is not None:
             self._flush_pending()
         st = self.model.store
@@ -396,9 +463,17 @@ class FusedSGD(FusedAdamW):
 
 
 def build_optimizer(model, args):
-    """The optimizer main_vg.py:234-268 builds, on the fused kernels: AdamW, or SGD(momentum 0.9) with --sgd."""
+    """The optimizer main_vg.py:234-268 builds, on the fused kernels: AdamW, or SGD(momentum 0.9) with --sgd.  `args.accum_steps`
+    (the one flag the reference does not have; default 1) is kept on the optimizer as `accum_steps` for the loop:
+    train_one_epoch(..., accum_steps=optimizer.accum_steps)."""
+    accum_steps = int(getattr(args, "accum_steps", 1))
+    if accum_steps < 1:
+        raise ValueError(f"accum_steps must be >= 1 (got {accum_steps})")
     if getattr(args, "sgd", False):
-        return FusedSGD(model, lr=args.lr, lr_backbone=args.lr_backbone, weight_decay=args.weight_decay,
-                        lr_mask_branch_proj=getattr(args, "lr_mask_branch_proj", 1.0))
-    return FusedAdamW(model, lr=args.lr, lr_backbone=args.lr_backbone, weight_decay=args.weight_decay,
-                      lr_mask_branch_proj=getattr(args, "lr_mask_branch_proj", 1.0))
+        opt = FusedSGD(model, lr=args.lr, lr_backbone=args.lr_backbone, weight_decay=args.weight_decay,
+                       lr_mask_branch_proj=getattr(args, "lr_mask_branch_proj", 1.0))
+    else:
+        opt = FusedAdamW(model, lr=args.lr, lr_backbone=args.lr_backbone, weight_decay=args.weight_decay,
+                         lr_mask_branch_proj=getattr(args, "lr_mask_branch_proj", 1.0))
+    opt.accum_steps = accum_steps
+    return opt
