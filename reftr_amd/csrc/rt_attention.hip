@@ -157,17 +157,6 @@ template <int DH> struct Lds {
     }
 };
 
-// dropout of one attention site: element `idx` is kept (and scaled by ks) iff keep(idx)
-struct Drop {
-    bool on;
-    uint32_t thresh;
-    float ks;
-    uint32_t seed;
-    __device__ __forceinline__ Drop(float drop_p, const uint32_t* seed_dev, uint32_t drop_seed)
-        : on(drop_p > 0.f), thresh(rt_drop_thresh(drop_p)), ks(on ? 1.f / (1.f - drop_p) : 1.f), seed(rt_site_seed(seed_dev, drop_seed)) {}
-    __device__ __forceinline__ bool keep(uint32_t idx) const { return rt_hash32(seed, idx) >= thresh; }
-};
-
 // sum / max over the 4 lane groups that share a query (or key) column
 __device__ __forceinline__ float group_sum(float v) {
     v += __shfl_xor(v, 16, 64);
@@ -278,7 +267,7 @@ __device__ __forceinline__ void fwd_stats_chunk(const Lds<DH>& s, int rows, cons
 // pass 2 over `rows` staged keys: normalised probabilities -> P^T fragments -> O^T += V^T P^T
 template <int DH>
 __device__ __forceinline__ void fwd_pv_chunk(const Lds<DH>& s, int rows, int c0, const Lanes& t, const bf16x8 (&qf)[Geo<DH>::KH], float scale,
-                                             float Ms, float inv_l, const Drop& drop, uint32_t drop_row, f32x4 (&o)[Geo<DH>::DT]) {
+                                             float Ms, float inv_l, const rt_drop& drop, uint32_t drop_row, f32x4 (&o)[Geo<DH>::DT]) {
     constexpr int RS = Geo<DH>::RS;
     for (int c = 0; c < (rows >> 5); ++c) {
         float pv[8];
@@ -344,7 +333,7 @@ __device__ __forceinline__ void attn_fwd_body(const rt_attn_desc& p, const int c
     float M, Ms, inv_l;
     softmax_finish(m, l, M, Ms, inv_l);
 
-    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const rt_drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     const uint32_t drop_row = (uint32_t)(((size_t)t.bh * p.Sq + q) * p.Sk);
     f32x4 o[Geo<DH>::DT];
     zero_acc<DH>(o);
@@ -417,7 +406,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_des
     l = group_sum(l);
     const float inv_l = 1.f / l;                 // fully masked row: 0 * inf = NaN below, as the reference
 
-    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const rt_drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     const uint32_t drop_row = (uint32_t)(((size_t)bh * p.Sq + q) * p.Sk);
     f32x4 o[DT];
     zero_acc<DH>(o);
@@ -462,7 +451,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_reg_kernel(const rt_attn_des
 // `rows` staged keys: dS^T from the recomputed probabilities, dQ^T += K^T dS^T
 template <int DH>
 __device__ __forceinline__ void dq_chunk(const Lds<DH>& s, int rows, int c0, const Lanes& t, const bf16x8 (&qf)[Geo<DH>::KH],
-                                         const bf16x8 (&dof)[Geo<DH>::KH], float lse, float delta, float scale, const Drop& drop,
+                                         const bf16x8 (&dof)[Geo<DH>::KH], float lse, float delta, float scale, const rt_drop& drop,
                                          uint32_t drop_row, f32x4 (&dq)[Geo<DH>::DT]) {
     constexpr int RS = Geo<DH>::RS;
     for (int c = 0; c < (rows >> 5); ++c) {
@@ -517,7 +506,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const rt_attn_bwd_desc& p, cons
     const float lse = (q < p.Sq) ? p.lse[(size_t)t.bh * p.Sq + q] : INFINITY;
     if (t.lg == 0 && q < p.Sq) p.delta[(size_t)t.bh * p.Sq + q] = delta;
 
-    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const rt_drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     const uint32_t drop_row = (uint32_t)(((size_t)t.bh * p.Sq + q) * p.Sk);
     f32x4 dq[Geo<DH>::DT];
     zero_acc<DH>(dq);
@@ -539,7 +528,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const rt_attn_bwd_desc& p, cons
 // `rows` staged queries: P and dS of [query 4g+r][key li], dV^T += dO^T P, dK^T += Q^T dS
 template <int DH>
 __device__ __forceinline__ void dkv_chunk(const Lds<DH>& s, int rows, int c0, const Lanes& t, const bf16x8 (&kf)[Geo<DH>::KH],
-                                          const bf16x8 (&vf)[Geo<DH>::KH], float kbias, float scale, const Drop& drop, int Sq, int Sk, int key,
+                                          const bf16x8 (&vf)[Geo<DH>::KH], float kbias, float scale, const rt_drop& drop, int Sq, int Sk, int key,
                                           f32x4 (&dk)[Geo<DH>::DT], f32x4 (&dv)[Geo<DH>::DT]) {
     constexpr int RS = Geo<DH>::RS;
     for (int c = 0; c < (rows >> 5); ++c) {
@@ -594,7 +583,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const rt_attn_bwd_desc& p, con
     load_bfrag<DH>(head_rows<DH>(p.v, t, p.Sk, p.ldv), key, p.Sk, p.ldv, t.lg, vf);
     const float kbias = (key < p.Sk && !(p.kpm && p.kpm[(size_t)t.b * p.Sk + key])) ? 0.f : -INFINITY;
 
-    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const rt_drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     f32x4 dk[Geo<DH>::DT], dv[Geo<DH>::DT];
     zero_acc<DH>(dk);
     zero_acc<DH>(dv);
@@ -769,7 +758,7 @@ __global__ __launch_bounds__(256) void attn_q1_fwd_kernel(const rt_attn_desc p) 
     l = red[4] + red[5] + red[6] + red[7];
     const float inv_l = 1.f / l;                 // fully masked row: NaN below, as the reference
     if (t == 0 && p.lse) p.lse[bh] = ms + __logf(l);
-    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const rt_drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     float o[32];
 #pragma unroll
     for (int d = 0; d < 32; ++d) o[d] = 0.f;
@@ -816,7 +805,7 @@ __global__ __launch_bounds__(256) void attn_q1_bwd_kernel(const rt_attn_bwd_desc
 #pragma unroll
     for (int d = 0; d < 32; ++d) delta += go[d] * ov[d];
     const float lse = p.lse[bh];
-    const Drop drop(p.drop_p, p.seed_dev, p.drop_seed);
+    const rt_drop drop(p.drop_p, p.seed_dev, p.drop_seed);
     float dq[32];
 #pragma unroll
     for (int d = 0; d < 32; ++d) dq[d] = 0.f;

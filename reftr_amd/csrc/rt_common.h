@@ -47,6 +47,30 @@ __device__ __forceinline__ uint32_t rt_site_seed(const uint32_t* seed_dev, uint3
 __device__ __forceinline__ uint32_t rt_drop_thresh(float p) {
     return (uint32_t)((double)p * 4294967296.0);
 }
+// dropout of one site: element `idx` is kept (and scaled by ks) iff keep(idx)
+struct rt_drop {
+    bool on;
+    uint32_t thresh;
+    float ks;
+    uint32_t seed;
+    __device__ __forceinline__ rt_drop(float drop_p, const uint32_t* seed_dev, uint32_t drop_seed)
+        : on(drop_p > 0.f), thresh(rt_drop_thresh(drop_p)), ks(on ? 1.f / (1.f - drop_p) : 1.f), seed(rt_site_seed(seed_dev, drop_seed)) {}
+    // `seed`: the site's effective seed, already resolved by the caller
+    __device__ __forceinline__ rt_drop(float drop_p, uint32_t seed)
+        : on(drop_p > 0.f), thresh(rt_drop_thresh(drop_p)), ks(on ? 1.f / (1.f - drop_p) : 1.f), seed(seed) {}
+    // a site whose kernel does not touch *seed_dev while dropout is off
+    static __device__ __forceinline__ rt_drop site(float drop_p, const uint32_t* seed_dev, uint32_t drop_seed) {
+        return rt_drop(drop_p, drop_p > 0.f ? rt_site_seed(seed_dev, drop_seed) : 0u);
+    }
+    __device__ __forceinline__ bool keep(uint32_t idx) const { return rt_hash32(seed, idx) >= thresh; }
+    // v behind the mask (unchanged while dropout is off); the four elements' indices are (idx0 + e) >> shift
+    __device__ __forceinline__ float apply(float v, uint32_t idx) const { return !on ? v : keep(idx) ? v * ks : 0.f; }
+    __device__ __forceinline__ f32x4 apply(f32x4 v, uint32_t idx0, int shift = 0) const {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = apply(v[e], (idx0 + e) >> shift);
+        return v;
+    }
+};
 
 __device__ __forceinline__ float rt_gelu(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

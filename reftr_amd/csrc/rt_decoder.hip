@@ -25,6 +25,7 @@
 // linear1 (F / 16 tiles) on the G - 16 "workers", which therefore hold their K / V rows and weight fragments long before the
 // rows they wait for exist.
 #include "rt_common.h"
+#include "rt_ln_row.h"
 #include <stdlib.h>
 
 namespace {
@@ -69,6 +70,48 @@ constexpr int LL_O = LL_HDR, LL_U = LL_O + 16 * 256 * 4, LL_Q2 = LL_U + 16 * 256
               LL_U2 = LL_O2 + 16 * 256 * 4, LL_U3 = LL_U2 + 16 * 256 * 8, LL_HDN = LL_U3 + 16 * 256 * 8;      // hdn: 16 * F * 4 bytes
 __device__ __forceinline__ unsigned ll_tag(unsigned epoch, int layer, int stage) { return (epoch << 8) | (unsigned)(layer * 8 + stage + 1); }
 
+// consumer side: N coherent 16-byte loads of `base` at the byte offsets off(j) (load j is left out where !pred(j)), issued together
+// and re-issued until words 1 and 3 of every one carry `tag`, `spin` times at most; a poll that gives up raises *err and the caller
+// goes on with whatever it read
+template <int N, class Off, class Pred>
+__device__ __forceinline__ void ll_poll(const unsigned char* base, unsigned tag, unsigned* err, int spin, u32x4 (&v)[N], Off off, Pred pred) {
+    u32x4 w[N];                              // polled into a local: the barrier below would keep the caller's array in memory
+    int guard = 0;
+    bool ok;
+    do {
+        asm volatile("" ::: "memory");       // the loads below must be re-issued on every pass
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (pred(j)) w[j] = dec_ld16(base, off(j));
+        ok = true;
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (pred(j)) ok = ok && w[j][1] == tag && w[j][3] == tag;
+    } while (!ok && ++guard < spin);
+    if (!ok) *err = 1u;
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = w[j];
+}
+template <int N, class Off>
+__device__ __forceinline__ void ll_poll(const unsigned char* base, unsigned tag, unsigned* err, int spin, u32x4 (&v)[N], Off off) {
+    ll_poll(base, tag, err, spin, v, off, [](int) { return true; });
+}
+// 4 consecutive fp32 features (4 units), 32 consecutive bf16 features as floats (16 units: elem is a multiple of 4)
+__device__ __forceinline__ f32x4 ll_get_f32x4(const unsigned char* ll, int region, unsigned tag, int elem, unsigned* err, int spin) {
+    u32x4 v[2];
+    ll_poll(ll + region, tag, err, spin, v, [&](int j) { return elem * 8 + j * 16; });
+    return f32x4{__uint_as_float(v[0][0]), __uint_as_float(v[0][2]), __uint_as_float(v[1][0]), __uint_as_float(v[1][2])};
+}
+__device__ __forceinline__ void ll_get_bf16x32(const unsigned char* ll, int region, unsigned tag, int elem, unsigned* err, int spin, float (&out)[32]) {
+    u32x4 raw[8];
+    ll_poll(ll + region, tag, err, spin, raw, [&](int c) { return (elem + c * 4) * 4; });
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const unsigned w0 = raw[c][0], w1 = raw[c][2];
+        const bf16x2 lo = *reinterpret_cast<const bf16x2*>(&w0), hi = *reinterpret_cast<const bf16x2*>(&w1);
+        out[c * 4 + 0] = (float)lo[0]; out[c * 4 + 1] = (float)lo[1]; out[c * 4 + 2] = (float)hi[0]; out[c * 4 + 3] = (float)hi[1];
+    }
+}
 // bf16 row block [M][K] (unit = 2 bf16 + tag) -> LDS operand rows; NL 16-byte loads per thread in flight per round trip
 template <int NL>
 __device__ __forceinline__ void ll_rows_to_lds(unsigned char* ll, int region, unsigned tag, int M, int K, bf16_t* xa, int ld,
@@ -77,23 +120,7 @@ __device__ __forceinline__ void ll_rows_to_lds(unsigned char* ll, int region, un
     const int per_row = K >> 2, pieces = M * per_row;            // 16-byte pieces: 2 units = 4 bf16
     for (int i0 = 0; i0 < pieces; i0 += 256 * NL) {
         u32x4 v[NL];
-        int guard = 0;
-        bool ok;
-        do {
-            asm volatile("" ::: "memory");       // the loads below must be re-issued on every pass
-#pragma unroll
-            for (int j = 0; j < NL; ++j) {
-                const int i = i0 + j * 256 + t;
-                if (i < pieces) v[j] = dec_ld16(ll + region, i * 16);
-            }
-            ok = true;
-#pragma unroll
-            for (int j = 0; j < NL; ++j) {
-                const int i = i0 + j * 256 + t;
-                if (i < pieces) ok = ok && v[j][1] == tag && v[j][3] == tag;
-            }
-        } while (!ok && ++guard < spin);
-        if (!ok) *err = 1u;
+        ll_poll(ll + region, tag, err, spin, v, [&](int j) { return (i0 + j * 256 + t) * 16; }, [&](int j) { return i0 + j * 256 + t < pieces; });
 #pragma unroll
         for (int j = 0; j < NL; ++j) {
             const int i = i0 + j * 256 + t;
@@ -123,7 +150,7 @@ __device__ __forceinline__ void dec_rows_to_lds(const bf16_t* src, int M, int K,
     }
 }
 
-// ---- LayerNorm of the M rows (layernorm_fwd_vec_kernel<1>'s arithmetic): fp32 result -> ln32, bf16(y [+ pos]) -> xa ----------
+// ---- LayerNorm of the M rows (rt_ln_row.h, as layernorm_fwd_vec_kernel<1>): fp32 result -> ln32, bf16(y [+ pos]) -> xa ----------
 struct DecLnOut { float* y_f32; bf16_t* y_bf16; bf16_t* ypos_bf16; float* mean; float* rstd; };
 // `ll` != nullptr: the rows come from a tagged fp32 region (4 units per lane), else from `u` (plain memory)
 __device__ __forceinline__ void dec_ln_rows(const float* u, unsigned char* ll, int region, unsigned tag, unsigned* err, int spin,
@@ -133,37 +160,14 @@ __device__ __forceinline__ void dec_ln_rows(const float* u, unsigned char* ll, i
     const int c = lane * 4;
     const f32x4 gam = *reinterpret_cast<const f32x4*>(gamma + c), bet = *reinterpret_cast<const f32x4*>(beta + c);
     for (int row = wave; row < M; row += 4) {
-        f32x4 v;
-        if (ll) {
-            u32x4 a, b;
-            int guard = 0;
-            bool ok;
-            do {
-            asm volatile("" ::: "memory");       // the loads below must be re-issued on every pass
-                a = dec_ld16(ll + region, (row * DEC_E + c) * 8);
-                b = dec_ld16(ll + region, (row * DEC_E + c) * 8 + 16);
-                ok = a[1] == tag && a[3] == tag && b[1] == tag && b[3] == tag;
-            } while (!ok && ++guard < spin);
-            if (!ok) *err = 1u;
-            v = f32x4{__uint_as_float(a[0]), __uint_as_float(a[2]), __uint_as_float(b[0]), __uint_as_float(b[2])};
-        } else {
-            v = *reinterpret_cast<const f32x4*>(u + (size_t)row * DEC_E + c);
-        }
+        const f32x4 v = ll ? ll_get_f32x4(ll, region, tag, row * DEC_E + c, err, spin) : *reinterpret_cast<const f32x4*>(u + (size_t)row * DEC_E + c);
         const f32x4 ps = pos ? *reinterpret_cast<const f32x4*>(pos + (size_t)row * DEC_E + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const float s = (v[0] + v[1]) + (v[2] + v[3]);
-        const float mean = rt_wave_sum(s) * (1.f / DEC_E);
-        float ss = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; ss += d * d; }
-        const float rstd = rsqrtf(rt_wave_sum(ss) * (1.f / DEC_E) + eps);
-        f32x4 y;
+        float mean, rstd;
+        rt_ln_stats<1>(&v, eps, mean, rstd);
+        const f32x4 y = rt_ln_affine(v, mean, rstd, gam, bet, false);
         bf16x4 yb, yp;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y[e] = (v[e] - mean) * rstd * gam[e] + bet[e];
-            yb[e] = (bf16_t)y[e];
-            yp[e] = (bf16_t)(y[e] + ps[e]);
-        }
+        for (int e = 0; e < 4; ++e) { yb[e] = (bf16_t)y[e]; yp[e] = (bf16_t)(y[e] + ps[e]); }
         *reinterpret_cast<f32x4*>(&sm.ln32[row][c]) = y;
         *reinterpret_cast<bf16x4*>(xa + row * ld + c) = pos ? yp : yb;
         if (writer) {
@@ -212,11 +216,7 @@ __device__ __forceinline__ void dec_tile(const u32x4 (&wv)[PER], const bf16_t* x
 }
 
 __device__ __forceinline__ f32x4 dec_dropout(f32x4 v, float p, uint32_t seed, uint32_t idx0, int shift) {
-    const uint32_t thresh = rt_drop_thresh(p);
-    const float ks = 1.0f / (1.0f - p);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = (rt_hash32(seed, (idx0 + r) >> shift) >= thresh) ? v[r] * ks : 0.f;
-    return v;
+    return rt_drop(p, seed).apply(v, idx0, shift);
 }
 __device__ __forceinline__ u32x2 dec_pack4(f32x4 v) {
     bf16x4 b;
@@ -253,27 +253,7 @@ __device__ __forceinline__ void dec_attn(const rt_decoder_fwd_desc& p, const rt_
     const int b = bh / p.H, h = bh - b * p.H;
     float q[32], sc[DEC_MAXK], o[32];
     float m = -INFINITY;
-    {   // the 32 query features of (b, h): 16 tagged units, the same 128 bytes for every lane
-        u32x4 raw[8];
-        int guard = 0;
-        bool ok;
-        do {
-            asm volatile("" ::: "memory");       // the loads below must be re-issued on every pass
-            ok = true;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                raw[c] = dec_ld16(ll + LL_Q2, (b * DEC_E + h * 32 + c * 4) * 4);
-                ok = ok && raw[c][1] == tag_q && raw[c][3] == tag_q;
-            }
-        } while (!ok && ++guard < spin);
-        if (!ok) *err = 1u;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const unsigned w0 = raw[c][0], w1 = raw[c][2];
-            const bf16x2 lo = *reinterpret_cast<const bf16x2*>(&w0), hi = *reinterpret_cast<const bf16x2*>(&w1);
-            q[c * 4 + 0] = (float)lo[0]; q[c * 4 + 1] = (float)lo[1]; q[c * 4 + 2] = (float)hi[0]; q[c * 4 + 3] = (float)hi[1];
-        }
-    }
+    ll_get_bf16x32(ll, LL_Q2, tag_q, b * DEC_E + h * 32, err, spin, q);      // the 32 query features of (b, h): the same 128 bytes for every lane
 #pragma unroll
     for (int i = 0; i < DEC_MAXK; ++i) {
         float a = 0.f;
@@ -298,9 +278,7 @@ __device__ __forceinline__ void dec_attn(const rt_decoder_fwd_desc& p, const rt_
     l = sm.redf[4] + sm.redf[5] + sm.redf[6] + sm.redf[7];
     const float inv_l = 1.f / l;                 // fully masked row: NaN below, as the reference
     if (t == 0) L.lse2[bh] = ms + __logf(l);
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
+    const rt_drop drop(p.drop_p, dseed);
 #pragma unroll
     for (int d = 0; d < 32; ++d) o[d] = 0.f;
 #pragma unroll
@@ -308,7 +286,7 @@ __device__ __forceinline__ void dec_attn(const rt_decoder_fwd_desc& p, const rt_
         const int j = t + i * 256;
         if (j >= p.S) continue;
         float pr = sc[i] * inv_l;
-        if (do_drop) pr = (rt_hash32(dseed, (uint32_t)((size_t)bh * p.S + j)) >= thresh) ? pr * ks : 0.f;
+        pr = drop.apply(pr, (uint32_t)((size_t)bh * p.S + j));
         if (pr != 0.f || pr != pr) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
@@ -556,7 +534,7 @@ struct DecSmemB {
 
 struct DecLnbSrc { const float* plain; const float* lds; unsigned char* ll; int region; unsigned tag; };
 
-// LayerNorm backward of the M rows, layernorm_bwd_vec_kernel<1>'s arithmetic (one wave per row; block b of that kernel = rows 4b..4b+3 =
+// LayerNorm backward of the M rows (rt_ln_row.h, as layernorm_bwd_vec_kernel<1>: one wave per row; block b of that kernel = rows 4b..4b+3 =
 // waves 0..3 here, so the parameter-gradient partials are the same sums in the same order).
 __device__ __forceinline__ void dec_lnb_rows(const DecLnbSrc& src, const float* x, const float* mean_p, const float* rstd_p, const float* gamma,
                                              int M, float drop2_p, uint32_t seed2, float (*res)[DEC_E], bf16_t* xa, int ld, bool writer,
@@ -564,15 +542,13 @@ __device__ __forceinline__ void dec_lnb_rows(const DecLnbSrc& src, const float* 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane * 4;
     const f32x4 gam = *reinterpret_cast<const f32x4*>(gamma + c);
-    const bool do_drop2 = drop2_p > 0.f;
-    const uint32_t thresh2 = rt_drop_thresh(drop2_p);
-    const float ks2 = do_drop2 ? 1.f / (1.f - drop2_p) : 1.f;
+    const rt_drop drop2(drop2_p, seed2);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 dg[4], db[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) { dg[b] = f32x4{0.f, 0.f, 0.f, 0.f}; db[b] = dg[b]; }
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-#pragma clang fp contract(off)      // as in layernorm_bwd_vec_kernel
         const int row = b * 4 + wave;
         if (row >= M) continue;
         f32x4 d = {0.f, 0.f, 0.f, 0.f};
@@ -580,42 +556,20 @@ __device__ __forceinline__ void dec_lnb_rows(const DecLnbSrc& src, const float* 
         if (src.plain) { d = *reinterpret_cast<const f32x4*>(src.plain + (size_t)row * DEC_E + c); have = true; }
         if (src.lds) { d = *reinterpret_cast<const f32x4*>(src.lds + row * DEC_E + c); have = true; }
         if (src.ll) {
-            u32x4 a, q;
-            int guard = 0;
-            bool ok;
-            do {
-                asm volatile("" ::: "memory");
-                a = dec_ld16(src.ll + src.region, (row * DEC_E + c) * 8);
-                q = dec_ld16(src.ll + src.region, (row * DEC_E + c) * 8 + 16);
-                ok = a[1] == src.tag && a[3] == src.tag && q[1] == src.tag && q[3] == src.tag;
-            } while (!ok && ++guard < spin);
-            if (!ok) *err = 1u;
-            const f32x4 v = f32x4{__uint_as_float(a[0]), __uint_as_float(a[2]), __uint_as_float(q[0]), __uint_as_float(q[2])};
+            const f32x4 v = ll_get_f32x4(src.ll, src.region, src.tag, row * DEC_E + c, err, spin);
             d = have ? d + v : v;
         }
-        const float mean = mean_p[row], rstd = rstd_p[row];
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + (size_t)row * DEC_E + c);
+        const float rstd = rstd_p[row];
         f32x4 xh, g;
         float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            xh[e] = (xv[e] - mean) * rstd;
-            const float de = d[e];
-            dg[b][e] += de * xh[e]; db[b][e] += de;
-            g[e] = de * gam[e];
-            s1 += g[e]; s2 += g[e] * xh[e];
-        }
-        s1 = rt_wave_sum(s1) * (1.f / DEC_E); s2 = rt_wave_sum(s2) * (1.f / DEC_E);
-        f32x4 dx;
-        bf16x4 bb;
+        rt_ln_bwd_group(d, *reinterpret_cast<const f32x4*>(x + (size_t)row * DEC_E + c), mean_p[row], rstd, gam, zero, false, xh, g, s1, s2, dg[b], db[b]);
+        rt_ln_bwd_means<1>(s1, s2);
+        const f32x4 dx = rt_ln_bwd_dx(g, xh, rstd, s1, s2);
         const int o = row * DEC_E + c;
+        const f32x4 d2 = drop2.apply(dx, (uint32_t)o);
+        bf16x4 bb;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dx[e] = rstd * (g[e] - s1 - xh[e] * s2);
-            float d2 = dx[e];
-            if (do_drop2) d2 = (rt_hash32(seed2, (uint32_t)(o + e)) >= thresh2) ? d2 * ks2 : 0.f;
-            bb[e] = (bf16_t)d2;
-        }
+        for (int e = 0; e < 4; ++e) bb[e] = (bf16_t)d2[e];
         *reinterpret_cast<f32x4*>(&res[row][c]) = dx;
         *reinterpret_cast<bf16x4*>(xa + row * ld + c) = bb;
         if (writer && dxb_plain) *reinterpret_cast<bf16x4*>(dxb_plain + o) = bb;
@@ -650,34 +604,12 @@ __device__ __forceinline__ void dec_attn_bwd(const rt_decoder_bwd_desc& p, const
 #pragma unroll
         for (int e = 0; e < 8; ++e) { q[c * 8 + e] = (float)qv[e]; ov[c * 8 + e] = (float)o8[e]; }
     }
-    {
-        u32x4 raw[8];
-        int guard = 0;
-        bool ok;
-        do {
-            asm volatile("" ::: "memory");
-            ok = true;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                raw[c] = dec_ld16(ll + LL_O2, (b * DEC_E + h * 32 + c * 4) * 4);
-                ok = ok && raw[c][1] == tag_in && raw[c][3] == tag_in;
-            }
-        } while (!ok && ++guard < spin);
-        if (!ok) *err = 1u;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const unsigned w0 = raw[c][0], w1 = raw[c][2];
-            const bf16x2 lo = *reinterpret_cast<const bf16x2*>(&w0), hi = *reinterpret_cast<const bf16x2*>(&w1);
-            go[c * 4 + 0] = (float)lo[0]; go[c * 4 + 1] = (float)lo[1]; go[c * 4 + 2] = (float)hi[0]; go[c * 4 + 3] = (float)hi[1];
-        }
-    }
+    ll_get_bf16x32(ll, LL_O2, tag_in, b * DEC_E + h * 32, err, spin, go);
     float delta = 0.f;
 #pragma unroll
     for (int d = 0; d < 32; ++d) delta += go[d] * ov[d];
     const float lse = L.lse2[bh];
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
+    const rt_drop drop(p.drop_p, dseed);
 #pragma unroll
     for (int d = 0; d < 32; ++d) dq[d] = 0.f;
 #pragma unroll
@@ -691,7 +623,7 @@ __device__ __forceinline__ void dec_attn_bwd(const rt_decoder_bwd_desc& p, const
             for (int e = 0; e < 8; ++e) dotk += (float)kv.k[i].c[c][e] * q[c * 8 + e];
         const float pr = kv.ok[i] ? __expf(dotk * p.scale - lse) : 0.f;
         float mk = 1.f;
-        if (do_drop) mk = (rt_hash32(dseed, (uint32_t)((size_t)bh * p.S + j)) >= thresh) ? ks : 0.f;
+        if (drop.on) mk = drop.keep((uint32_t)((size_t)bh * p.S + j)) ? drop.ks : 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll

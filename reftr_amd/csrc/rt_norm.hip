@@ -2,6 +2,7 @@
 // One 64-lane wave owns one token row (D <= 1024); the epilogue emits everything the next GEMM needs
 // (fp32 residual stream, bf16 operand copy, bf16 copy of y + pos) so no separate cast/add kernels run.
 #include "rt_common.h"
+#include "rt_ln_row.h"
 #include <stdlib.h>
 
 namespace {
@@ -35,9 +36,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const rt_layernorm_d
     const float rstd = rsqrtf(rt_wave_sum(ss) / D + p.eps);
     if (lane == 0) { if (p.mean) p.mean[row] = mean; if (p.rstd) p.rstd[row] = rstd; }
     const int orow = rt_map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
+    const rt_drop drop = rt_drop::site(p.drop_p, p.seed_dev, p.drop_seed);
     bf16_t* yb = (bf16_t*)p.y_bf16;
     bf16_t* ypb = (bf16_t*)p.ypos_bf16;
 #pragma unroll
@@ -46,11 +45,27 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const rt_layernorm_d
         if (i < nper && c < D) {
             float y = (v[i] - mean) * rstd * p.gamma[c] + p.beta[c];
             if (p.act == RT_ACT_RELU) y = fmaxf(y, 0.f);
-            if (do_drop) y = (rt_hash32(rt_site_seed(p.seed_dev, p.drop_seed), (uint32_t)(row * D + c)) >= thresh) ? y * ks : 0.f;
+            y = drop.apply(y, (uint32_t)(row * D + c));
             const size_t o = (size_t)orow * D + c;
             if (p.y_f32) p.y_f32[o] = y;
             if (yb) yb[o] = (bf16_t)y;
             if (ypb) ypb[o] = (bf16_t)(y + p.pos[o]);
+        }
+    }
+}
+
+// The tail of both backward kernels: the four waves' d gamma / d beta rows (sm_g / sm_b, `ld` floats apart, written by the caller) are
+// added wave 0 + 1 + 2 + 3 and leave as this workgroup's partial-sum row pair or as one atomic per channel.
+__device__ __forceinline__ void ln_bwd_tail(const rt_layernorm_bwd_desc& p, const float* sm_g, const float* sm_b, const int ld, const int D) {
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += 256) {
+        const float a = sm_g[c] + sm_g[ld + c] + sm_g[2 * ld + c] + sm_g[3 * ld + c];
+        const float b = sm_b[c] + sm_b[ld + c] + sm_b[2 * ld + c] + sm_b[3 * ld + c];
+        if (p.partials) {
+            p.partials[((size_t)blockIdx.x * 2) * D + c] = a; p.partials[((size_t)blockIdx.x * 2 + 1) * D + c] = b;
+        } else {
+            if (p.dgamma) atomicAdd(p.dgamma + c, a);
+            if (p.dbeta) atomicAdd(p.dbeta + c, b);
         }
     }
 }
@@ -65,12 +80,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const rt_layernorm_b
     float dg[LN_MAX_PER_LANE], db[LN_MAX_PER_LANE];
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) { dg[i] = 0.f; db[i] = 0.f; }
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const bool do_drop2 = p.drop2_p > 0.f;
-    const uint32_t thresh2 = rt_drop_thresh(p.drop2_p);
-    const float ks2 = do_drop2 ? 1.f / (1.f - p.drop2_p) : 1.f;
+    const rt_drop drop = rt_drop::site(p.drop_p, p.seed_dev, p.drop_seed), drop2 = rt_drop::site(p.drop2_p, p.seed_dev, p.drop2_seed);
     bf16_t* dxb = (bf16_t*)p.dx_bf16;
 
     for (int row = blockIdx.x * 4 + wave; row < p.M; row += gridDim.x * 4) {
@@ -89,7 +99,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const rt_layernorm_b
                 if (p.dy2) d += p.dy2[o];
                 xh[i] = (xr[c] - mean) * rstd;
                 const float gam = p.gamma[c];
-                if (do_drop) d = (rt_hash32(rt_site_seed(p.seed_dev, p.drop_seed), (uint32_t)(row * D + c)) >= thresh) ? d * ks : 0.f;
+                d = drop.apply(d, (uint32_t)(row * D + c));
                 if (p.act == RT_ACT_RELU) { if (xh[i] * gam + p.beta[c] <= 0.f) d = 0.f; }
                 dg[i] += d * xh[i]; db[i] += d;
                 g[i] = d * gam;
@@ -104,11 +114,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const rt_layernorm_b
                 const float dx = rstd * (g[i] - s1 - xh[i] * s2);
                 const size_t o = (size_t)row * D + c;
                 if (p.dx_f32) p.dx_f32[o] = dx;
-                if (dxb) {
-                    float d2 = dx;
-                    if (do_drop2) d2 = (rt_hash32(rt_site_seed(p.seed_dev, p.drop2_seed), (uint32_t)o) >= thresh2) ? dx * ks2 : 0.f;
-                    dxb[o] = (bf16_t)d2;
-                }
+                if (dxb) dxb[o] = (bf16_t)(drop2.apply(dx, (uint32_t)o));
             }
         }
     }
@@ -118,21 +124,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const rt_layernorm_b
         const int c = lane + (i << 6);
         if (i < nper && c < D) { sm_g[wave][c] = dg[i]; sm_b[wave][c] = db[i]; }
     }
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += 256) {
-        const float a = sm_g[0][c] + sm_g[1][c] + sm_g[2][c] + sm_g[3][c];
-        const float b = sm_b[0][c] + sm_b[1][c] + sm_b[2][c] + sm_b[3][c];
-        if (p.partials) {
-            p.partials[((size_t)blockIdx.x * 2) * D + c] = a; p.partials[((size_t)blockIdx.x * 2 + 1) * D + c] = b;
-        } else {
-            if (p.dgamma) atomicAdd(p.dgamma + c, a);
-            if (p.dbeta) atomicAdd(p.dbeta + c, b);
-        }
-    }
+    ln_bwd_tail(p, &sm_g[0][0], &sm_b[0][0], 1024, D);
 }
 
 // ---------------- vectorised variants for D = 256 * V (V = 1: transformer width, V = 3: BERT width) ----------------
-// Same arithmetic as the kernels above; lane l owns channels 4*(64*i + l) .. +3 of float4 group i, so every tensor row
+// The row arithmetic of rt_ln_row.h; lane l owns channels 4*(64*i + l) .. +3 of float4 group i, so every tensor row
 // is moved with 16-byte accesses (8-byte for bf16) instead of four strided dword accesses per group.
 template <int V>
 __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const rt_layernorm_desc p) {
@@ -153,49 +149,21 @@ __global__ __launch_bounds__(256) void layernorm_fwd_vec_kernel(const rt_layerno
         gam_[i] = *reinterpret_cast<const f32x4*>(p.gamma + c); bet_[i] = *reinterpret_cast<const f32x4*>(p.beta + c);
         pos_[i] = p.ypos_bf16 ? *reinterpret_cast<const f32x4*>(p.pos + (size_t)orow * D + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-    const float mean = rt_wave_sum(s) * (1.f / D);
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < V; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; ss += d * d; }
-    const float rstd = rsqrtf(rt_wave_sum(ss) * (1.f / D) + p.eps);
+    float mean, rstd;
+    rt_ln_stats<V>(v, p.eps, mean, rstd);
     if (lane == 0) { if (p.mean) p.mean[row] = mean; if (p.rstd) p.rstd[row] = rstd; }
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t seed = do_drop ? rt_site_seed(p.seed_dev, p.drop_seed) : 0u;
+    const rt_drop drop = rt_drop::site(p.drop_p, p.seed_dev, p.drop_seed);
     bf16_t* yb = (bf16_t*)p.y_bf16;
     bf16_t* ypb = (bf16_t*)p.ypos_bf16;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         const int c = (i * 64 + lane) * 4;
-        const f32x4 gam = gam_[i], bet = bet_[i];
-        f32x4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y[e] = (v[i][e] - mean) * rstd * gam[e] + bet[e];
-            if (p.act == RT_ACT_RELU) y[e] = fmaxf(y[e], 0.f);
-            if (do_drop) y[e] = (rt_hash32(seed, (uint32_t)(row * D + c + e)) >= thresh) ? y[e] * ks : 0.f;
-        }
+        f32x4 y = rt_ln_affine(v[i], mean, rstd, gam_[i], bet_[i], p.act == RT_ACT_RELU);
+        y = drop.apply(y, (uint32_t)(row * D + c));
         const size_t o = (size_t)orow * D + c;
         if (p.y_f32) *reinterpret_cast<f32x4*>(p.y_f32 + o) = y;
-        if (yb) {
-            bf16x4 b;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b[e] = (bf16_t)y[e];
-            *reinterpret_cast<bf16x4*>(yb + o) = b;
-        }
-        if (ypb) {
-            const f32x4 ps = pos_[i];
-            bf16x4 b;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b[e] = (bf16_t)(y[e] + ps[e]);
-            *reinterpret_cast<bf16x4*>(ypb + o) = b;
-        }
+        if (yb) rt_store_bf16(yb + o, y);
+        if (ypb) rt_store_bf16(ypb + o, y + pos_[i]);
     }
 }
 
@@ -212,18 +180,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const rt_layerno
         gam[i] = *reinterpret_cast<const f32x4*>(p.gamma + (i * 64 + lane) * 4);
         bet[i] = p.beta ? *reinterpret_cast<const f32x4*>(p.beta + (i * 64 + lane) * 4) : dg[i];
     }
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const bool do_drop2 = p.drop2_p > 0.f;
-    const uint32_t thresh2 = rt_drop_thresh(p.drop2_p);
-    const float ks2 = do_drop2 ? 1.f / (1.f - p.drop2_p) : 1.f;
-    const uint32_t seed = do_drop ? rt_site_seed(p.seed_dev, p.drop_seed) : 0u;
-    const uint32_t seed2 = do_drop2 ? rt_site_seed(p.seed_dev, p.drop2_seed) : 0u;
+    const rt_drop drop = rt_drop::site(p.drop_p, p.seed_dev, p.drop_seed), drop2 = rt_drop::site(p.drop2_p, p.seed_dev, p.drop2_seed);
     bf16_t* dxb = (bf16_t*)p.dx_bf16;
 
     for (int row = blockIdx.x * 4 + wave; row < p.M; row += gridDim.x * 4) {
-#pragma clang fp contract(off)      // rt_decoder_bwd repeats this arithmetic and must round the same way: no fused multiply-adds
         const int orow = rt_map_row(row, p.grp_rows, p.grp_stride, p.grp_off);
         const float mean = p.mean[row], rstd = p.rstd[row];
         const f32x4* xr = reinterpret_cast<const f32x4*>(p.x + (size_t)row * D);
@@ -235,38 +195,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const rt_layerno
         for (int i = 0; i < V; ++i) {
             f32x4 d = dyr[i * 64 + lane];
             if (dy2r) d += dy2r[i * 64 + lane];
-            const f32x4 xv = xr[i * 64 + lane];
-            const int c = (i * 64 + lane) * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xh[i][e] = (xv[e] - mean) * rstd;
-                float de = d[e];
-                if (do_drop) de = (rt_hash32(seed, (uint32_t)(row * D + c + e)) >= thresh) ? de * ks : 0.f;
-                if (p.act == RT_ACT_RELU) { if (xh[i][e] * gam[i][e] + bet[i][e] <= 0.f) de = 0.f; }
-                dg[i][e] += de * xh[i][e]; db[i][e] += de;
-                g[i][e] = de * gam[i][e];
-                s1 += g[i][e]; s2 += g[i][e] * xh[i][e];
-            }
+            d = drop.apply(d, (uint32_t)(row * D + (i * 64 + lane) * 4));
+            rt_ln_bwd_group(d, xr[i * 64 + lane], mean, rstd, gam[i], bet[i], p.act == RT_ACT_RELU, xh[i], g[i], s1, s2, dg[i], db[i]);
         }
-        s1 = rt_wave_sum(s1) * (1.f / D); s2 = rt_wave_sum(s2) * (1.f / D);
+        rt_ln_bwd_means<V>(s1, s2);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            const size_t o = (size_t)row * D + c;
-            f32x4 dx;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dx[e] = rstd * (g[i][e] - s1 - xh[i][e] * s2);
+            const size_t o = (size_t)row * D + (i * 64 + lane) * 4;
+            const f32x4 dx = rt_ln_bwd_dx(g[i], xh[i], rstd, s1, s2);
             if (p.dx_f32) *reinterpret_cast<f32x4*>(p.dx_f32 + o) = dx;
-            if (dxb) {
-                bf16x4 b;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float d2 = dx[e];
-                    if (do_drop2) d2 = (rt_hash32(seed2, (uint32_t)(o + e)) >= thresh2) ? d2 * ks2 : 0.f;
-                    b[e] = (bf16_t)d2;
-                }
-                *reinterpret_cast<bf16x4*>(dxb + o) = b;
-            }
+            if (dxb) rt_store_bf16(dxb + o, drop2.apply(dx, (uint32_t)o));
         }
     }
     if (!p.dgamma && !p.dbeta && !p.partials) return;
@@ -275,17 +213,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_vec_kernel(const rt_layerno
         *reinterpret_cast<f32x4*>(&sm_g[wave][(i * 64 + lane) * 4]) = dg[i];
         *reinterpret_cast<f32x4*>(&sm_b[wave][(i * 64 + lane) * 4]) = db[i];
     }
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += 256) {
-        const float a = sm_g[0][c] + sm_g[1][c] + sm_g[2][c] + sm_g[3][c];
-        const float b = sm_b[0][c] + sm_b[1][c] + sm_b[2][c] + sm_b[3][c];
-        if (p.partials) {
-            p.partials[((size_t)blockIdx.x * 2) * D + c] = a; p.partials[((size_t)blockIdx.x * 2 + 1) * D + c] = b;
-        } else {
-            if (p.dgamma) atomicAdd(p.dgamma + c, a);
-            if (p.dbeta) atomicAdd(p.dbeta + c, b);
-        }
-    }
+    ln_bwd_tail(p, &sm_g[0][0], &sm_b[0][0], D, D);
 }
 
 // ---------------- GroupNorm over token-major images x[b][p][c], groups of C/G channels ----------------

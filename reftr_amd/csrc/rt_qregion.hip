@@ -18,6 +18,7 @@
 // Weight gradients stay with the grouped launches (rt_small_wgrad_grouped / rt_conv_wgrad_grouped): the kernels emit the bf16 dy
 // operands those read.
 #include "rt_common.h"
+#include "rt_ln_row.h"
 #include "rt_loss_row.h"
 
 namespace {
@@ -131,46 +132,25 @@ __device__ __forceinline__ void q_gemm(const bf16_t* __restrict__ W, const int l
     }
 }
 
-// LayerNorm of one 256-feature row by one wave (lane: features 4 lane .. 4 lane + 3): rt_layernorm_fwd's arithmetic
-__device__ __forceinline__ f32x4 ln_row(const f32x4 v, const f32x4 gam, const f32x4 bet, const float eps, const bool relu,
-                                        float& mean, float& rstd) {
-    const float s = (v[0] + v[1]) + (v[2] + v[3]);
-    mean = rt_wave_sum(s) * (1.f / QE);
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; ss += d * d; }
-    rstd = rsqrtf(rt_wave_sum(ss) * (1.f / QE) + eps);
-    f32x4 y;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        y[e] = (v[e] - mean) * rstd * gam[e] + bet[e];
-        if (relu) y[e] = fmaxf(y[e], 0.f);
-    }
-    return y;
+// LayerNorm of one 256-feature row by one wave (lane: features 4 lane .. 4 lane + 3), rt_ln_row.h's arithmetic as the launches run it
+__device__ __forceinline__ f32x4 q_ln(const float* x, const float* gamma, const float* beta, const float eps, const bool relu,
+                                      float* mean_out, float* rstd_out) {
+    const int lane = threadIdx.x & 63;
+    const f32x4 v = ld4(x + lane * 4);
+    float mean, rstd;
+    rt_ln_stats<1>(&v, eps, mean, rstd);
+    if (lane == 0) { *mean_out = mean; *rstd_out = rstd; }
+    return rt_ln_affine(v, mean, rstd, ld4(gamma + lane * 4), ld4(beta + lane * 4), relu);
 }
-// its backward (rt_layernorm_bwd's arithmetic, un-contracted like there): d = dy of the row, returns dx; dg / db accumulate the
-// row's contribution to d gamma / d beta.  drop: the forward's dropout mask (behind the ReLU) regenerated from (seed, row * 256 + c).
-__device__ __forceinline__ f32x4 ln_row_bwd(const f32x4 d, const f32x4 xv, const float mean, const float rstd, const f32x4 gam,
-                                            const f32x4 bet, const bool relu, const bool do_drop, const uint32_t seed,
-                                            const uint32_t thresh, const float ks, const uint32_t idx0, f32x4& dg, f32x4& db) {
-#pragma clang fp contract(off)
+// its backward: d = dy of the row (already through the forward's dropout mask), returns dx; dg / db accumulate the row's contribution
+// to d gamma / d beta
+__device__ __forceinline__ f32x4 q_ln_bwd(const f32x4 d, const float* x, const float mean, const float rstd, const f32x4 gam, const f32x4 bet,
+                                          const bool relu, f32x4& dg, f32x4& db) {
     f32x4 xh, g;
     float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        xh[e] = (xv[e] - mean) * rstd;
-        float de = d[e];
-        if (do_drop) de = (rt_hash32(seed, idx0 + (uint32_t)e) >= thresh) ? de * ks : 0.f;
-        if (relu) { if (xh[e] * gam[e] + bet[e] <= 0.f) de = 0.f; }
-        dg[e] += de * xh[e]; db[e] += de;
-        g[e] = de * gam[e];
-        s1 += g[e]; s2 += g[e] * xh[e];
-    }
-    s1 = rt_wave_sum(s1) * (1.f / QE); s2 = rt_wave_sum(s2) * (1.f / QE);
-    f32x4 dx;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) dx[e] = rstd * (g[e] - s1 - xh[e] * s2);
-    return dx;
+    rt_ln_bwd_group(d, ld4(x + (threadIdx.x & 63) * 4), mean, rstd, gam, bet, relu, xh, g, s1, s2, dg, db);
+    rt_ln_bwd_means<1>(s1, s2);
+    return rt_ln_bwd_dx(g, xh, rstd, s1, s2);
 }
 // the waves' d gamma / d beta sums of one LayerNorm -> this workgroup's partial-sum row pair (rt_ln_param_grad_grouped's input)
 __device__ __forceinline__ void ln_partials(float (*sm)[QE], const f32x4 dg, const f32x4 db, float* __restrict__ part) {
@@ -275,9 +255,7 @@ __global__ __launch_bounds__(QT) void qenc_fwd_kernel(const rt_qenc_fwd_desc p) 
     bf16_t* cat16 = (bf16_t*)p.cat16;
     for (int j = wave; j < P; j += QW) {
         const int r = b * P + j;
-        float mean, rstd;
-        const f32x4 y = ln_row(ld4(p.co + (size_t)r * QE + lane * 4), ld4(p.gc + lane * 4), ld4(p.betc + lane * 4), p.eps, false, mean, rstd);
-        if (lane == 0) { p.cmean[r] = mean; p.crstd[r] = rstd; }
+        const f32x4 y = q_ln(p.co + (size_t)r * QE, p.gc, p.betc, p.eps, false, p.cmean + r, p.crstd + r);
         st4b(cat16 + (size_t)r * 2 * QE + lane * 4, y + ld4(p.mem32 + (size_t)b * S * QE + lane * 4));
     }
     __syncthreads(); q_stamp(0, q_slot);
@@ -290,20 +268,11 @@ __global__ __launch_bounds__(QT) void qenc_fwd_kernel(const rt_qenc_fwd_desc p) 
     __syncthreads(); q_stamp(0, q_slot);
     // ---- stage 6: LayerNorm + ReLU + Dropout(0.1) -> a16
     {
-        const bool do_drop = p.drop_p > 0.f;
-        const uint32_t thresh = rt_drop_thresh(p.drop_p);
-        const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-        const uint32_t seed = do_drop ? rt_site_seed(p.seed_dev, p.drop_seed) : 0u;
+        const rt_drop drop = rt_drop::site(p.drop_p, p.seed_dev, p.drop_seed);
         for (int j = wave; j < P; j += QW) {
             const int r = b * P + j;
-            float mean, rstd;
-            f32x4 y = ln_row(ld4(p.t1 + (size_t)r * QE + lane * 4), ld4(p.g1 + lane * 4), ld4(p.bet1 + lane * 4), p.eps, true, mean, rstd);
-            if (lane == 0) { p.m1[r] = mean; p.r1[r] = rstd; }
-            if (do_drop) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    y[e] = (rt_hash32(seed, (uint32_t)(r * QE + lane * 4 + e)) >= thresh) ? y[e] * ks : 0.f;
-            }
+            f32x4 y = q_ln(p.t1 + (size_t)r * QE, p.g1, p.bet1, p.eps, true, p.m1 + r, p.r1 + r);
+            y = drop.apply(y, (uint32_t)(r * QE + lane * 4));
             st4b((bf16_t*)p.a16 + (size_t)r * QE + lane * 4, y);
         }
     }
@@ -319,9 +288,7 @@ __global__ __launch_bounds__(QT) void qenc_fwd_kernel(const rt_qenc_fwd_desc p) 
     // ---- stage 8: LayerNorm + ReLU -> fused phrase feature; tgt = f + query_embed[:, :E], query_pos = f + query_embed[:, E:]
     for (int j = wave; j < P; j += QW) {
         const int r = b * P + j;
-        float mean, rstd;
-        const f32x4 f = ln_row(ld4(p.t2 + (size_t)r * QE + lane * 4), ld4(p.g5 + lane * 4), ld4(p.bet5 + lane * 4), p.eps, true, mean, rstd);
-        if (lane == 0) { p.m2[r] = mean; p.r2[r] = rstd; }
+        const f32x4 f = q_ln(p.t2 + (size_t)r * QE, p.g5, p.bet5, p.eps, true, p.m2 + r, p.r2 + r);
         for (int q = 0; q < p.nq; ++q) {
             const size_t o = ((size_t)r * p.nq + q) * QE + lane * 4;
             const f32x4 tg = f + ld4(p.qembed + (size_t)q * 2 * QE + lane * 4);
@@ -351,9 +318,7 @@ __global__ __launch_bounds__(QT) void head_loss_kernel(const rt_head_loss_desc p
 
     // ---- decoder.norm on the layer's rows (transformer.py:131-141)
     for (int m = wave; m < N; m += QW) {
-        float mean, rstd;
-        const f32x4 y = ln_row(ld4(t3 + (size_t)m * QE + lane * 4), ld4(p.gn + lane * 4), ld4(p.betn + lane * 4), p.eps, false, mean, rstd);
-        if (lane == 0) { p.hmean[r0 + m] = mean; p.hrstd[r0 + m] = rstd; }
+        const f32x4 y = q_ln(t3 + (size_t)m * QE, p.gn, p.betn, p.eps, false, p.hmean + r0 + m, p.hrstd + r0 + m);
         st4b(hs16 + (size_t)m * QE + lane * 4, y);
     }
     __syncthreads(); q_stamp(1, q_slot);
@@ -497,8 +462,8 @@ __global__ __launch_bounds__(QT) void head_loss_kernel(const rt_head_loss_desc p
     {
         const f32x4 gam = ld4(p.gn + lane * 4), bet = ld4(p.betn + lane * 4);
         for (int m = wave; m < N; m += QW) {
-            const f32x4 dx = ln_row_bwd(ld4(dhs + (size_t)m * QE + lane * 4), ld4(t3 + (size_t)m * QE + lane * 4), p.hmean[r0 + m],
-                                        p.hrstd[r0 + m], gam, bet, false, false, 0u, 0u, 1.f, 0u, dg, db);
+            const f32x4 dx = q_ln_bwd(ld4(dhs + (size_t)m * QE + lane * 4), t3 + (size_t)m * QE, p.hmean[r0 + m], p.hrstd[r0 + m], gam, bet,
+                                      false, dg, db);
             st4(p.dnorm + (r0 + m) * QE + lane * 4, dx);
         }
     }
@@ -516,10 +481,7 @@ __global__ __launch_bounds__(QT) void qenc_bwd_kernel(const rt_qenc_bwd_desc p) 
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int S = p.S, L = p.L, P = p.P;
     const int rb = b * P;                     // first phrase row of the image
-    const bool do_drop = p.drop_p > 0.f;
-    const uint32_t thresh = rt_drop_thresh(p.drop_p);
-    const float ks = do_drop ? 1.f / (1.f - p.drop_p) : 1.f;
-    const uint32_t seed = do_drop ? rt_site_seed(p.seed_dev, p.drop_seed) : 0u;
+    const rt_drop drop = rt_drop::site(p.drop_p, p.seed_dev, p.drop_seed);
 
     // ---- d fused = ga (+ gb) + d query_pos; d query_embed; fuse_encoder_query.5 (LayerNorm + ReLU) backward -> dt2b
     {
@@ -532,7 +494,7 @@ __global__ __launch_bounds__(QT) void qenc_bwd_kernel(const rt_qenc_bwd_desc p) 
             if (p.gb) { const f32x4 g2 = ld4(p.gb + (size_t)r * QE + lane * 4); d = d + g2; sa = sa + g2; }
             d = d + q;
             sa = sa + a; sq = sq + q;
-            const f32x4 dx = ln_row_bwd(d, ld4(p.t2 + (size_t)r * QE + lane * 4), p.m2[r], p.r2[r], gam, bet, true, false, 0u, 0u, 1.f, 0u, dg, db);
+            const f32x4 dx = q_ln_bwd(d, p.t2 + (size_t)r * QE, p.m2[r], p.r2[r], gam, bet, true, dg, db);
             st4b((bf16_t*)p.dt2b + (size_t)r * QE + lane * 4, dx);
         }
         if (p.dqembed) {
@@ -555,8 +517,9 @@ __global__ __launch_bounds__(QT) void qenc_bwd_kernel(const rt_qenc_bwd_desc p) 
         const f32x4 gam = ld4(p.g1 + lane * 4), bet = ld4(p.bet1 + lane * 4);
         for (int j = wave; j < P; j += QW) {
             const int r = rb + j;
-            const f32x4 dx = ln_row_bwd(ld4(p.da + (size_t)r * QE + lane * 4), ld4(p.t1 + (size_t)r * QE + lane * 4), p.m1[r], p.r1[r], gam, bet,
-                                        true, do_drop, seed, thresh, ks, (uint32_t)(r * QE + lane * 4), dg, db);
+            f32x4 d = ld4(p.da + (size_t)r * QE + lane * 4);
+            d = drop.apply(d, (uint32_t)(r * QE + lane * 4));
+            const f32x4 dx = q_ln_bwd(d, p.t1 + (size_t)r * QE, p.m1[r], p.r1[r], gam, bet, true, dg, db);
             st4b((bf16_t*)p.dt1b + (size_t)r * QE + lane * 4, dx);
         }
         ln_partials(sm, dg, db, p.part1);
@@ -572,8 +535,7 @@ __global__ __launch_bounds__(QT) void qenc_bwd_kernel(const rt_qenc_bwd_desc p) 
         const f32x4 gam = ld4(p.gc + lane * 4), bet = ld4(p.betc + lane * 4);
         for (int j = wave; j < P; j += QW) {
             const int r = rb + j;
-            const f32x4 dx = ln_row_bwd(ld4(p.dcat + (size_t)r * 2 * QE + lane * 4), ld4(p.co + (size_t)r * QE + lane * 4), p.cmean[r], p.crstd[r],
-                                        gam, bet, false, false, 0u, 0u, 1.f, 0u, dg, db);
+            const f32x4 dx = q_ln_bwd(ld4(p.dcat + (size_t)r * 2 * QE + lane * 4), p.co + (size_t)r * QE, p.cmean[r], p.crstd[r], gam, bet, false, dg, db);
             st4b((bf16_t*)p.dcob + (size_t)r * QE + lane * 4, dx);
         }
         ln_partials(sm, dg, db, p.partc);

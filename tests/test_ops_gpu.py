@@ -65,6 +65,62 @@ def test_layernorm_rowmap_and_dropout(hip):
     assert rel(dxb, xg.grad * keep2 / (1 - np.float32(0.2))) < 3e-3
 
 
+@pytest.mark.parametrize("D", [256, 768])
+def test_layernorm_vec_second_row_atomics(hip, D):
+    """The vectorised kernels against fp64 torch where a wave of the backward walks a second row and the last workgroup is ragged:
+    M = 1029 = 3 * 343 rows over the 256 workgroups of four rows that the atomics path is capped at, with ReLU, both dropout sites,
+    dy2 and a row map all at once; d gamma / d beta through the atomics."""
+    g = torch.Generator().manual_seed(40 + D)
+    B, L, S, off = 3, 343, 350, 2
+    M = B * L
+    p, seed, p2, seed2 = 0.1, 77, 0.2, 5
+    x = torch.randn(M, D, generator=g)
+    gam = torch.rand(D, generator=g) + 0.5; bet = torch.randn(D, generator=g) * 0.1
+    pos = torch.randn(B * S, D, generator=g); dy = torch.randn(B * S, D, generator=g); dy2 = torch.randn(B * S, D, generator=g)
+    rows = lambda t: t.view(B, S, D)[:, off:off + L].reshape(M, D)
+    keep = torch.from_numpy(hash_keep(seed, np.arange(M * D, dtype=np.uint64), p).reshape(M, D))
+    keep2 = torch.from_numpy(hash_keep(seed2, np.arange(M * D, dtype=np.uint64), p2).reshape(M, D))
+    x64, g64, b64 = (t.double().requires_grad_(True) for t in (x, gam, bet))
+    y = F.relu(F.layer_norm(x64, (D,), g64, b64, 1e-5)) * keep / (1 - float(np.float32(p)))
+    y.backward(rows(dy).double() + rows(dy2).double())
+    yf = torch.zeros(B * S, D, device="cuda"); yb = torch.zeros(B * S, D, device="cuda", dtype=torch.bfloat16); ypb = torch.zeros_like(yb)
+    _, _, _, mean, rstd = hip.layernorm_fwd(cu(x), cu(gam), cu(bet), 1e-5, act=1, drop_p=p, drop_seed=seed, pos=cu(pos), y_f32=yf,
+                                            y_bf16=yb, ypos_bf16=ypb, rowmap=(L, S, off))
+    e_y, e_yb, e_yp = rel(rows(yf.cpu()), y), rel(rows(yb.cpu()), y), rel(rows(ypb.cpu()), y.detach() + rows(pos))
+    print(f"D={D}: y {e_y:.2e} y_bf16 {e_yb:.2e} ypos_bf16 {e_yp:.2e}")
+    assert e_y < 1e-5 and e_yb < 3e-3 and e_yp < 3e-3
+    assert float(yf.cpu().view(B, S, D)[:, :off].abs().max()) == 0.0 and float(yf.cpu().view(B, S, D)[:, off + L:].abs().max()) == 0.0
+    dgam = torch.zeros(D, device="cuda"); dbet = torch.zeros(D, device="cuda")
+    dxf, dxb = hip.layernorm_bwd(cu(dy), cu(x), cu(gam), cu(bet), mean, rstd, dgam, dbet, dy2=cu(dy2), act=1, drop_p=p, drop_seed=seed,
+                                 drop2_p=p2, drop2_seed=seed2, rowmap=(L, S, off))
+    e_dx, e_dxb = rel(dxf, x64.grad), rel(dxb, x64.grad * keep2 / (1 - float(np.float32(p2))))
+    e_dg, e_db = rel(dgam, g64.grad), rel(dbet, b64.grad)
+    print(f"D={D}: dx {e_dx:.2e} dx_bf16 {e_dxb:.2e} dgamma {e_dg:.2e} dbeta {e_db:.2e}")
+    assert e_dx < 2e-5 and e_dxb < 3e-3 and e_dg < 2e-5 and e_db < 2e-5
+
+
+def test_layernorm_partials_past_cap(hip):
+    """d gamma / d beta through the partial-sum path (LnGradBatch) one row past its 880 workgroups of four rows: M = 3525, so one
+    wave takes a second row; against fp64 torch."""
+    g = torch.Generator().manual_seed(41)
+    M, D = 3525, 256
+    x = torch.randn(M, D, generator=g)
+    gam = torch.rand(D, generator=g) + 0.5; bet = torch.randn(D, generator=g) * 0.1
+    dy = torch.randn(M, D, generator=g)
+    x64, g64, b64 = (t.double().requires_grad_(True) for t in (x, gam, bet))
+    y = F.layer_norm(x64, (D,), g64, b64, 1e-5)
+    y.backward(dy.double())
+    yf, yb, _, mean, rstd = hip.layernorm_fwd(cu(x), cu(gam), cu(bet), 1e-5)
+    dgam = torch.zeros(D, device="cuda"); dbet = torch.zeros(D, device="cuda")
+    batch = hip.LnGradBatch()
+    dxf, dxb = hip.layernorm_bwd(cu(dy), cu(x), cu(gam), cu(bet), mean, rstd, dgam, dbet, pg_batch=batch)
+    assert len(batch.jobs) == 1 and batch.jobs[0].n_blocks == 880
+    batch.run()
+    e = [rel(yf, y), rel(yb, y), rel(dxf, x64.grad), rel(dxb, x64.grad), rel(dgam, g64.grad), rel(dbet, b64.grad)]
+    print("y {:.2e} y_bf16 {:.2e} dx {:.2e} dx_bf16 {:.2e} dgamma {:.2e} dbeta {:.2e}".format(*e))
+    assert e[0] < 1e-5 and e[1] < 3e-3 and e[2] < 2e-5 and e[3] < 3e-3 and e[4] < 2e-5 and e[5] < 2e-5
+
+
 def test_groupnorm_fwd_bwd(hip):
     g = torch.Generator().manual_seed(9)
     B, HW, C, G, L = 3, 12, 256, 32, 4
