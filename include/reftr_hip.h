@@ -364,8 +364,11 @@ typedef struct rt_mask_loss_desc {
     float* dpred; const float* g_focal; const float* g_dice;
     int32_t B, h, w, Ht, Wt, ldp, lddp;
     float inv_norm;
-    float* gbuf;           /* backward only: scratch fp32 [B, Ht, Wt] (the per-target-pixel gradient between the two passes) */
+    float* gbuf;           /* backward: scratch fp32 [B, Ht, Wt] (the per-target-pixel gradient between the two passes); forward, optional:
+                              RT_MASK_LOSS_PARTIALS floats per image -- the workgroups' partial sums go there and are added in a fixed
+                              order (the same loss bits from run to run) instead of through atomics */
 } rt_mask_loss_desc;
+#define RT_MASK_LOSS_PARTIALS 1024     /* 4 sums x at most 256 workgroups per image */
 int rt_mask_loss(const rt_mask_loss_desc* d, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
@@ -725,6 +728,47 @@ typedef struct rt_box_post_desc {
     int32_t B, P, K;
 } rt_box_post_desc;
 int rt_box_postprocess(const rt_box_post_desc* d, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * rt_eval_metrics — the metric stage of engine_vg.evaluate (engine_vg.py:127-152) for one batch, running totals kept on the device.
+ * Two launches on `stream`, no floating-point atomics, nothing the caller has to clear, the same bits from run to run:
+ *   (a) mask partials (only when `masks` is given), grid (chunk, image): a workgroup counts I = sum(pred & tgt), U = sum(pred | tgt)
+ *       as integers over its run of RT_EVAL_CHUNK pixels of the image's ih x iw (= sizes[b]) pixels -- pred = query 0 of image b in
+ *       `masks` (uint8 [B, Q, max_h, max_w], what rt_mask_postprocess wrote), read at pitch max_w inside [:ih, :iw] only; the target at
+ *       its own pitch -- and stores {I, U} to partials[b][chunk] (int32 workspace of B * ceil(max_h * max_w / RT_EVAL_CHUNK) * 2 words);
+ *   (b) finish, ONE workgroup, image ascending then row ascending:
+ *       boxes: the r-th VALID phrase of image b (rt_box_postprocess's ordered selection of pred_boxes fp32 [B, P, K, 4] cxcywh by valid
+ *       uint8 [B, P, K]) is paired with target box r, at most n_b rows; IoU in fp32, every operation un-fused in util/box_ops.py's
+ *       order (box_cxcywh_to_xyxy of both, then box_iou(target, pred): areas, max / min, clamp(min=0), inter = w * h,
+ *       union = (a1 + a2) - inter, inter / union; 0 / 0 stays NaN) -> iou_det fp32 [B, P], unused rows 0;
+ *       masks: the partials added in chunk order to int64 I_b, U_b -> iu int64 [B, 2] = {I_b, U_b}, iou_seg fp32 [B] =
+ *       (float)I_b / (float)U_b (NaN when both are empty, as util/box_ops.py mask_iou); an image whose mask pointer is 0 is left out
+ *       (iou_seg 0, iu 0, not counted);
+ *       accumulators: `acc` = RT_EVAL_SLOTS words of 8 bytes, int64 but for the two double sums; hits are the samples whose fp32 IoU is
+ *       STRICTLY greater than the fp32 value nearest 0.5, 0.6, 0.7, 0.8, 0.9 (a NaN is a miss, and leaves the sum NaN as torch's does).
+ *       reset != 0: the accumulators start from zero in this same launch (the first batch of an evaluation).
+ * table (DEVICE int64 [B][5]) = {pointer to image b's target boxes fp32 [n_b, 4] cxcywh, n_b, pointer to its target mask (1 byte per
+ * pixel, non-zero = set, row pitch = its width; 0: none), mask height, mask width}.  masks == NULL: the box part only (sizes, partials,
+ * iou_seg, iu may be NULL).  RT_ERR_UNSUPPORTED for max_h * max_w >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+enum { RT_EVAL_DET_N = 0, RT_EVAL_DET_HIT = 1 /* .. 5 */, RT_EVAL_SEG_N = 6, RT_EVAL_SEG_HIT = 7 /* .. 11 */, RT_EVAL_SEG_I = 12,
+       RT_EVAL_SEG_U = 13, RT_EVAL_DET_SUM = 14 /* double */, RT_EVAL_SEG_SUM = 15 /* double */, RT_EVAL_SLOTS = 16 };
+#define RT_EVAL_CHUNK 16384
+typedef struct rt_eval_metrics_args {
+    const float*   pred_boxes;
+    const uint8_t* valid;
+    const int64_t* table;
+    const uint8_t* masks;
+    const int32_t* sizes;
+    int32_t* partials;
+    float*   iou_det;
+    float*   iou_seg;
+    int64_t* iu;
+    void*    acc;
+    int32_t B, P, K, Q, max_h, max_w;
+    int32_t reset;
+} rt_eval_metrics_args;
+int rt_eval_metrics(const rt_eval_metrics_args* a, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * rt_comm_* — the data-parallel gradient exchange: what the reference gets from

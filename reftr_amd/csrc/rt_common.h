@@ -104,6 +104,21 @@ __device__ __forceinline__ float rt_block_sum(float v, float* sm) {
     return r;
 }
 
+// Ordered selection of one image's valid phrases, one pass of 64 phrase slots per call (rt_box_postprocess, rt_eval_metrics).
+// `valid_b` is the image's [P, K] slice of phrase_mask; the reference masked_selects the (p, k) entries of [P, K, 4] whose mask is
+// set and keeps prediction 0 of each selected phrase (post_process.py:62-70).  The K entries of a phrase are equal by construction
+// (reftr_transformer.py:237-238), so a phrase is selected iff its entry 0 is set; rank = number of selected phrases in front of it.
+// Called by ALL 64 lanes of one wave with ph = j0 + lane: ranks inside a pass come from a ballot + population count of the lower
+// lanes (ordered, exact), `base` carries the count of the passes before and is advanced by this pass's.  Returns whether this
+// lane's phrase is selected; `rank` is meaningful only then.
+__device__ __forceinline__ bool rt_phrase_rank(const uint8_t* __restrict__ valid_b, int P, int K, int ph, int lane, int& base, int& rank) {
+    const bool mine = ph < P && valid_b[(size_t)ph * K] != 0;
+    const unsigned long long bal = __ballot(mine);
+    rank = base + __popcll(bal & ((1ull << lane) - 1ull));
+    base += __popcll(bal);
+    return mine;
+}
+
 // Row map of the grouped / broadcast row layouts (norm and fused-add descriptors):
 // grp_rows > 0: (r / g) * stride + off + r % g;  grp_rows < 0: broadcast (r / -g) * stride + off;  0: identity
 __device__ __forceinline__ int rt_map_row(int r, int grp_rows, int grp_stride, int grp_off) {

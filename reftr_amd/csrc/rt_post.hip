@@ -72,19 +72,12 @@ __global__ __launch_bounds__(256) void mask_postprocess_kernel(const rt_mask_pos
 __global__ __launch_bounds__(64) void box_postprocess_kernel(const rt_box_post_desc p) {
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
-    // phrase_mask is [B, P, K]; the reference masked_selects the (p, k) entries of [P, K, 4] whose mask is set and keeps
-    // prediction 0 of each selected phrase (post_process.py:62-70).  The K entries of a phrase are equal by construction
-    // (reftr_transformer.py:237-238), so a phrase is selected iff its entry 0 is set; rank = number of selected phrases in
-    // front of it.  Any P: the wave walks the phrases 64 at a time, ranks inside a pass come from a ballot + population count
-    // of the lower lanes (ordered, exact), `base` carries the count of the passes before.
-    int base = 0;
+    // phrase_mask is [B, P, K]; any P: the wave walks the phrases 64 at a time, rt_phrase_rank (rt_common.h) gives each selected
+    // phrase its place in the reference's masked_select order
+    int base = 0, rank;
     for (int j0 = 0; j0 < p.P; j0 += 64) {
         const int ph = j0 + lane;
-        const bool mine = ph < p.P && p.valid[((size_t)b * p.P + ph) * p.K] != 0;
-        const unsigned long long bal = __ballot(mine);
-        const int rank = base + __popcll(bal & ((1ull << lane) - 1ull));
-        base += __popcll(bal);
-        if (!mine) continue;
+        if (!rt_phrase_rank(p.valid + (size_t)b * p.P * p.K, p.P, p.K, ph, lane, base, rank)) continue;
         const float* s = p.boxes + ((size_t)(b * p.P + ph) * p.K) * 4;
         const float cx = s[0], cy = s[1], w = s[2], h = s[3];
         float x0 = __fsub_rn(cx, __fmul_rn(0.5f, w)), y0 = __fsub_rn(cy, __fmul_rn(0.5f, h));

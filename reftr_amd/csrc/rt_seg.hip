@@ -306,12 +306,29 @@ __global__ __launch_bounds__(256) void mask_loss_fwd_kernel(const rt_mask_loss_d
     const int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sm[wv][0] = f; sm[wv][1] = it; sm[wv][2] = ps; sm[wv][3] = ts; }
     __syncthreads();
-    if (threadIdx.x < 4) atomicAdd(p.sums + b * 4 + threadIdx.x, sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x]);
+    if (threadIdx.x < 4) {
+        const float v = sm[0][threadIdx.x] + sm[1][threadIdx.x] + sm[2][threadIdx.x] + sm[3][threadIdx.x];
+        // with a workspace (gbuf: [B, gridDim.x, 4]) every workgroup stores its own partial and mask_loss_final_kernel adds them in a
+        // fixed order: the same loss bits from run to run (evaluate's losses are compared across runs); without one, atomics as before
+        if (p.gbuf) p.gbuf[((size_t)b * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = v;
+        else atomicAdd(p.sums + b * 4 + threadIdx.x, v);
+    }
 }
 
 // losses[0] = focal, losses[1] = dice (both already divided by the normaliser B*Q)
-__global__ void mask_loss_final_kernel(const float* __restrict__ sums, float* __restrict__ losses, int B, int npix, float inv_norm) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// (one wave; `partials` [B, gx, 4] when the forward stored per-workgroup partials: added here lane-strided + butterfly, a fixed order)
+__global__ __launch_bounds__(64) void mask_loss_final_kernel(float* __restrict__ sums, float* __restrict__ losses, int B, int npix, float inv_norm,
+                                                             const float* __restrict__ partials, int gx) {
+    if (partials) {
+        for (int i = 0; i < B * 4; ++i) {
+            const int b = i >> 2, t = i & 3;
+            float v = 0.f;
+            for (int c = threadIdx.x; c < gx; c += 64) v += partials[((size_t)b * gx + c) * 4 + t];
+            v = rt_wave_sum(v);
+            if (threadIdx.x == 0) sums[i] = v;
+        }
+    }
+    if (threadIdx.x != 0) return;
     float f = 0.f, d = 0.f;
     for (int b = 0; b < B; ++b) {
         f += sums[b * 4] / (float)npix;
@@ -472,11 +489,14 @@ extern "C" int rt_mask_loss(const rt_mask_loss_desc* d, rt_stream_t stream) {
     const int gx = grid_for((size_t)d->Ht * d->Wt, 256);
     if (!d->dpred) {
         if (!d->losses) return RT_ERR_BADARG;
-        hipError_t e = rt_zero_f32(d->sums, 4 * (size_t)d->B, s);
-        if (e != hipSuccess) return (int)e;
+        if (!d->gbuf) {
+            hipError_t e = rt_zero_f32(d->sums, 4 * (size_t)d->B, s);
+            if (e != hipSuccess) return (int)e;
+        }
         hipLaunchKernelGGL(mask_loss_fwd_kernel, dim3(gx, d->B), dim3(256), 0, s, *d);
         RT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(mask_loss_final_kernel, dim3(1), dim3(64), 0, s, d->sums, d->losses, d->B, d->Ht * d->Wt, d->inv_norm);
+        hipLaunchKernelGGL(mask_loss_final_kernel, dim3(1), dim3(64), 0, s, d->sums, d->losses, d->B, d->Ht * d->Wt, d->inv_norm,
+                           (const float*)d->gbuf, gx);
         RT_CHECK_LAUNCH();
     } else {
         if (!d->g_focal || !d->g_dice || d->lddp <= 0 || !d->gbuf) return RT_ERR_BADARG;

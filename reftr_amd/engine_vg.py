@@ -1183,10 +1183,44 @@ def _dump_visuals(root, dataset, dataset_id, mask_origin, pred_box, mask_att):
             plt.imsave(root / "att" / f"{tag}_{head}.jpg", att[head, :h // 2, :w // 2], cmap="viridis")
 
 
+def _metered(postprocessors, device):
+    """evaluate() scores on the device (metrics.EvalMeter: two launches per batch, totals read back once) unless REFTR_EVAL_METRICS=0,
+    the device is a CPU, or a post-processor is not this package's (the meter reads PostProcessSegm's frame)."""
+    from .models.post_process import PostProcessSegm, PostProcessVGMultiPhrase
+    return (os.environ.get("REFTR_EVAL_METRICS", "1") == "1" and torch.device(device).type == "cuda"
+            and isinstance(postprocessors["bbox"], PostProcessVGMultiPhrase)
+            and isinstance(postprocessors.get("segm", PostProcessSegm()), PostProcessSegm))
+
+
+def _fill_results(results_dict, targets, results_scaled):
+    """results_dict[image_id] = the image's scaled boxes as nested lists, from ONE device-to-host copy per batch for boxes and
+    image ids together (float64 holds an fp32 box coordinate and an image id below 2^53 exactly)."""
+    sel = [i for i, tg in enumerate(targets) if "image_id" in tg]
+    if not sel:
+        return
+    dev = results_scaled[0]["boxes"].device
+    ids = [targets[i]["image_id"] for i in sel]
+    on_dev = [torch.is_tensor(v) and v.device == dev for v in ids]
+    parts = [results_scaled[i]["boxes"].reshape(-1).double() for i in sel]
+    if all(on_dev):
+        parts.append(torch.stack([v.reshape(()) for v in ids]).double())
+    flat = torch.cat(parts).cpu().tolist()
+    if all(on_dev):
+        ids = [int(v) for v in flat[len(flat) - len(sel):]]
+    o = 0
+    for i, image_id in zip(sel, ids):
+        n = results_scaled[i]["boxes"].shape[0]
+        results_dict[int(image_id)] = [flat[o + 4 * r: o + 4 * r + 4] for r in range(n)]
+        o += 4 * n
+
+
 @torch.no_grad()
 def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=None, visualize=False):
     """engine_vg.evaluate (engine_vg.py:82-225): losses, Acc@0.5 / mean IoU of the predicted boxes (:127-140), mask IoU when a
     'segm' post-processor is present (:143-152), boxes scaled to the original image size in the returned results dict (:141,203).
+    On a GPU the metrics are scored by metrics.EvalMeter (csrc/rt_eval.hip: one ABI call per batch, the running totals stay on the
+    device and are read back once), which adds 'seg_oiou' and 'seg_prec@0.5' ... '@0.9' for a RES model; REFTR_EVAL_METRICS=0 (or a
+    CPU device) runs the reference's per-image torch loop, without the new keys.
     `visualize` (needs the 'segm' post-processor, `output_dir` and a dataset with `split` / `pull_item`, as in the reference):
     per sample the predicted mask, the ground-truth mask, the image with both boxes and four attention maps under
     output_dir/vis/<split>/{mask,gt,bbox,att} (:86-96,157-192)."""
@@ -1194,8 +1228,13 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     model.eval()
     criterion.eval()
     board = utils.StatBoard()
-    sum_accu = torch.zeros((), device=device); sum_iou = torch.zeros((), device=device); cnt = torch.zeros((), device=device)
-    seg_iou = torch.zeros((), device=device); cnt_seg = 0.0
+    meter = None
+    if _metered(postprocessors, device):
+        from .metrics import EvalMeter
+        meter = EvalMeter(device, seg="segm" in postprocessors)
+    else:
+        sum_accu = torch.zeros((), device=device); sum_iou = torch.zeros((), device=device); cnt = torch.zeros((), device=device)
+        seg_iou = torch.zeros((), device=device); cnt_seg = 0.0
     results_dict = {}
     vis_dir = _vis_dirs(output_dir, data_loader.dataset.split) if visualize else None
     prefetcher = data_prefetcher(data_loader, device, prefetch=True)
@@ -1222,6 +1261,24 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
         board.add_device([f"{k}_unscaled" for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]))
         key = "orig_size" if "orig_size" in targets[0] else "size"
         orig_sizes = torch.stack([t[key] for t in targets], dim=0)
+        if meter is not None:
+            results_scaled = postprocessors["bbox"](outputs, orig_sizes, scale_to_original_shape=True)
+            for res, tg in zip(results_scaled, targets):         # the reference's check, on the post-processor's host counts
+                assert tg["boxes"].size(0) == res["boxes"].size(0), (res, tg["boxes"])
+            if "segm" in postprocessors:
+                target_sizes = torch.stack([t["size"] for t in targets], dim=0)
+                frame = postprocessors["segm"].frame(outputs, orig_sizes, target_sizes)
+                meter.update(outputs, targets, masks=frame[0], sizes=frame[2])
+                if vis_dir is not None:                          # the dumps alone need per-image views
+                    results = postprocessors["segm"].views([{} for _ in targets], frame)
+                    for i, (res, tg) in enumerate(zip(results, targets)):
+                        _dump_visuals(vis_dir, data_loader.dataset, int(tg["dataset_id"]), res["masks_origin"][0, 0],
+                                      results_scaled[i]["boxes"][0], outputs["mask_att"][i])
+            else:
+                meter.update(outputs, targets)
+            _fill_results(results_dict, targets, results_scaled)
+            samples, targets = prefetcher.next()
+            continue
         results = postprocessors["bbox"](outputs, orig_sizes)
         for res, tg in zip(results, targets):
             gt = box_cxcywh_to_xyxy(tg["boxes"])
@@ -1245,15 +1302,18 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     _check_cooperative(model)
     board.synchronize_between_processes()
     stats = board.global_avg()
-    if utils.is_dist_avail_and_initialized():
-        for t in (sum_accu, sum_iou, cnt):
-            torch.distributed.all_reduce(t)
-    stats["accuracy_iou0.5"] = float(sum_accu / cnt.clamp(min=1))
-    stats["miou"] = float(sum_iou / cnt.clamp(min=1))
-    if "segm" in postprocessors:
+    if meter is not None:
+        stats.update(meter.compute())
+    else:
         if utils.is_dist_avail_and_initialized():
-            torch.distributed.all_reduce(seg_iou)
-            cnt_seg = utils.get_world_size() * cnt_seg
-        stats["seg_miou"] = float(seg_iou / max(cnt_seg, 1.0))
+            for t in (sum_accu, sum_iou, cnt):
+                torch.distributed.all_reduce(t)
+        stats["accuracy_iou0.5"] = float(sum_accu / cnt.clamp(min=1))
+        stats["miou"] = float(sum_iou / cnt.clamp(min=1))
+        if "segm" in postprocessors:
+            if utils.is_dist_avail_and_initialized():
+                torch.distributed.all_reduce(seg_iou)
+                cnt_seg = utils.get_world_size() * cnt_seg
+            stats["seg_miou"] = float(seg_iou / max(cnt_seg, 1.0))
     stats = {k: v for k, v in stats.items() if k.split("_")[-1] not in ("unscaled", "0", "1", "2")}      # engine_vg.py:221
     return stats, results_dict

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2, 3
 _c_float_p = POINTER(c_float)
@@ -239,6 +239,13 @@ class MaskLossDesc(Structure):
                 ("lddp", c_int32), ("inv_norm", c_float), ("gbuf", c_void_p)]
 
 
+class EvalMetricsArgs(Structure):
+    _fields_ = [("pred_boxes", c_void_p), ("valid", c_void_p), ("table", c_void_p), ("masks", c_void_p), ("sizes", c_void_p),
+                ("partials", c_void_p), ("iou_det", c_void_p), ("iou_seg", c_void_p), ("iu", c_void_p), ("acc", c_void_p),
+                ("B", c_int32), ("P", c_int32), ("K", c_int32), ("Q", c_int32), ("max_h", c_int32), ("max_w", c_int32),
+                ("reset", c_int32)]
+
+
 DEC_MAX_LAYERS = 8
 
 
@@ -336,6 +343,7 @@ _SIGNATURES = {
     "rt_cem_bwd": (c_int, [POINTER(CemDesc), c_void_p]),
     "rt_mask_postprocess": (c_int, [POINTER(MaskPostDesc), c_void_p]),
     "rt_box_postprocess": (c_int, [POINTER(BoxPostDesc), c_void_p]),
+    "rt_eval_metrics": (c_int, [POINTER(EvalMetricsArgs), c_void_p]),
     "rt_small_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rt_pos_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rt_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1204,6 +1212,37 @@ def box_postprocess(boxes, valid_u8, sizes_f32=None):
     return out, counts
 
 
+# rt_eval_metrics: accumulator slots (8 bytes each: int64 but for the two double sums) and the mask kernel's pixels per workgroup
+(EVAL_DET_N, EVAL_DET_HIT, EVAL_SEG_N, EVAL_SEG_HIT, EVAL_SEG_I, EVAL_SEG_U, EVAL_DET_SUM, EVAL_SEG_SUM, EVAL_SLOTS) = (
+    0, 1, 6, 7, 12, 13, 14, 15, 16)
+EVAL_CHUNK = 16384
+
+
+def eval_metrics(pred_boxes, valid_u8, table, acc, masks=None, sizes_i32=None, reset=False):
+    """rt_eval_metrics for one batch: pred_boxes fp32 [B, P, K, 4] cxcywh, valid uint8 [B, P, K], table device int64 [B, 5] =
+    {target boxes pointer, n_b, target mask pointer | 0, mask height, mask width}, acc device int64 [EVAL_SLOTS] (slots
+    EVAL_DET_SUM / EVAL_SEG_SUM hold doubles), updated in place -- from zero when `reset`.  masks uint8 [B, Q, max_h, max_w] (what
+    mask_postprocess returned) + sizes_i32 device int32 [B, 2] add the mask part (query 0 of every image).
+    Returns (iou_det fp32 [B, P], iou_seg fp32 [B] | None, iu int64 [B, 2] | None) of this batch."""
+    B, P, K, _ = pred_boxes.shape
+    _req(pred_boxes, torch.float32, "pred_boxes"); _req(valid_u8, torch.uint8, "valid"); _req(table, torch.int64, "table")
+    _req(acc, torch.int64, "acc"); _req(masks, torch.uint8, "masks"); _req(sizes_i32, torch.int32, "sizes")
+    assert tuple(valid_u8.shape) == (B, P, K) and tuple(table.shape) == (B, 5) and acc.numel() == EVAL_SLOTS
+    iou_det = _new((B, P), torch.float32, pred_boxes)
+    Q = max_h = max_w = 0
+    partials = iou_seg = iu = None
+    if masks is not None:
+        assert sizes_i32 is not None and masks.dim() == 4 and masks.shape[0] == B and tuple(sizes_i32.shape) == (B, 2)
+        Q, max_h, max_w = (int(v) for v in masks.shape[1:])
+        partials = _new((B, max(1, -(-(max_h * max_w) // EVAL_CHUNK)), 2), torch.int32, pred_boxes)
+        iou_seg = _new((B,), torch.float32, pred_boxes)
+        iu = _new((B, 2), torch.int64, pred_boxes)
+    a = EvalMetricsArgs(_p(pred_boxes), _p(valid_u8), _p(table), _p(masks), _p(sizes_i32), _p(partials), _p(iou_det), _p(iou_seg),
+                        _p(iu), _p(acc), B, P, K, Q, max_h, max_w, 1 if reset else 0)
+    _check(lib().rt_eval_metrics(ctypes.byref(a), _stream()), "rt_eval_metrics")
+    return iou_det, iou_seg, iu
+
+
 def zero_chunks(base, table, n):
     """Clears n chunks {element offset, count} (static device int64 table) of the fp32 buffer `base` in one launch."""
     _req(base, torch.float32, "base"); _req(table, torch.int64, "table")
@@ -1548,6 +1587,9 @@ def seg_concat(src, mem, out, B, HW, E, nh, rows_per_img, row_off, src_dense=Fal
     return out
 
 
+MASK_LOSS_PARTIALS = 1024
+
+
 def mask_loss(pred, target_u8, B, h, w, Ht, Wt, ldp, norm, sums=None, dpred=None, g_focal=None, g_dice=None):
     """Forward (dpred None): returns (losses[2] = {focal, dice}, sums [B,4]).  Backward: accumulates into dpred."""
     _req(pred, torch.float32, "pred"); _req(target_u8, torch.uint8, "target")
@@ -1555,7 +1597,8 @@ def mask_loss(pred, target_u8, B, h, w, Ht, Wt, ldp, norm, sums=None, dpred=None
     if dpred is None:
         sums = torch.empty((B, 4), dtype=torch.float32, device=pred.device)
         losses = torch.empty(2, dtype=torch.float32, device=pred.device)
-        d = MaskLossDesc(_p(pred), _p(target_u8), _p(sums), _p(losses), None, None, None, B, h, w, Ht, Wt, ldp, 0, 1.0 / norm, None)
+        partials = torch.empty((B, MASK_LOSS_PARTIALS), dtype=torch.float32, device=pred.device)      # fixed-order sums: no atomics
+        d = MaskLossDesc(_p(pred), _p(target_u8), _p(sums), _p(losses), None, None, None, B, h, w, Ht, Wt, ldp, 0, 1.0 / norm, _p(partials))
         _check(lib().rt_mask_loss(ctypes.byref(d), _stream()), "rt_mask_loss")
         return losses, sums
     _req(dpred, torch.float32, "dpred"); _req(g_focal, torch.float32, "g_focal"); _req(g_dice, torch.float32, "g_dice")

@@ -44,7 +44,10 @@ class PostProcessSegm(nn.Module):
         self.threshold = threshold
 
     @torch.no_grad()
-    def forward(self, results, outputs, orig_target_sizes, max_target_sizes):
+    def frame(self, outputs, orig_target_sizes, max_target_sizes):
+        """The kernel launch of forward() without the per-image views: (masks uint8 [B, Q, max_h, max_w], packed uint8 masks_origin,
+        sizes, orig, off) -- sizes / orig the per-image (h, w) as python ints, off the images' offsets into `packed`.  What
+        metrics.EvalMeter scores (it reads the frame inside every image's own [:img_h, :img_w] only)."""
         assert len(orig_target_sizes) == len(max_target_sizes)
         pm = outputs["pred_masks"]
         if pm.dim() == 5:
@@ -61,8 +64,19 @@ class PostProcessSegm(nn.Module):
         masks, packed = H.mask_postprocess(pm, table[:2 * B].view(B, 2), (max_h, max_w), self.threshold,
                                            orig_i32=table[2 * B:].view(B, 2), origin_off=torch.tensor(off, dtype=torch.int64).to(dev),
                                            origin_total=off[-1], max_origin=max(oh * ow for oh, ow in orig))
+        return masks, packed, sizes, orig, off
+
+    @staticmethod
+    def views(results, frame):
+        """results[i]['masks'] / ['masks_origin'] as views into what frame() returned."""
+        masks, packed, sizes, orig, off = frame
+        Q = masks.shape[1]
         masks = masks.view(torch.bool)
         for i, ((ih, iw), (oh, ow)) in enumerate(zip(sizes, orig)):
             results[i]["masks"] = masks[i, :, :ih, :iw].unsqueeze(1)
             results[i]["masks_origin"] = packed[off[i]:off[i + 1]].view(Q, 1, oh, ow)
         return results
+
+    @torch.no_grad()
+    def forward(self, results, outputs, orig_target_sizes, max_target_sizes):
+        return self.views(results, self.frame(outputs, orig_target_sizes, max_target_sizes))
