@@ -14,7 +14,7 @@ def load(d):
         if len(r) > len(rows):
             rows = r
     # the timed region: the last 10 steps = the last 10 step-ending kernels back to the 11th-last
-    ends = [i for i, r in enumerate(rows) if "finish_stats_kernel" in r[0] or "finish_step_kernel" in r[0]]
+    ends = [i for i, r in enumerate(rows) if "finish_stats_kernel" in r[0]]      # (rt_finish_step launches it too)
     print(d, len(rows), "dispatches,", len(ends), "step ends", file=sys.stderr)
     a, b = ends[-11] + 1, ends[-1] + 1
     agg = collections.defaultdict(lambda: [0, 0.0])

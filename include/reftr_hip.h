@@ -638,8 +638,9 @@ int rt_finish_stats(const rt_finish_desc* d, rt_stream_t stream);
  * kernel the measurement tools capture into the step's graph at phase boundaries of every stream (tools/concurrent_timeline.py),
  * because rocprofv3 serialises the graph's concurrent streams. */
 int rt_stamp(uint64_t* buf, int idx, rt_stream_t stream);
-/* rt_adamw_mat / rt_adamw_chunks — rt_adamw_flat's update (same descriptor, same arithmetic and rounding, same `active` / step /
- * learning-rate device words), split into (a) the weight MATRICES, walked in tiles of 32 rows x 256 columns of [N][T*C] so that the kernel also writes the bf16
+/* rt_adamw_mat / rt_adamw_chunks — rt_adamw_flat's update (same descriptor, same arithmetic -- one definition in rt_optim.hip -- same
+ * `active` / step / learning-rate device words; which products of the moment updates are fused into their adds differs between the
+ * three kernels, so they agree to an ulp, not bit for bit: profiles/optim_unify_bits.txt), split into (a) the weight MATRICES, walked in tiles of 32 rows x 256 columns of [N][T*C] so that the kernel also writes the bf16
  * GEMM operands of the NEXT forward / backward from the registers that hold the new fp32 values -- what rt_weight_prep_batched
  * produced in a second pass over the masters -- and (b) everything else (biases, norm parameters, embeddings), in chunks.
  *   mat table (DEVICE int64 [njobs][8], static): {element offset of the matrix [N][T][C] in p / g / m / v, scale pointer | 0

@@ -249,12 +249,7 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const float* __restric
 // element-wise path of the same tile.
 __global__ __launch_bounds__(256) void weight_prep_batched_kernel(const int64_t* __restrict__ table, int njobs) {
     __shared__ float tile[64][65];
-    int lo = 0, hi = njobs - 1;                       // last job whose first_tile <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid * 8 + 7] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* j = table + lo * 8;
+    const int64_t* j = table + rt_job_of(table, njobs, blockIdx.x) * 8;
     const float* src = reinterpret_cast<const float*>(j[0]);
     const float* scale = reinterpret_cast<const float*>(j[1]);
     bf16_t* dst = reinterpret_cast<bf16_t*>(j[2]);

@@ -127,6 +127,31 @@ __device__ __forceinline__ int rt_map_row(int r, int grp_rows, int grp_stride, i
     return r;
 }
 
+// "Last job whose first tile <= b" of a launch that serves several jobs: first[j] = the first workgroup of job j (ascending, n >= 1)
+__device__ __forceinline__ int rt_job_of(const int* first, int n, int b) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (first[mid] <= b) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+// ... of the int64 [njobs][8] job tables in device memory (rt_weight_prep_batched, rt_adamw_mat): word 7 of a row is its first tile
+__device__ __forceinline__ int rt_job_of(const int64_t* table, int n, int64_t b) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (table[mid * 8 + 7] <= b) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// One workgroup of 256 threads over chunk blockIdx.x of a device table of {int64 element offset, int64 count}: vec4(e) for every four
+// elements e .. e + 3 inside the chunk whose e is a multiple of 4 (16-byte accesses are allowed), one(e) for each of the others -- a
+// ragged end, or the whole chunk when its offset is not a multiple of 4.  ALIGNED: the table promises multiples of 4 (one() is dead).
+template <bool ALIGNED, class V, class S>
+__device__ __forceinline__ void rt_chunk_walk(const int64_t* __restrict__ table, V vec4, S one) {
+    const size_t off = (size_t)table[2 * blockIdx.x], cnt = (size_t)table[2 * blockIdx.x + 1];
+    for (size_t i = threadIdx.x * 4; i < cnt; i += 1024) {
+        if (ALIGNED || (i + 4 <= cnt && ((off + i) & 3) == 0)) vec4(off + i);
+        else for (size_t k = i; k < cnt && k < i + 4; ++k) one(off + k);
+    }
+}
+
 // Small fp32 workspaces are cleared with a KERNEL, not hipMemsetAsync: inside a captured hipGraph (ROCm 7.2) memset
 // nodes were observed to race with the kernel nodes that follow them (intermittent garbage statistics / losses),
 // while kernel -> kernel ordering on the captured stream is reliable.
@@ -178,11 +203,11 @@ template <class T>
 __device__ __forceinline__ float rt_wg_commit(T a, T* o, bf16_t* twin, bool accumulate) {
     return rt_wg_commit(a, accumulate ? *o : a, o, twin, accumulate);
 }
-// sign * |buf|^2 of up to 32 fp32 buffers into the slots (the producers without an in-kernel contribution: a pass with sign -1
-// in front of an accumulating launch, +1 behind every launch); rt_optim.hip
+// sign * |buf|^2 of n <= 32 fp32 buffers into the slots, one launch (the producers without an in-kernel contribution: a pass with
+// sign -1 in front of an accumulating launch, +1 behind every launch); more than 32: RT_ERR_BADARG, the caller batches; rt_optim.hip
 int rt_sq_pass(float* const* bufs, const long long* counts, const float* signs, int n, float* slots, hipStream_t s);
-// twin[i] = bf16(buf[i]) for up to any number of fp32 buffers (the bf16 exchange twins of weight gradients whose producer has no
-// in-kernel twin store); rt_optim.hip
+// twin[i] = bf16(buf[i]) for n <= 32 fp32 buffers, one launch (the bf16 exchange twins of weight gradients whose producer has no
+// in-kernel twin store); more than 32: RT_ERR_BADARG; rt_optim.hip
 int rt_round_pass(float* const* bufs, void* const* twins, const long long* counts, int n, hipStream_t s);
 
 #define RT_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)

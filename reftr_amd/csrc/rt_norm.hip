@@ -362,8 +362,7 @@ struct LnPgJobs { rt_ln_pg_job j[64]; int first[65]; int n; };
 // one workgroup = 64 channels of one job x 4 row lanes (4 loads in flight each), combined through LDS
 __global__ __launch_bounds__(256) void ln_param_grad_grouped_kernel(const LnPgJobs p) {
     __shared__ float red[2][3][64];
-    int lo = 0, hi = p.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (p.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const int lo = rt_job_of(p.first, p.n, (int)blockIdx.x);
     const rt_ln_pg_job& q = p.j[lo];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int c = ((int)blockIdx.x - p.first[lo]) * 64 + tx;

@@ -8,142 +8,43 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ g, size_t n, float* __restrict__ out) {
+// s + |v|^2, summed in the order each element type's norm has always used (the order is part of the result's bits)
+__device__ __forceinline__ float sq_add(float s, f32x4 v) { return s + (v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]); }
+__device__ __forceinline__ float sq_add(float s, bf16x8 v) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { const float f = (float)v[c]; s += f * f; }
+    return s;
+}
+// T = float (V = f32x4) or bf16_t (V = bf16x8): 16-byte loads, the ragged tail one element at a time, one atomic per workgroup
+template <class T, class V>
+__global__ __launch_bounds__(256) void sqnorm_kernel(const T* __restrict__ g, size_t n, float* __restrict__ out) {
+    constexpr int W = sizeof(V) / sizeof(T);
     __shared__ float sm[16];
     float s = 0.f;
-    const size_t n4 = n >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(g);
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const float4 v = g4[i];
-        s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    }
-    for (size_t i = (n4 << 2) + blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s += g[i] * g[i];
+    const size_t nv = n / W;
+    const V* gv = reinterpret_cast<const V*>(g);
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nv; i += (size_t)gridDim.x * 256) s = sq_add(s, gv[i]);
+    for (size_t i = nv * W + blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float f = (float)g[i]; s += f * f; }
     s = rt_block_sum(s, sm);
     if (threadIdx.x == 0) atomicAdd(out, s);
 }
 
-__global__ __launch_bounds__(256) void sqnorm_bf16_kernel(const bf16_t* __restrict__ g, size_t n, float* __restrict__ out) {
-    __shared__ float sm[16];
-    float s = 0.f;
-    const size_t n8 = n >> 3;
-    const bf16x8* g8 = reinterpret_cast<const bf16x8*>(g);
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-        const bf16x8 v = g8[i];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) { const float f = (float)v[c]; s += f * f; }
-    }
-    for (size_t i = (n8 << 3) + blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float f = (float)g[i]; s += f * f; }
-    s = rt_block_sum(s, sm);
-    if (threadIdx.x == 0) atomicAdd(out, s);
-}
-
-__global__ __launch_bounds__(256) void adamw_kernel(const rt_adamw_desc p, const int nontemporal) {
-    if (p.active && p.active[0] == 0) return;
-    const float total = sqrtf(p.gnorm_sq ? p.gnorm_sq[0] : 0.f) * p.grad_scale;
-    float coef = 1.f;
-    if (p.max_norm > 0.f) coef = fminf(1.f, p.max_norm / (total + 1e-6f));
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.gnorm_out) p.gnorm_out[0] = total;
-    const float gs = p.grad_scale * coef;
-    const int step = p.step_dev ? p.step_dev[0] : p.step;
-    const float bc1 = 1.f - powf(p.beta1, (float)step);
-    const float bc2 = 1.f - powf(p.beta2, (float)step);
-    const float inv_sqrt_bc2 = rsqrtf(bc2);
-    const size_t i0 = (size_t)p.span_begin >> 2, n4 = (size_t)p.span_end >> 2;
-    float4* P4 = reinterpret_cast<float4*>(p.p);
-    const float4* G4 = reinterpret_cast<const float4*>(p.g);
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-    const bf16x4_t* G16 = reinterpret_cast<const bf16x4_t*>(p.g16);
-    float4* M4 = reinterpret_cast<float4*>(p.m);
-    float4* V4 = reinterpret_cast<float4*>(p.v);
-    for (size_t i = i0 + blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const size_t e = i << 2;
-        float lr = 0.f, wd = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r < p.n_ranges && e >= (size_t)p.range_begin[r] && e < (size_t)p.range_end[r]) {
-                lr = p.lr_dev ? p.lr_dev[r] : p.range_lr[r]; wd = p.range_wd[r];
-            }
-        float4 pv, gv, mv, vv;
-        if (nontemporal) {         // streamed once per step: do not displace the activations / operands in L2 and the MALL
-            auto ntl = [](const float4* q) __attribute__((always_inline)) {
-                const f32x4 t4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
-                return make_float4(t4[0], t4[1], t4[2], t4[3]);
-            };
-            pv = ntl(P4 + i); mv = ntl(M4 + i); vv = ntl(V4 + i);
-            if (!G16) gv = ntl(G4 + i);
-        } else { pv = P4[i]; mv = M4[i]; vv = V4[i]; if (!G16) gv = G4[i]; }
-        if (G16) { const bf16x4_t h = __builtin_nontemporal_load(G16 + i); gv = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]); }
-        float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float g = gp[c] * gs;
-            pp[c] *= (1.f - lr * wd);
-            mp[c] = p.beta1 * mp[c] + (1.f - p.beta1) * g;
-            vp[c] = p.beta2 * vp[c] + (1.f - p.beta2) * g * g;
-            const float denom = sqrtf(vp[c]) * inv_sqrt_bc2 + p.eps;
-            pp[c] -= (lr / bc1) * (mp[c] / denom);
-        }
-        if (nontemporal) { P4[i] = pv; __builtin_nontemporal_store(f32x4{mv.x, mv.y, mv.z, mv.w}, reinterpret_cast<f32x4*>(M4 + i)); __builtin_nontemporal_store(f32x4{vv.x, vv.y, vv.z, vv.w}, reinterpret_cast<f32x4*>(V4 + i)); }
-        else { P4[i] = pv; M4[i] = mv; V4[i] = vv; }
-    }
-}
-
-// torch.optim.SGD(momentum, weight_decay) as the reference builds it with --sgd (main_vg.py:263-265: momentum 0.9, dampening 0, no
-// Nesterov): g' = clip * scale * g + wd * p;  buf = momentum * buf + g'  (a zero-initialised buffer makes step 1 "buf = g'");
-// p -= lr * buf.  Same descriptor as AdamW: m = momentum buffer, beta1 = momentum, v / beta2 / eps unused.  20 B per parameter.
-__global__ __launch_bounds__(256) void sgd_kernel(const rt_adamw_desc p) {
-    if (p.active && p.active[0] == 0) return;
-    const float total = sqrtf(p.gnorm_sq ? p.gnorm_sq[0] : 0.f) * p.grad_scale;
-    float coef = 1.f;
-    if (p.max_norm > 0.f) coef = fminf(1.f, p.max_norm / (total + 1e-6f));
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.gnorm_out) p.gnorm_out[0] = total;
-    const float gs = p.grad_scale * coef;
-    const size_t i0 = (size_t)p.span_begin >> 2, n4 = (size_t)p.span_end >> 2;
-    float4* P4 = reinterpret_cast<float4*>(p.p);
-    const float4* G4 = reinterpret_cast<const float4*>(p.g);
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-    const bf16x4_t* G16 = reinterpret_cast<const bf16x4_t*>(p.g16);
-    float4* M4 = reinterpret_cast<float4*>(p.m);
-    for (size_t i = i0 + blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const size_t e = i << 2;
-        float lr = 0.f, wd = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (r < p.n_ranges && e >= (size_t)p.range_begin[r] && e < (size_t)p.range_end[r]) {
-                lr = p.lr_dev ? p.lr_dev[r] : p.range_lr[r]; wd = p.range_wd[r];
-            }
-        float4 pv = P4[i], mv = M4[i], gv;
-        if (G16) { const bf16x4_t h = G16[i]; gv = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]); }
-        else gv = G4[i];
-        float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float g = gp[c] * gs + wd * pp[c];
-            mp[c] = p.beta1 * mp[c] + g;
-            pp[c] -= lr * mp[c];
-        }
-        P4[i] = pv; M4[i] = mv;
-    }
-}
-
-__global__ void counter_add_kernel(int32_t* c, int32_t inc) { c[0] += inc; }
-
-// ------------------------------------------------------------------------------------------------
-// Matrix-aware AdamW (round 4): the same update, walked per WEIGHT MATRIX in 64(n) x 64(c) tiles per tap, so that the kernel that
-// produces the new fp32 master also emits the bf16 GEMM operands the next forward / backward read -- W [N][T][C] (x FrozenBN scale)
-// and its transpose [C][T][N] -- while the new values are still in registers.  The separate operand refresh (rt_weight_prep_batched:
-// re-reads 4 B per parameter, one more dependent launch at the head of the step) disappears; arithmetic and rounding points are
-// those of adamw_kernel followed by weight_prep_batched_kernel, bit for bit.  Everything that is not a matrix job (biases, norm
-// parameters, embeddings) is updated by adamw_chunks_kernel over a static chunk table (the complement of the jobs).
+// ---- what every update kernel shares: the launch's coefficients, the range lookup, the gradient load, one rule per optimizer
+// and the four-element step.  The flat, the chunk and the matrix kernels all call adam_elem: one definition of the arithmetic,
+// inlined into three loops, each of which keeps the rounding it had (profiles/optim_unify_bits.txt).
 struct AdamCoef { float gs, bc1, inv_sqrt_bc2; };
-__device__ __forceinline__ AdamCoef adam_coef(const rt_adamw_desc& p) {
+// grad_scale x clip coefficient (clip_grad_norm_: skipped when max_norm <= 0); the launch's first thread stores the total norm
+__device__ __forceinline__ float clip_scale(const rt_adamw_desc& p) {
     const float total = sqrtf(p.gnorm_sq ? p.gnorm_sq[0] : 0.f) * p.grad_scale;
     float coef = 1.f;
     if (p.max_norm > 0.f) coef = fminf(1.f, p.max_norm / (total + 1e-6f));
     if (blockIdx.x == 0 && threadIdx.x == 0 && p.gnorm_out) p.gnorm_out[0] = total;
-    const int step = p.step_dev ? p.step_dev[0] : p.step;
+    return p.grad_scale * coef;
+}
+__device__ __forceinline__ AdamCoef adam_coef(const rt_adamw_desc& p) {
     AdamCoef c;
-    c.gs = p.grad_scale * coef;
+    c.gs = clip_scale(p);
+    const int step = p.step_dev ? p.step_dev[0] : p.step;
     c.bc1 = 1.f - powf(p.beta1, (float)step);
     c.inv_sqrt_bc2 = rsqrtf(1.f - powf(p.beta2, (float)step));
     return c;
@@ -156,16 +57,98 @@ __device__ __forceinline__ void adam_range(const rt_adamw_desc& p, size_t e, flo
             lr = p.lr_dev ? p.lr_dev[r] : p.range_lr[r]; wd = p.range_wd[r];
         }
 }
-// the update of one element, written exactly as in adamw_kernel (same operation order: the two kernels must round alike)
+// NT: streamed once per step -- do not displace the activations / operands in L2 and the MALL
+template <bool NT>
+__device__ __forceinline__ f32x4 ld4(const float* q) {
+    const f32x4* q4 = reinterpret_cast<const f32x4*>(q);
+    return NT ? __builtin_nontemporal_load(q4) : *q4;
+}
+template <bool NT>
+__device__ __forceinline__ void st4(float* q, f32x4 v) {
+    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(q)); else *reinterpret_cast<f32x4*>(q) = v;
+}
+// the four gradients at element e (a multiple of 4): from g (policy NT), or from its bf16 twin g16 (policy NT16) when the descriptor has one
+template <bool NT, bool NT16>
+__device__ __forceinline__ f32x4 grad4(const float* g, const bf16_t* g16, size_t e) {
+    if (g16) {
+        const bf16x4* q = reinterpret_cast<const bf16x4*>(g16 + e);
+        const bf16x4 h = NT16 ? __builtin_nontemporal_load(q) : *q;
+        return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    } else return ld4<NT>(g + e);
+}
+// AdamW with decoupled weight decay: the update of one element, the ONLY statement of this arithmetic.  What the plain text does not
+// fix is which products the compiler fuses into the adds (fp-contract): that depends on the loop it is inlined into, and the
+// kernels have always differed in it by an ulp -- the chunk kernel rounds m = fma(b1, m, (1 - b1) g), adamw_mat_kernel
+// m = fma(1 - b1, g, b1 m), its element-wise path adds the two rounded products of v.  Those two keep the plain text and, with it, their
+// bits.  FLAT is the flat pass: sharing the chunk kernel's step it would take over the chunk kernel's rounding, so the rounding its
+// own loop had -- m = fma(1 - b1, g, b1 m), v = fma(g, (1 - b2) g, b2 v) -- is written out (profiles/optim_unify_bits.txt).
+template <bool FLAT = false>
 __device__ __forceinline__ void adam_elem(const rt_adamw_desc& p, const AdamCoef& c, float lr, float wd, float graw, float& pv, float& mv, float& vv) {
     const float g = graw * c.gs;
-    pv *= (1.f - lr * wd);
-    mv = p.beta1 * mv + (1.f - p.beta1) * g;
-    vv = p.beta2 * vv + (1.f - p.beta2) * g * g;
-    const float denom = sqrtf(vv) * c.inv_sqrt_bc2 + p.eps;
-    pv -= (lr / c.bc1) * (mv / denom);
+    if (FLAT) {
+#pragma clang fp contract(off)
+        mv = __builtin_fmaf(1.f - p.beta1, g, p.beta1 * mv);
+        vv = __builtin_fmaf(g, (1.f - p.beta2) * g, p.beta2 * vv);
+        const float denom = __builtin_fmaf(sqrtf(vv), c.inv_sqrt_bc2, p.eps);
+        pv = __builtin_fmaf(__builtin_fmaf(-lr, wd, 1.f), pv, -((lr / c.bc1) * (mv / denom)));
+    } else {
+        pv *= (1.f - lr * wd);
+        mv = p.beta1 * mv + (1.f - p.beta1) * g;
+        vv = p.beta2 * vv + (1.f - p.beta2) * g * g;
+        const float denom = sqrtf(vv) * c.inv_sqrt_bc2 + p.eps;
+        pv -= (lr / c.bc1) * (mv / denom);
+    }
+}
+// torch.optim.SGD(momentum, weight_decay) as the reference builds it with --sgd (main_vg.py:263-265: momentum 0.9, dampening 0, no
+// Nesterov): g' = clip * scale * g + wd * p;  buf = momentum * buf + g'  (a zero-initialised buffer makes step 1 "buf = g'");
+// p -= lr * buf.  Same descriptor as AdamW: m = momentum buffer, beta1 = momentum, v / beta2 / eps unused.  20 B per parameter.
+// One kernel only, so its fused multiply-adds are written out (wd * p is the product that is rounded on its own).
+__device__ __forceinline__ void sgd_elem(const rt_adamw_desc& p, const AdamCoef& c, float lr, float wd, float graw, float& pv, float& mv) {
+#pragma clang fp contract(off)
+    mv = __builtin_fmaf(p.beta1, mv, __builtin_fmaf(graw, c.gs, wd * pv));
+    pv = __builtin_fmaf(-lr, mv, pv);
+}
+// the rule of a four-element step: AdamW as the chunk kernel applies it, AdamW as the flat pass rounds it, SGD
+enum { RULE_ADAMW, RULE_ADAMW_FLAT, RULE_SGD };
+template <int RULE>
+__device__ __forceinline__ AdamCoef opt_coef(const rt_adamw_desc& p) { return RULE == RULE_SGD ? AdamCoef{clip_scale(p), 1.f, 1.f} : adam_coef(p); }
+// the four elements at e: load p / m / v / g, apply the rule, store (NT: m, v and g both ways and the load of p; p is stored plain;
+// the flat AdamW pass reads the bf16 twin non-temporally under either policy, as it always has)
+template <int RULE, bool NT>
+__device__ __forceinline__ void opt_step4(const rt_adamw_desc& p, const AdamCoef& cf, size_t e) {
+    constexpr bool SGD = RULE == RULE_SGD;
+    float lr, wd;
+    adam_range(p, e, lr, wd);
+    f32x4 pv = ld4<NT>(p.p + e), mv = ld4<NT>(p.m + e), vv = {0.f, 0.f, 0.f, 0.f};
+    if (!SGD) vv = ld4<NT>(p.v + e);
+    const f32x4 gv = grad4<NT, NT || RULE == RULE_ADAMW_FLAT>(p.g, reinterpret_cast<const bf16_t*>(p.g16), e);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float a = pv[c], b = mv[c], d = vv[c];
+        if (SGD) sgd_elem(p, cf, lr, wd, gv[c], a, b); else adam_elem<RULE == RULE_ADAMW_FLAT>(p, cf, lr, wd, gv[c], a, b, d);
+        pv[c] = a; mv[c] = b; vv[c] = d;
+    }
+    st4<false>(p.p + e, pv); st4<NT>(p.m + e, mv);
+    if (!SGD) st4<NT>(p.v + e, vv);
 }
 
+// rt_adamw_flat (RULE_ADAMW_FLAT) and rt_sgd_flat (RULE_SGD): the rule over the span [span_begin, span_end), grid-strided.  Both rules
+// keep this name, because the trace tools find the update by it: in a trace, adamw_kernel<2, false> is SGD.
+template <int RULE, bool NT>
+__global__ __launch_bounds__(256) void adamw_kernel(const rt_adamw_desc p) {
+    if (p.active && p.active[0] == 0) return;
+    const AdamCoef cf = opt_coef<RULE>(p);
+    const size_t i0 = (size_t)p.span_begin >> 2, n4 = (size_t)p.span_end >> 2;
+    for (size_t i = i0 + blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) opt_step4<RULE, NT>(p, cf, i << 2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Matrix-aware AdamW (round 4): the same update, walked per WEIGHT MATRIX in 64(n) x 64(c) tiles per tap, so that the kernel that
+// produces the new fp32 master also emits the bf16 GEMM operands the next forward / backward read -- W [N][T][C] (x FrozenBN scale)
+// and its transpose [C][T][N] -- while the new values are still in registers.  The separate operand refresh (rt_weight_prep_batched:
+// re-reads 4 B per parameter, one more dependent launch at the head of the step) disappears; the arithmetic is adam_elem, the
+// rounding points of the operands those of weight_prep_batched_kernel.  Everything that is not a matrix job (biases, norm
+// parameters, embeddings) is updated by adamw_chunks_kernel over a static chunk table (the complement of the jobs).
 // table: int64 [njobs][8] = {element offset of the matrix in p/g/m/v, scale ptr | 0, dst ptr | 0, dst_t ptr | 0, N, T, C, first tile}
 // A matrix [N][T][C] is walked as the 2-D array [N][K'] (K' = T * C: a row is contiguous) in tiles of 32 rows x 256 columns: a wave
 // reads / writes ONE KB-contiguous row piece per instruction in each of p, g, m, v (the first version used 64 x 64 tiles -- 256-byte
@@ -177,12 +160,7 @@ __global__ __launch_bounds__(256) void adamw_mat_kernel(const rt_adamw_desc p, c
     if (p.active && p.active[0] == 0) return;
     __shared__ __attribute__((aligned(16))) bf16_t tile[AM_TN][AM_LD];
     const AdamCoef cf = adam_coef(p);
-    int lo = 0, hi = njobs - 1;                       // last job whose first_tile <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (table[mid * 8 + 7] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const int64_t* j = table + lo * 8;
+    const int64_t* j = table + rt_job_of(table, njobs, blockIdx.x) * 8;
     const size_t base = (size_t)j[0];
     bf16_t* dst = reinterpret_cast<bf16_t*>(j[2]);
     bf16_t* dst_t = reinterpret_cast<bf16_t*>(j[3]);
@@ -204,7 +182,6 @@ __global__ __launch_bounds__(256) void adamw_mat_kernel(const rt_adamw_desc p, c
     float* P = p.p + base; float* Mo = p.m + base; float* Vo = p.v + base;
     const float* G = p.g ? p.g + base : nullptr;
     const bf16_t* G16 = p.g16 ? reinterpret_cast<const bf16_t*>(p.g16) + base : nullptr;
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
     const int t = threadIdx.x;
     const bool vec = (K & 3) == 0 && (base & 3) == 0 && (!dst || ((uintptr_t)dst & 7) == 0);
     if (vec) {
@@ -218,10 +195,10 @@ __global__ __launch_bounds__(256) void adamw_mat_kernel(const rt_adamw_desc p, c
             for (int jj = 0; jj < 4; ++jj) {
                 const int n = n0 + (half * 4 + jj) * 4 + r;
                 ok[jj] = n < N && k < K;
-                if (ok[jj]) {
+                if (ok[jj]) {                       // (not grad4: inlined here it costs the kernel 60 VGPRs and an occupancy step)
                     const size_t o = (size_t)n * K + k;
                     if (G16) {
-                        const bf16x4_t h = __builtin_nontemporal_load(reinterpret_cast<const bf16x4_t*>(G16 + o));
+                        const bf16x4 h = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(G16 + o));
                         gv[jj] = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
                     } else gv[jj] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(G + o));
                 }
@@ -249,7 +226,7 @@ __global__ __launch_bounds__(256) void adamw_mat_kernel(const rt_adamw_desc p, c
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) {
                 const int nl = (half * 4 + jj) * 4 + r, n = n0 + nl;
-                bf16x4_t ov = bf16x4_t{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+                bf16x4 ov = bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
                 if (ok[jj]) {
                     const size_t o = (size_t)n * K + k;
 #pragma unroll
@@ -267,9 +244,9 @@ __global__ __launch_bounds__(256) void adamw_mat_kernel(const rt_adamw_desc p, c
                     const float sc = scale ? scale[n] : 1.f;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) ov[e] = (bf16_t)(scale ? pv[jj][e] * sc : pv[jj][e]);
-                    if (dst) *reinterpret_cast<bf16x4_t*>(dst + o) = ov;
+                    if (dst) *reinterpret_cast<bf16x4*>(dst + o) = ov;
                 }
-                if (dst_t) *reinterpret_cast<bf16x4_t*>(&tile[nl][q]) = ov;
+                if (dst_t) *reinterpret_cast<bf16x4*>(&tile[nl][q]) = ov;
             }
         }
     } else {                                          // ragged / misaligned matrices: element-wise over the same tile
@@ -313,49 +290,48 @@ __global__ __launch_bounds__(256) void adamw_mat_kernel(const rt_adamw_desc p, c
 __global__ __launch_bounds__(256) void adamw_chunks_kernel(const rt_adamw_desc p, const int64_t* __restrict__ table) {
     if (p.active && p.active[0] == 0) return;
     const AdamCoef cf = adam_coef(p);
-    const size_t off = (size_t)table[2 * blockIdx.x], cnt = (size_t)table[2 * blockIdx.x + 1];
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-    for (size_t i = threadIdx.x * 4; i < cnt; i += 1024) {
-        const size_t e = off + i;
-        float lr, wd;
-        adam_range(p, e, lr, wd);
-        f32x4 pv = *reinterpret_cast<const f32x4*>(p.p + e), mv = *reinterpret_cast<const f32x4*>(p.m + e), vv = *reinterpret_cast<const f32x4*>(p.v + e), gv;
-        if (p.g16) { const bf16x4_t h = *reinterpret_cast<const bf16x4_t*>(reinterpret_cast<const bf16_t*>(p.g16) + e); gv = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]}; }
-        else gv = *reinterpret_cast<const f32x4*>(p.g + e);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { float a = pv[c], b = mv[c], d = vv[c]; adam_elem(p, cf, lr, wd, gv[c], a, b, d); pv[c] = a; mv[c] = b; vv[c] = d; }
-        *reinterpret_cast<f32x4*>(p.p + e) = pv; *reinterpret_cast<f32x4*>(p.m + e) = mv; *reinterpret_cast<f32x4*>(p.v + e) = vv;
-    }
+    rt_chunk_walk<true>(table, [&](size_t e) { opt_step4<RULE_ADAMW, false>(p, cf, e); }, [](size_t) {});
 }
 
 // ---- gradient-norm accumulator (rt_common.h): passes over whole buffers / chunk tables, and the final sum of the slots
+// A pass over up to 32 whole buffers (rt_sq_pass, rt_round_pass; L = SqList or RoundList): first[b] = the first workgroup of buffer
+// b, 4096 elements per workgroup.  list_buffer finds the workgroup's buffer b; list_walk calls vec4(i) for every four elements
+// i .. i + 3 of the workgroup's piece that the buffer still holds, one(k) for the elements of a ragged tail.
 struct SqList { const float* buf[32]; long long cnt[32]; float sign[32]; int first[33]; int n; };
-__global__ __launch_bounds__(256) void sq_list_kernel(const SqList l, float* __restrict__ slots) {
-    __shared__ float sm[16];
-    int lo = 0, hi = l.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (l.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const float* g = l.buf[lo];
-    const size_t n = (size_t)l.cnt[lo];
-    const size_t b0 = (size_t)((int)blockIdx.x - l.first[lo]) * 4096;              // 4096 elements per workgroup
-    float s = 0.f;
+struct RoundList { const float* buf[32]; bf16_t* twin[32]; long long cnt[32]; int first[33]; int n; };
+template <class L>
+__device__ __forceinline__ int list_buffer(const L& l) { return rt_job_of(l.first, l.n, (int)blockIdx.x); }
+template <class L, class V, class S>
+__device__ __forceinline__ void list_walk(const L& l, int b, V vec4, S one) {
+    const size_t n = (size_t)l.cnt[b];
+    const size_t b0 = (size_t)((int)blockIdx.x - l.first[b]) * 4096;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const size_t i = b0 + (size_t)j * 1024 + threadIdx.x * 4;
-        if (i + 4 <= n) { const f32x4 v = *reinterpret_cast<const f32x4*>(g + i); s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
-        else for (size_t k = i; k < n; ++k) s += g[k] * g[k];
+        if (i + 4 <= n) vec4(i);
+        else for (size_t k = i; k < n; ++k) one(k);
     }
+}
+__global__ __launch_bounds__(256) void sq_list_kernel(const SqList l, float* __restrict__ slots) {
+    __shared__ float sm[16];
+    const int b = list_buffer(l);
+    const float* g = l.buf[b];
+    float s = 0.f;
+    list_walk(l, b, [&](size_t i) { s = sq_add(s, *reinterpret_cast<const f32x4*>(g + i)); }, [&](size_t k) { s += g[k] * g[k]; });
     s = rt_block_sum(s, sm);
-    if (threadIdx.x == 0) rt_sq_add(slots, blockIdx.x, l.sign[lo] * s);
+    if (threadIdx.x == 0) rt_sq_add(slots, blockIdx.x, l.sign[b] * s);
+}
+__global__ __launch_bounds__(256) void round_list_kernel(const RoundList l) {
+    const int b = list_buffer(l);
+    const float* g = l.buf[b]; bf16_t* tw = l.twin[b];
+    list_walk(l, b, [&](size_t i) { rt_store_bf16(tw + i, *reinterpret_cast<const f32x4*>(g + i)); }, [&](size_t k) { tw[k] = (bf16_t)g[k]; });
 }
 // the tensors that are accumulated with atomics (the complement of the weight matrices): table = n x {element offset, count <= 16384}
 __global__ __launch_bounds__(256) void sq_chunks_kernel(const float* __restrict__ base, const int64_t* __restrict__ table, float* __restrict__ slots) {
     __shared__ float sm[16];
-    const size_t off = (size_t)table[2 * blockIdx.x], cnt = (size_t)table[2 * blockIdx.x + 1];
     float s = 0.f;
-    for (size_t i = threadIdx.x * 4; i < cnt; i += 1024) {
-        if (i + 4 <= cnt && ((off + i) & 3) == 0) { const f32x4 v = *reinterpret_cast<const f32x4*>(base + off + i); s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
-        else for (size_t k = i; k < cnt && k < i + 4; ++k) s += base[off + k] * base[off + k];
-    }
+    rt_chunk_walk<false>(table, [&](size_t e) { s = sq_add(s, *reinterpret_cast<const f32x4*>(base + e)); },
+                         [&](size_t e) { s += base[e] * base[e]; });
     s = rt_block_sum(s, sm);
     if (threadIdx.x == 0) rt_sq_add(slots, blockIdx.x, s);
 }
@@ -365,46 +341,19 @@ __global__ __launch_bounds__(256) void sq_sum_kernel(const float* __restrict__ s
     s = rt_block_sum(s, sm);
     if (threadIdx.x == 0) out[0] = fmaxf(s, 0.f) + (extra ? extra[0] : 0.f);      // (new^2 - old^2 terms may leave -1 ulp when everything is zero)
 }
-
-struct RoundList { const float* buf[32]; bf16_t* twin[32]; long long cnt[32]; int first[33]; int n; };
-__global__ __launch_bounds__(256) void round_list_kernel(const RoundList l) {
-    int lo = 0, hi = l.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (l.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const float* g = l.buf[lo]; bf16_t* tw = l.twin[lo];
-    const size_t n = (size_t)l.cnt[lo];
-    const size_t b0 = (size_t)((int)blockIdx.x - l.first[lo]) * 4096;
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const size_t i = b0 + (size_t)j * 1024 + threadIdx.x * 4;
-        if (i + 4 <= n) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
-            *reinterpret_cast<bf16x4_t*>(tw + i) = bf16x4_t{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-        } else for (size_t k = i; k < n; ++k) tw[k] = (bf16_t)g[k];
-    }
-}
 __global__ __launch_bounds__(256) void round_chunks_kernel(const float* __restrict__ base, bf16_t* __restrict__ twin, const int64_t* __restrict__ table) {
-    const size_t off = (size_t)table[2 * blockIdx.x], cnt = (size_t)table[2 * blockIdx.x + 1];
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-    for (size_t i = threadIdx.x * 4; i < cnt; i += 1024) {
-        if (i + 4 <= cnt && ((off + i) & 3) == 0) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(base + off + i);
-            *reinterpret_cast<bf16x4_t*>(twin + off + i) = bf16x4_t{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-        } else for (size_t k = i; k < cnt && k < i + 4; ++k) twin[off + k] = (bf16_t)base[off + k];
-    }
+    rt_chunk_walk<false>(table, [&](size_t e) { rt_store_bf16(twin + e, *reinterpret_cast<const f32x4*>(base + e)); },
+                         [&](size_t e) { twin[e] = (bf16_t)base[e]; });
 }
 
+// (the unconditional counter keeps its own kernel: as the conditional one with a null condition it measured slower than its bar)
+__global__ void counter_add_kernel(int32_t* c, int32_t inc) { c[0] += inc; }
 __global__ void counter_add_if_zero_kernel(int32_t* c, int32_t inc, const uint32_t* cond, int reset_else) {
     if (cond[0] == 0u) c[0] += inc; else if (reset_else) c[0] = 0;
 }
 __global__ void stamp_kernel(uint64_t* buf, int idx) { buf[idx] = wall_clock64(); }
 // the end of an iteration in deferred mode, decided on the device: the update is armed (and the step counter advanced) only when no
-// cooperative launch failed AND the iteration's total loss is finite
-__global__ void finish_step_kernel(int32_t* step, int32_t* active, const uint32_t* cond, const float* loss) {
-    const bool bad = (cond && cond[0] != 0u) || (loss && !isfinite(loss[0]));
-    if (!bad) { step[0] += 1; active[0] += 1; } else active[0] = 0;
-}
-
+// cooperative launch failed AND the iteration's total loss is finite; then the loop's numbers (rt_finish_stats; rt_finish_step has none)
 __global__ void finish_stats_kernel(const rt_finish_desc d) {
     const uint32_t cw = d.cond ? d.cond[0] : 0u;
     const bool bad = cw != 0u || (d.loss && !isfinite(d.loss[0]));
@@ -486,18 +435,9 @@ extern "C" int rt_counter_add(int32_t* ctr, int32_t inc, rt_stream_t stream) {
     RT_CHECK_LAUNCH();
     return RT_OK;
 }
-
-
 extern "C" int rt_counter_add_if_zero(int32_t* ctr, int32_t inc, const uint32_t* cond, int reset_else, rt_stream_t stream) {
     if (!ctr || !cond) return RT_ERR_BADARG;
     hipLaunchKernelGGL(counter_add_if_zero_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ctr, inc, cond, reset_else);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
-}
-
-extern "C" int rt_finish_step(int32_t* step, int32_t* active, const uint32_t* cond, const float* loss, rt_stream_t stream) {
-    if (!step || !active) return RT_ERR_BADARG;
-    hipLaunchKernelGGL(finish_step_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, active, cond, loss);
     RT_CHECK_LAUNCH();
     return RT_OK;
 }
@@ -509,6 +449,11 @@ extern "C" int rt_finish_stats(const rt_finish_desc* d, rt_stream_t stream) {
     RT_CHECK_LAUNCH();
     return RT_OK;
 }
+extern "C" int rt_finish_step(int32_t* step, int32_t* active, const uint32_t* cond, const float* loss, rt_stream_t stream) {
+    rt_finish_desc d = {};
+    d.step = step; d.active = active; d.cond = cond; d.loss = loss;
+    return rt_finish_stats(&d, stream);
+}
 
 extern "C" int rt_stamp(uint64_t* buf, int idx, rt_stream_t stream) {
     if (!buf || idx < 0) return RT_ERR_BADARG;
@@ -517,15 +462,16 @@ extern "C" int rt_stamp(uint64_t* buf, int idx, rt_stream_t stream) {
     return RT_OK;
 }
 
-static int adamw_desc_ok(const rt_adamw_desc* d) {
-    if (!d || !d->p || (!d->g && !d->g16) || !d->m || !d->v || d->n <= 0 || (d->n & 3) || d->n_ranges < 1 || d->n_ranges > 8 || (d->step < 1 && !d->step_dev))
-        return RT_ERR_BADARG;
+// the descriptor check of all four update entries (SGD has no v and no step)
+static int opt_desc_ok(const rt_adamw_desc* d, bool sgd) {
+    if (!d || !d->p || (!d->g && !d->g16) || !d->m || d->n <= 0 || (d->n & 3) || d->n_ranges < 1 || d->n_ranges > 8) return RT_ERR_BADARG;
+    if (!sgd && (!d->v || (d->step < 1 && !d->step_dev))) return RT_ERR_BADARG;
     for (int r = 0; r < d->n_ranges; ++r) if ((d->range_begin[r] & 3) || (d->range_end[r] & 3)) return RT_ERR_BADARG;
     return RT_OK;
 }
 
 extern "C" int rt_adamw_mat(const rt_adamw_desc* d, const int64_t* table, int njobs, int total_tiles, rt_stream_t stream) {
-    const int rc = adamw_desc_ok(d);
+    const int rc = opt_desc_ok(d, false);
     if (rc != RT_OK) return rc;
     if (!table || njobs <= 0 || total_tiles <= 0) return RT_ERR_BADARG;
     hipLaunchKernelGGL(adamw_mat_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream, *d, table, njobs);
@@ -534,7 +480,7 @@ extern "C" int rt_adamw_mat(const rt_adamw_desc* d, const int64_t* table, int nj
 }
 
 extern "C" int rt_adamw_chunks(const rt_adamw_desc* d, const int64_t* table, int nchunks, rt_stream_t stream) {
-    const int rc = adamw_desc_ok(d);
+    const int rc = opt_desc_ok(d, false);
     if (rc != RT_OK) return rc;
     if (!table || nchunks <= 0) return RT_ERR_BADARG;
     hipLaunchKernelGGL(adamw_chunks_kernel, dim3((unsigned)nchunks), dim3(256), 0, (hipStream_t)stream, *d, table);
@@ -542,36 +488,30 @@ extern "C" int rt_adamw_chunks(const rt_adamw_desc* d, const int64_t* table, int
     return RT_OK;
 }
 
-int rt_sq_pass(float* const* bufs, const long long* counts, const float* signs, int n, float* slots, hipStream_t s) {
-    for (int base = 0; base < n; base += 32) {
-        SqList l; l.n = 0; int blocks = 0;
-        for (int i = base; i < n && i < base + 32; ++i) {
-            if (!bufs[i] || counts[i] <= 0) continue;
-            l.buf[l.n] = bufs[i]; l.cnt[l.n] = counts[i]; l.sign[l.n] = signs[i]; l.first[l.n] = blocks; ++l.n;
-            blocks += (int)((counts[i] + 4095) / 4096);
-        }
-        if (!l.n) continue;
-        l.first[l.n] = blocks;
-        hipLaunchKernelGGL(sq_list_kernel, dim3((unsigned)blocks), dim3(256), 0, s, l, slots);
-        RT_CHECK_LAUNCH();
+// the host side of rt_sq_pass / rt_round_pass: the n <= 32 buffers that take(l, i) accepts and stores (null / empty ones are
+// skipped) with their counts and first workgroups, in one launch
+template <class L, class Take, class Launch>
+static int list_pass(const long long* counts, int n, Take take, Launch launch) {
+    if (n > 32) return RT_ERR_BADARG;
+    L l; l.n = 0; int blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        if (counts[i] <= 0 || !take(l, i)) continue;
+        l.cnt[l.n] = counts[i]; l.first[l.n] = blocks; ++l.n;
+        blocks += (int)((counts[i] + 4095) / 4096);
     }
+    if (!l.n) return RT_OK;
+    l.first[l.n] = blocks;
+    launch(l, blocks);
+    RT_CHECK_LAUNCH();
     return RT_OK;
 }
-
+int rt_sq_pass(float* const* bufs, const long long* counts, const float* signs, int n, float* slots, hipStream_t s) {
+    return list_pass<SqList>(counts, n, [&](SqList& l, int i) { l.buf[l.n] = bufs[i]; l.sign[l.n] = signs[i]; return bufs[i] != nullptr; },
+                             [&](const SqList& l, int blocks) { hipLaunchKernelGGL(sq_list_kernel, dim3((unsigned)blocks), dim3(256), 0, s, l, slots); });
+}
 int rt_round_pass(float* const* bufs, void* const* twins, const long long* counts, int n, hipStream_t s) {
-    for (int base = 0; base < n; base += 32) {
-        RoundList l; l.n = 0; int blocks = 0;
-        for (int i = base; i < n && i < base + 32; ++i) {
-            if (!bufs[i] || !twins[i] || counts[i] <= 0) continue;
-            l.buf[l.n] = bufs[i]; l.twin[l.n] = (bf16_t*)twins[i]; l.cnt[l.n] = counts[i]; l.first[l.n] = blocks; ++l.n;
-            blocks += (int)((counts[i] + 4095) / 4096);
-        }
-        if (!l.n) continue;
-        l.first[l.n] = blocks;
-        hipLaunchKernelGGL(round_list_kernel, dim3((unsigned)blocks), dim3(256), 0, s, l);
-        RT_CHECK_LAUNCH();
-    }
-    return RT_OK;
+    return list_pass<RoundList>(counts, n, [&](RoundList& l, int i) { l.buf[l.n] = bufs[i]; l.twin[l.n] = (bf16_t*)twins[i]; return bufs[i] && twins[i]; },
+                                [&](const RoundList& l, int blocks) { hipLaunchKernelGGL(round_list_kernel, dim3((unsigned)blocks), dim3(256), 0, s, l); });
 }
 
 extern "C" int rt_round_chunks(const float* base, void* twin, const int64_t* table, int n, rt_stream_t stream) {
@@ -594,53 +534,36 @@ extern "C" int rt_sqnorm_finish(const float* base, const int64_t* table, int nch
     return RT_OK;
 }
 
-extern "C" int rt_sqnorm(const float* g, int64_t n, float* out, rt_stream_t stream) {
+template <class T, class V>
+static int sqnorm(const void* g, int64_t n, float* out, rt_stream_t stream) {
     if (!g || !out || n <= 0) return RT_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = rt_zero_f32(out, 1, s);
     if (e != hipSuccess) return (int)e;
-    int blocks = (int)(((size_t)n / 4 + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(sqnorm_kernel, dim3(blocks), dim3(256), 0, s, g, (size_t)n, out);
+    int blocks = (int)(((size_t)n / (sizeof(V) / sizeof(T)) + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL((sqnorm_kernel<T, V>), dim3(blocks), dim3(256), 0, s, (const T*)g, (size_t)n, out);
     RT_CHECK_LAUNCH();
     return RT_OK;
 }
+extern "C" int rt_sqnorm(const float* g, int64_t n, float* out, rt_stream_t stream) { return sqnorm<float, f32x4>(g, n, out, stream); }
+extern "C" int rt_sqnorm_bf16(const void* g16, int64_t n, float* out, rt_stream_t stream) { return sqnorm<bf16_t, bf16x8>(g16, n, out, stream); }
 
-extern "C" int rt_sqnorm_bf16(const void* g16, int64_t n, float* out, rt_stream_t stream) {
-    if (!g16 || !out || n <= 0) return RT_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = rt_zero_f32(out, 1, s);
-    if (e != hipSuccess) return (int)e;
-    int blocks = (int)(((size_t)n / 8 + 255) / 256); if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(sqnorm_bf16_kernel, dim3(blocks), dim3(256), 0, s, (const bf16_t*)g16, (size_t)n, out);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
-}
-
-extern "C" int rt_adamw_flat(const rt_adamw_desc* d, rt_stream_t stream) {
-    if (!d || !d->p || (!d->g && !d->g16) || !d->m || !d->v || d->n <= 0 || (d->n & 3) || d->n_ranges < 1 || d->n_ranges > 8 || (d->step < 1 && !d->step_dev))
-        return RT_ERR_BADARG;
-    for (int r = 0; r < d->n_ranges; ++r) if ((d->range_begin[r] & 3) || (d->range_end[r] & 3)) return RT_ERR_BADARG;
+// rt_adamw_flat / rt_sgd_flat: the descriptor check, the span (0, 0 = the whole buffer) and the launch
+static int flat_update(const rt_adamw_desc* d, bool sgd, rt_stream_t stream) {
+    const int rc = opt_desc_ok(d, sgd);
+    if (rc != RT_OK) return rc;
     rt_adamw_desc a = *d;
     if (a.span_begin == 0 && a.span_end == 0) a.span_end = a.n;
     if (a.span_begin < 0 || a.span_end > a.n || a.span_begin >= a.span_end || (a.span_begin & 3) || (a.span_end & 3)) return RT_ERR_BADARG;
     int blocks = (int)(((size_t)(a.span_end - a.span_begin) / 4 + 255) / 256); if (blocks > 4096) blocks = 4096;
     static const int nt_env = RT_TUNE("REFTR_ADAMW_NT", 1);
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, nt_env);
+    auto kernel = sgd ? adamw_kernel<RULE_SGD, false> : nt_env ? adamw_kernel<RULE_ADAMW_FLAT, true> : adamw_kernel<RULE_ADAMW_FLAT, false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     RT_CHECK_LAUNCH();
     return RT_OK;
 }
-
-extern "C" int rt_sgd_flat(const rt_adamw_desc* d, rt_stream_t stream) {
-    if (!d || !d->p || (!d->g && !d->g16) || !d->m || d->n <= 0 || (d->n & 3) || d->n_ranges < 1 || d->n_ranges > 8) return RT_ERR_BADARG;
-    for (int r = 0; r < d->n_ranges; ++r) if ((d->range_begin[r] & 3) || (d->range_end[r] & 3)) return RT_ERR_BADARG;
-    rt_adamw_desc a = *d;
-    if (a.span_begin == 0 && a.span_end == 0) a.span_end = a.n;
-    if (a.span_begin < 0 || a.span_end > a.n || a.span_begin >= a.span_end || (a.span_begin & 3) || (a.span_end & 3)) return RT_ERR_BADARG;
-    int blocks = (int)(((size_t)(a.span_end - a.span_begin) / 4 + 255) / 256); if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(sgd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
-}
+extern "C" int rt_adamw_flat(const rt_adamw_desc* d, rt_stream_t stream) { return flat_update(d, false, stream); }
+extern "C" int rt_sgd_flat(const rt_adamw_desc* d, rt_stream_t stream) { return flat_update(d, true, stream); }
 
 extern "C" int rt_grad_accum(int mode, float* g, float* acc, int64_t n, float scale, const float* scale_dev, float* partials,
                              float* out_sq, rt_stream_t stream) {

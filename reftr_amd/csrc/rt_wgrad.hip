@@ -476,9 +476,7 @@ __global__ __launch_bounds__(256, MINB) void conv_wgrad_dma_kernel(const bf16_t*
 struct WgradGroup { WgradArgs j[24]; int first[25]; int gx[24]; int gy[24]; int n; };
 template <int BN, int BC, int CR, int NS, int MINB>
 __global__ __launch_bounds__(256, MINB) void conv_wgrad_dma_grouped_kernel(const WgradGroup g) {
-    int lo = 0, hi = g.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (g.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    lo = __builtin_amdgcn_readfirstlane(lo);
+    const int lo = __builtin_amdgcn_readfirstlane(rt_job_of(g.first, g.n, (int)blockIdx.x));
     const int lin = (int)blockIdx.x - g.first[lo];
     if (lin >= g.gx[lo] * g.gy[lo]) return;
     wgrad_dma_body<BN, BC, true, CR, NS>(g.j[lo].dy, g.j[lo].x, g.j[lo], lin, g.gx[lo], g.gy[lo]);
@@ -523,9 +521,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 __global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const ReduceGroup g) {
-    int lo = 0, hi = g.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (g.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    lo = __builtin_amdgcn_readfirstlane(lo);
+    const int lo = __builtin_amdgcn_readfirstlane(rt_job_of(g.first, g.n, (int)blockIdx.x));
     wgrad_reduce_body<false>(g.part[lo], g.dw[lo], g.scale[lo], g.out_elems[lo], g.row_elems[lo], g.nsplit[lo], g.overwrite[lo],
                              (int)blockIdx.x - g.first[lo]);
 }
@@ -561,8 +557,7 @@ __global__ __launch_bounds__(256) void small_m_wgrad_kernel(const bf16_t* __rest
 struct SmallJobs { rt_small_wgrad_job j[64]; int first[65]; int n; };
 __global__ __launch_bounds__(256) void small_m_wgrad_grouped_kernel(const SmallJobs p) {
     __shared__ float sm[16];
-    int lo = 0, hi = p.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (p.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const int lo = rt_job_of(p.first, p.n, (int)blockIdx.x);
     const rt_small_wgrad_job& q = p.j[lo];
     const bf16_t* dy = (const bf16_t*)q.dy; const bf16_t* x = (const bf16_t*)q.x;
     const int k4 = q.K >> 2;

@@ -467,9 +467,7 @@ __global__ __launch_bounds__(512, 1) void w2_grouped_kernel(const W2Group g) {
 struct W2Reduce { const float* part[W2_MAXP]; float* dw[W2_MAXP]; const float* scale[W2_MAXP]; float* sqacc[W2_MAXP]; bf16_t* g16[W2_MAXP];
                   int out_elems[W2_MAXP], row_elems[W2_MAXP], nsplit[W2_MAXP], accumulate[W2_MAXP], first[W2_MAXP + 1]; int n; };
 __global__ __launch_bounds__(256) void w2_reduce_kernel(const W2Reduce g) {
-    int lo = 0, hi = g.n - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (g.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    lo = __builtin_amdgcn_readfirstlane(lo);
+    const int lo = __builtin_amdgcn_readfirstlane(rt_job_of(g.first, g.n, (int)blockIdx.x));
     const float* part = g.part[lo]; float* dw = g.dw[lo]; const float* scale = g.scale[lo];
     const int out_elems = g.out_elems[lo], nsplit = g.nsplit[lo];
     const int i = (((int)blockIdx.x - g.first[lo]) * 256 + (int)threadIdx.x) * 4;

@@ -366,10 +366,21 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.active is not None:
             self.active.zero_()
 
+    # The checkpoint format (torch.optim.AdamW's): per-parameter state key -> the flat buffer it is a view of, whether a `step` is
+    # written and whether a state entry may lack a key, the keys of this class's param groups that torch's group dicts lack / the ones torch's have on top, and the
+    # hyper-parameters a loaded group hands over.  FusedSGD states its own.
+    _STATE = (("exp_avg", "m"), ("exp_avg_sq", "v"))
+    _STATE_STEP = True
+    _STATE_OPTIONAL = False
+    _PG_DROP = ("params", "group_id")
+    _PG_ADD = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
+    _PG_LOAD = ("lr", "weight_decay", "betas", "eps", "initial_lr")
+
     def state_dict(self):
-        """torch.optim.AdamW's format (what the reference writes into checkpoint['optimizer'], main_vg.py:377-384):
-        per-parameter `step`, `exp_avg`, `exp_avg_sq` keyed by the parameter's index in the reference's group order, so a
-        checkpoint written here resumes under the reference and vice versa."""
+        """The torch optimizer's format (torch.optim.AdamW: what the reference writes into checkpoint['optimizer'], main_vg.py:377-384;
+        torch.optim.SGD for FusedSGD): the per-parameter state of `_STATE` (AdamW: `step`, `exp_avg`, `exp_avg_sq`; SGD:
+        `momentum_buffer`) keyed by the parameter's index in the reference's group order, so a checkpoint written here resumes under
+        the reference and vice versa."""
         self._refuse_mid_window("state_dict()")
         if self._flush_pending is not None:
             self._flush_pending()
@@ -379,17 +390,22 @@ class FusedAdamW(torch.optim.Optimizer):
             ids = []
             for n in ns:
                 if self.step_count > 0:
-                    state[idx] = {"step": torch.tensor(float(self.step_count)),
-                                  "exp_avg": st.view_of(self.m, n).detach().clone(memory_format=torch.contiguous_format),
-                                  "exp_avg_sq": st.view_of(self.v, n).detach().clone(memory_format=torch.contiguous_format)}
+                    state[idx] = {"step": torch.tensor(float(self.step_count))} if self._STATE_STEP else {}
+                    for key, buf in self._STATE:
+                        state[idx][key] = st.view_of(getattr(self, buf), n).detach().clone(memory_format=torch.contiguous_format)
                 ids.append(idx); idx += 1
-            pg = {k: v for k, v in g.items() if k not in ("params", "group_id")}
-            pg.update(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None, params=ids)
+            pg = {k: v for k, v in g.items() if k not in self._PG_DROP}
+            pg.update(self._PG_ADD, params=ids)
             groups.append(pg)
         return {"state": state, "param_groups": groups}
 
+    def _restored_step(self, state):
+        steps = {int(float(s_["step"])) for s_ in state.values()}
+        assert len(steps) <= 1, "per-parameter step counts differ: not representable by the fused optimizer"
+        return steps.pop() if steps else 0
+
     def load_state_dict(self, sd):
-        """Accepts a torch.optim.AdamW state_dict with the reference's grouping (as written by the reference or by
+        """Accepts the torch optimizer's state_dict with the reference's grouping (as written by the reference or by
         state_dict() above); hyper-parameters of the groups are taken over like torch does."""
         if self._flush_pending is not None:
             self._flush_pending()
@@ -398,17 +414,15 @@ class FusedAdamW(torch.optim.Optimizer):
         groups = sd["param_groups"]
         # the reference leaves its 4th (mask branch) group empty for REC models; older checkpoints may have 3 groups
         assert sum(len(g["params"]) for g in groups) == len(flat), "optimizer state does not match this model's parameters"
-        steps = set()
         with torch.no_grad():
             for i, s_ in sd["state"].items():
-                n = flat[int(i)]
-                st.view_of(self.m, n).copy_(s_["exp_avg"]); st.view_of(self.v, n).copy_(s_["exp_avg_sq"])
-                steps.add(int(float(s_["step"])))
-        assert len(steps) <= 1, "per-parameter step counts differ: not representable by the fused optimizer"
-        self.step_count = steps.pop() if steps else 0
+                for key, buf in self._STATE:
+                    if not self._STATE_OPTIONAL or s_.get(key) is not None:          # (a missing AdamW moment is an error)
+                        st.view_of(getattr(self, buf), flat[int(i)]).copy_(s_[key])
+        self.step_count = self._restored_step(sd["state"])
         self.step_dev.fill_(self.step_count)
         for g, s_ in zip(self.param_groups, groups):
-            for k in ("lr", "weight_decay", "betas", "eps", "initial_lr"):
+            for k in self._PG_LOAD:
                 if k in s_:
                     g[k] = s_[k]
 
@@ -418,6 +432,12 @@ class FusedSGD(FusedAdamW):
     on the same flat buffers, schedules (deferred update under graph replay, device learning rates, data-parallel bf16
     gradients) and clip path as FusedAdamW: `m` is the momentum buffer, `v` is not allocated, rt_sgd_flat is the kernel."""
     SGD = True
+    _STATE = (("momentum_buffer", "m"),)
+    _STATE_STEP = False
+    _STATE_OPTIONAL = True                    # torch.optim.SGD keeps momentum_buffer = None until a parameter's first step
+    _PG_DROP = ("params", "group_id", "betas", "eps")
+    _PG_ADD = dict(dampening=0, nesterov=False, maximize=False, foreach=None, differentiable=False, fused=None)
+    _PG_LOAD = ("lr", "weight_decay", "momentum", "initial_lr")
 
     def __init__(self, model, lr=1e-4, lr_backbone=1e-5, lr_bert=None, weight_decay=1e-4, momentum=0.9, lr_mask_branch_proj=1.0):
         super().__init__(model, lr=lr, lr_backbone=lr_backbone, lr_bert=lr_bert, weight_decay=weight_decay, betas=(momentum, 0.0),
@@ -426,40 +446,8 @@ class FusedSGD(FusedAdamW):
         for g in self.param_groups:
             g["momentum"] = momentum
 
-    def state_dict(self):
-        """torch.optim.SGD's format: per-parameter `momentum_buffer` keyed by the parameter's index in the reference's group order."""
-        self._refuse_mid_window("state_dict()")
-        if self._flush_pending is not None:
-            self._flush_pending()
-        st = self.model.store
-        state, groups, idx = {}, [], 0
-        for g, ns in zip(self.param_groups, self._names):
-            ids = []
-            for n in ns:
-                if self.step_count > 0:
-                    state[idx] = {"momentum_buffer": st.view_of(self.m, n).detach().clone(memory_format=torch.contiguous_format)}
-                ids.append(idx); idx += 1
-            pg = {k: v for k, v in g.items() if k not in ("params", "group_id", "betas", "eps")}
-            pg.update(dampening=0, nesterov=False, maximize=False, foreach=None, differentiable=False, fused=None, params=ids)
-            groups.append(pg)
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd):
-        if self._flush_pending is not None:
-            self._flush_pending()
-        st = self.model.store
-        flat = [n for ns in self._names for n in ns]
-        assert sum(len(g["params"]) for g in sd["param_groups"]) == len(flat), "optimizer state does not match this model's parameters"
-        with torch.no_grad():
-            for i, s_ in sd["state"].items():
-                if s_.get("momentum_buffer") is not None:
-                    st.view_of(self.m, flat[int(i)]).copy_(s_["momentum_buffer"])
-        self.step_count = 1 if sd["state"] else 0
-        self.step_dev.fill_(self.step_count)
-        for g, s_ in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "weight_decay", "momentum", "initial_lr"):
-                if k in s_:
-                    g[k] = s_[k]
+    def _restored_step(self, state):
+        return 1 if state else 0                # torch.optim.SGD keeps no step: "some state" only tells the first step from the others
 
 
 def build_optimizer(model, args):

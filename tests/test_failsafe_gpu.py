@@ -155,7 +155,9 @@ def test_eager_loop_body_reruns_a_timed_out_iteration_on_the_chain(coop_env):
 def test_matrix_adamw_equals_flat_adamw_plus_weight_prep(hip):
     """rt_adamw_mat + rt_adamw_chunks over a synthetic flat buffer (a vectorisable Linear, a 3x3 convolution with a FrozenBN scale,
     a ragged matrix that takes the element-wise path, loose vectors in between) == rt_adamw_flat followed by rt_weight_prep_batched:
-    masters and moments to 1 ulp (the two kernels are compiled separately), operands bit-equal given equal masters."""
+    masters and moments to 1 ulp, operands bit-equal given equal masters.  (All three kernels inline one definition of the update, but
+    which products are fused into the adds differs between the three, as it always has: each keeps its own rounding --
+    benchmarks/optim_dump.py, profiles/optim_unify_bits.txt.)"""
     from reftr_amd.optim import cover_span
     H = hip
     dev = "cuda"
@@ -453,10 +455,11 @@ def test_finish_stats_is_finish_step_plus_the_loops_numbers(hip):
         assert int(step) == (8 if expect_armed else 7) and int(active) == (2 if expect_armed else 0)
         assert float(gn) == 1.25
         assert stats.tolist() == [0.125, 0.25, 7.0, float(veto_word), 1.25]
-        # the reference behaviour of the single launches
+        # rt_finish_step: the same counters (one kernel behind both entries, hence also against the values computed here)
         step2 = torch.tensor([7], dtype=torch.int32, device=dev); active2 = torch.tensor([1], dtype=torch.int32, device=dev)
         H.finish_step(step2, active2, veto, loss)
         assert int(step2) == int(step) and int(active2) == int(active)
+        assert int(step2) == (8 if expect_armed else 7) and int(active2) == (2 if expect_armed else 0)
     # no veto word, no stats: counters and norm only
     step = torch.tensor([0], dtype=torch.int32, device=dev); active = torch.tensor([0], dtype=torch.int32, device=dev)
     sq = torch.tensor([4.0], dtype=torch.float32, device=dev); gn = torch.zeros(1, dtype=torch.float32, device=dev)

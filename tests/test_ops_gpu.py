@@ -520,6 +520,65 @@ def test_sqnorm_adamw_bf16_gradients_spans_active_and_device_lr(hip):
         assert rel(a, b) < 1e-6
 
 
+def test_sgd_flat_bf16_gradients_spans_active_and_device_lr(hip):
+    """rt_sgd_flat in the variants the engine uses, as the AdamW test above but exact: the squared norm is computed on the host in
+    float64 and passed in, so nothing depends on the order of atomics.  bf16 gradients give exactly what fp32 gradients of the same
+    (bf16-representable) values give; two spans equal one launch; active == 0 changes nothing; lr_dev gives what the same rates in
+    `ranges` give."""
+    g = torch.Generator().manual_seed(13)
+    n = 2 * 4096 + 8
+    p0 = torch.randn(n, generator=g).cuda(); gr16 = (torch.randn(n, generator=g) * 0.01).cuda().bfloat16()
+    gr = gr16.float()
+    sq = (gr.double() ** 2).sum().float().reshape(1)
+    ranges = [(0, 4096, 1e-2, 1e-4), (4096, n, 1e-3, 1e-4)]
+
+    def run(ranges=ranges, spans=(None,), **kw):
+        p = p0.clone(); m = torch.zeros(n, device="cuda")
+        for step in (1, 2, 3):
+            for sp in spans:
+                hip.adamw_flat(p, gr, m, m[:4], step=step, ranges=ranges, gnorm_sq=sq, max_norm=0.05, beta1=0.9, span=sp, sgd=True, **kw)
+        return p, m
+
+    ref = run()
+    assert not torch.equal(ref[0], p0) and float(ref[1].abs().max()) > 0.0
+    for got in (run(g16=gr16), run(spans=[(0, 4100), (4100, n)])):
+        assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
+    idle = run(active=torch.zeros(1, dtype=torch.int32, device="cuda"))
+    assert torch.equal(idle[0], p0) and float(idle[1].abs().max()) == 0.0
+    lr_dev = torch.tensor([1e-2, 1e-3, 0, 0, 0, 0, 0, 0], dtype=torch.float32, device="cuda")
+    dev = run(ranges=[(0, 4096, 7.0, 1e-4), (4096, n, 9.0, 1e-4)], lr_dev=lr_dev)      # rates by value that the device words must override
+    assert torch.equal(dev[0], ref[0]) and torch.equal(dev[1], ref[1])
+
+
+def test_chunk_table_kernels_at_ragged_offsets(hip):
+    """rt_zero_chunks, rt_round_chunks and rt_sqnorm_finish over one {offset, count} table with a single element, two chunks shorter
+    than a vector at odd offsets, a full-size chunk at an odd offset (single elements throughout), a full-size aligned chunk and a
+    chunk at offset = 2 mod 4 with a ragged end.  Zeroing and rounding touch exactly the listed elements.  The norm: all summands
+    are positive and no partial sum is longer than about 90 additions (64 + 4 per thread, 6 + 4 in the workgroup, one add per slot,
+    6 + 4 + 1 in the final sum), so the square is within 90 * 2^-24 = 5.4e-6 relative and the norm within half of that: 1e-5."""
+    table = [(0, 1), (5, 3), (12, 5), (4097, 16384), (20484, 16384), (36870, 1023)]
+    n = 45056
+    g = torch.Generator().manual_seed(14)
+    base = (torch.randn(n, generator=g) + 3.0).cuda()
+    tab = torch.tensor([x for c in table for x in c], dtype=torch.int64).cuda()
+    inside = torch.zeros(n, dtype=torch.bool, device="cuda")
+    for off, cnt in table:
+        inside[off:off + cnt] = True
+    z = base.clone()
+    hip.zero_chunks(z, tab, len(table))
+    assert torch.equal(z.view(torch.int32), torch.where(inside, torch.zeros_like(base), base).view(torch.int32))
+    twin = torch.full((n,), 7.0, dtype=torch.bfloat16, device="cuda")
+    hip.round_chunks(base, twin, tab, len(table))
+    assert torch.equal(twin.view(torch.int16), torch.where(inside, base.bfloat16(), torch.full_like(twin, 7.0)).view(torch.int16))
+    slots = torch.zeros(hip.SQ_SLOTS * hip.SQ_STRIDE, device="cuda"); out = torch.zeros(1, device="cuda")
+    extra = torch.tensor([3.5], device="cuda")
+    hip.sqnorm_finish(base, tab, len(table), slots, out, extra=extra)
+    want = math.sqrt(float((base.double()[inside] ** 2).sum()) + 3.5)
+    got = math.sqrt(float(out))
+    print("sqnorm_finish over the ragged table: norm", got, "float64", want, "relative", abs(got - want) / want)
+    assert abs(got - want) <= 1e-5 * want
+
+
 def test_head_granular_epilogue_dropout_equals_one_key_attention_dropout(hip):
     """rt_conv_gemm's drop_shift = log2(head_dim): one keep/drop decision per head, at the attention kernel's hash index
     b * H + h -- the zero pattern and the kept values of `attn(v, v, v)` over a single key are reproduced exactly."""
