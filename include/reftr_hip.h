@@ -672,6 +672,28 @@ int rt_img_collate_norm(const int64_t* table, float* out, uint8_t* mask, int B, 
                         const float* std3, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * rt_batch_stage — one batch of any size into the fixed-size ("canvas") input buffers of a captured training step, ONE launch:
+ *   img  fp32 [B,3,Hc,Wc]  <- src_img fp32 [B,3,hs,ws] (contiguous), zeros to the right and below;
+ *   mask u8   [B,Hc,Wc]    <- src_mask u8 [B,hs,ws], 1 outside (NestedTensor convention: 1 = padding);
+ *   boxes fp32 [B*boxes_per_image, 4] <- the B device arrays box_ptrs[b] (fp32 [box_counts[b], 4]) packed in image order, zeros behind;
+ *   tgt_off int32 [B+1] = exclusive prefix sums of box_counts, num_boxes fp32 [1] = their sum (the loss kernels clamp it to >= 1);
+ *   tgt_masks u8 [B,1,Hc,Wc] <- the B device arrays tm_ptrs[b] (u8 [tm_hw[2b], tm_hw[2b+1]]), zeros outside -- optional: tm_ptrs,
+ *   tm_hw and tgt_masks are all NULL or all given.
+ * Every byte of every destination is written by every call (the buffers hold the previous batch).  box_ptrs, box_counts, tm_ptrs and
+ * tm_hw are HOST arrays of B entries: they and every size travel by value in the kernel's argument block -- no device table, no
+ * host -> device copy, no synchronisation -- which bounds B by RT_BATCH_STAGE_MAX_B (RT_ERR_UNSUPPORTED above it, and for
+ * B*3*Hc*Wc >= 2^32).  A box pointer may be NULL when its count is 0.  RT_ERR_BADARG, with nothing launched: a NULL required pointer,
+ * a non-positive size, hs > Hc, ws > Wc, a target mask larger than the canvas, a count < 0 or > boxes_per_image.
+ * 16-byte stores when Wc % 4 == 0 (fp32) / Wc % 16 == 0 (bytes) and the destination base is 16-byte aligned, element stores otherwise;
+ * sources of any width and alignment.  No atomics: bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+#define RT_BATCH_STAGE_MAX_B 64
+int rt_batch_stage(const float* src_img, const uint8_t* src_mask, int B, int hs, int ws, float* img, uint8_t* mask,
+                   int Hc, int Wc, const float* const* box_ptrs, const int32_t* box_counts, int boxes_per_image,
+                   float* boxes, int32_t* tgt_off, float* num_boxes, const uint8_t* const* tm_ptrs, const int32_t* tm_hw,
+                   uint8_t* tgt_masks, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * rt_cem_fwd / rt_cem_bwd — the CEM block of RefTRSeg (--ablation cem_loss, models/reftr_segmentation.py:16-41) for the one
  * query per image of RES: u_b = c3(hs_b) (hs bf16 [B, E] = last decoder output, w3 [16, E], b3 [16]), res bf16 [B*HW, ld] =
  * MaskHeadSmallConv's last feature map (16 channels in front of the padding), a_p = res_p . w2 + b2,

@@ -61,7 +61,151 @@ __global__ __launch_bounds__(256) void collate_norm_kernel(const long long* __re
     }
 }
 
+// ---- rt_batch_stage: one batch of any size into the fixed canvas buffers a captured step reads.
+// Every per-batch fact rides in the kernel argument block (1.9 KB of the 4 KB a launch carries): no device table, so no host -> device
+// copy and no host synchronisation between two replays.  The index space is [image units | mask units | target-mask units | box words];
+// a unit is one 16-byte store where the destination rows allow it (W_c % 4 == 0 for fp32, W_c % 16 == 0 for bytes, 16-byte aligned base),
+// else one element.  Sources are read with one 16-byte load when the four / sixteen elements lie inside the row at an aligned address,
+// element by element otherwise (source row starts are aligned only by accident).  Plain loads and stores: the same bits every run.
+struct BatchStageArgs {
+    const float* src_img; const uint8_t* src_mask; float* img; uint8_t* mask;
+    float* boxes; int32_t* tgt_off; float* num_boxes; uint8_t* tgt_masks;
+    int B, hs, ws, Hc, Wc, box_rows;
+    int img_vec, mask_vec, tm_vec;                 // elements per unit: 4 | 1 (fp32), 16 | 1 (bytes)
+    unsigned n_img, n_mask, n_tm, n_box;           // units per segment
+    const float* box_ptr[RT_BATCH_STAGE_MAX_B]; const uint8_t* tm_ptr[RT_BATCH_STAGE_MAX_B];
+    int32_t box_n[RT_BATCH_STAGE_MAX_B], tm_h[RT_BATCH_STAGE_MAX_B], tm_w[RT_BATCH_STAGE_MAX_B];
+};
+static_assert(sizeof(BatchStageArgs) <= 4096, "the argument block of a launch");
+
+// unit u of a [planes][Hc][Wc] byte destination: dst rows <- src[h][w] (plane `p`'s source), `fill` outside
+template <int V>
+__device__ __forceinline__ void stage_bytes(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int h, int w, int Hc, int Wc,
+                                            int p, int y, int x, uint8_t fill) {
+    uint8_t* d = dst + ((size_t)p * Hc + y) * Wc + x;
+    if constexpr (V == 1) {
+        *d = (y < h && x < w) ? src[(size_t)y * w + x] : fill;
+    } else {
+        union { uint4 q; uint8_t b[16]; } v;
+        const uint8_t* s = src + (size_t)y * w + x;
+        if (y < h && x + 15 < w && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+            v.q = *reinterpret_cast<const uint4*>(s);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v.b[j] = (y < h && x + j < w) ? s[j] : fill;
+        }
+        *reinterpret_cast<uint4*>(d) = v.q;
+    }
+}
+
+__global__ __launch_bounds__(256) void batch_stage_kernel(const BatchStageArgs a) {
+    const size_t total = (size_t)a.n_img + a.n_mask + a.n_tm + a.n_box;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        if (i < a.n_img) {
+            const unsigned u = (unsigned)i, ru = (unsigned)(a.Wc / a.img_vec);
+            const int x = (int)(u % ru) * a.img_vec; const unsigned t = u / ru;
+            const int y = (int)(t % (unsigned)a.Hc), p = (int)(t / (unsigned)a.Hc);          // p = b * 3 + c
+            float* d = a.img + ((size_t)p * a.Hc + y) * a.Wc + x;
+            const float* s = a.src_img + ((size_t)p * a.hs + y) * a.ws + x;
+            if (a.img_vec == 1) {
+                *d = (y < a.hs && x < a.ws) ? *s : 0.f;
+            } else {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (y < a.hs) {
+                    if (x + 3 < a.ws && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+                        v = *reinterpret_cast<const float4*>(s);
+                    } else {
+                        if (x < a.ws) v.x = s[0];
+                        if (x + 1 < a.ws) v.y = s[1];
+                        if (x + 2 < a.ws) v.z = s[2];
+                        if (x + 3 < a.ws) v.w = s[3];
+                    }
+                }
+                *reinterpret_cast<float4*>(d) = v;
+            }
+            continue;
+        }
+        size_t j = i - a.n_img;
+        if (j < a.n_mask) {
+            const unsigned u = (unsigned)j, ru = (unsigned)(a.Wc / a.mask_vec);
+            const int x = (int)(u % ru) * a.mask_vec; const unsigned t = u / ru;
+            const int y = (int)(t % (unsigned)a.Hc), b = (int)(t / (unsigned)a.Hc);
+            const uint8_t* s = a.src_mask + (size_t)b * a.hs * a.ws;
+            if (a.mask_vec == 1) stage_bytes<1>(a.mask, s, a.hs, a.ws, a.Hc, a.Wc, b, y, x, 1);
+            else stage_bytes<16>(a.mask, s, a.hs, a.ws, a.Hc, a.Wc, b, y, x, 1);
+            continue;
+        }
+        j -= a.n_mask;
+        if (j < a.n_tm) {
+            const unsigned u = (unsigned)j, ru = (unsigned)(a.Wc / a.tm_vec);
+            const int x = (int)(u % ru) * a.tm_vec; const unsigned t = u / ru;
+            const int y = (int)(t % (unsigned)a.Hc), b = (int)(t / (unsigned)a.Hc);
+            if (a.tm_vec == 1) stage_bytes<1>(a.tgt_masks, a.tm_ptr[b], a.tm_h[b], a.tm_w[b], a.Hc, a.Wc, b, y, x, 0);
+            else stage_bytes<16>(a.tgt_masks, a.tm_ptr[b], a.tm_h[b], a.tm_w[b], a.Hc, a.Wc, b, y, x, 0);
+            continue;
+        }
+        j -= a.n_tm;
+        const int k = (int)j, nbox = a.box_rows * 4;
+        if (k < nbox) {                                   // boxes[box_rows][4]: packed in image order, zero behind the last box
+            const int r = k >> 2, c = k & 3;
+            float v = 0.f;
+            int off = 0;
+            for (int b = 0; b < a.B; ++b) {
+                const int n = a.box_n[b];
+                if (r >= off && r < off + n) v = a.box_ptr[b][(size_t)(r - off) * 4 + c];
+                off += n;
+            }
+            a.boxes[k] = v;
+        } else {                                          // tgt_off[0 .. B] (exclusive prefix sums), then num_boxes
+            const int b = k - nbox;
+            int off = 0;
+            for (int q = 0; q < (b < a.B ? b : a.B); ++q) off += a.box_n[q];
+            if (b <= a.B) a.tgt_off[b] = off;
+            else a.num_boxes[0] = (float)off;
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int rt_batch_stage(const float* src_img, const uint8_t* src_mask, int B, int hs, int ws, float* img, uint8_t* mask,
+                              int Hc, int Wc, const float* const* box_ptrs, const int32_t* box_counts, int boxes_per_image,
+                              float* boxes, int32_t* tgt_off, float* num_boxes, const uint8_t* const* tm_ptrs, const int32_t* tm_hw,
+                              uint8_t* tgt_masks, rt_stream_t stream) {
+    if (!src_img || !src_mask || !img || !mask || !box_ptrs || !box_counts || !boxes || !tgt_off || !num_boxes) return RT_ERR_BADARG;
+    if (B <= 0 || hs <= 0 || ws <= 0 || Hc <= 0 || Wc <= 0 || boxes_per_image <= 0) return RT_ERR_BADARG;
+    if ((tm_ptrs || tm_hw || tgt_masks) && !(tm_ptrs && tm_hw && tgt_masks)) return RT_ERR_BADARG;
+    if (B > RT_BATCH_STAGE_MAX_B) return RT_ERR_UNSUPPORTED;
+    if (hs > Hc || ws > Wc) return RT_ERR_BADARG;
+    BatchStageArgs a{};
+    for (int b = 0; b < B; ++b) {
+        const int n = box_counts[b];
+        if (n < 0 || n > boxes_per_image || (n > 0 && !box_ptrs[b])) return RT_ERR_BADARG;
+        a.box_ptr[b] = box_ptrs[b]; a.box_n[b] = n;
+        if (tm_ptrs) {
+            const int h = tm_hw[2 * b], w = tm_hw[2 * b + 1];
+            if (!tm_ptrs[b] || h <= 0 || w <= 0 || h > Hc || w > Wc) return RT_ERR_BADARG;
+            a.tm_ptr[b] = tm_ptrs[b]; a.tm_h[b] = h; a.tm_w[b] = w;
+        }
+    }
+    const size_t plane = (size_t)Hc * Wc;
+    if ((size_t)B * 3 * plane >= ((size_t)1 << 32) || (size_t)B * boxes_per_image * 4 + B + 2 >= ((size_t)1 << 31)) return RT_ERR_UNSUPPORTED;
+    a.src_img = src_img; a.src_mask = src_mask; a.img = img; a.mask = mask;
+    a.boxes = boxes; a.tgt_off = tgt_off; a.num_boxes = num_boxes; a.tgt_masks = tgt_masks;
+    a.B = B; a.hs = hs; a.ws = ws; a.Hc = Hc; a.Wc = Wc; a.box_rows = B * boxes_per_image;
+    a.img_vec = (Wc % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0) ? 4 : 1;
+    a.mask_vec = (Wc % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) ? 16 : 1;
+    a.tm_vec = (Wc % 16 == 0 && (reinterpret_cast<uintptr_t>(tgt_masks) & 15) == 0) ? 16 : 1;
+    a.n_img = (unsigned)((size_t)B * 3 * plane / a.img_vec);
+    a.n_mask = (unsigned)((size_t)B * plane / a.mask_vec);
+    a.n_tm = tgt_masks ? (unsigned)((size_t)B * plane / a.tm_vec) : 0u;
+    a.n_box = (unsigned)(a.box_rows * 4 + B + 2);
+    const size_t total = (size_t)a.n_img + a.n_mask + a.n_tm + a.n_box;
+    size_t blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;       // 256 CUs x 8 workgroups, grid-stride beyond
+    hipLaunchKernelGGL(batch_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
 
 extern "C" int rt_resample_u8(const void* src, void* dst, const int32_t* bounds, const int32_t* coeffs, int n0, int n1, int C,
                               int out_len, int ksize, int axis, rt_stream_t stream) {

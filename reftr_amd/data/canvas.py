@@ -1,0 +1,153 @@
+"""The batch canvas: one fixed input shape for data whose batches all differ.
+
+The reference's collate (util/collate_fn.py:24-41) pads a batch to the largest image IN that batch, Flickr30k Entities carries a
+different number of boxes per image, RES target masks have the size of their image -- so nearly every batch has its own shape, and a
+step captured into a hipGraph for one shape (engine_vg.CapturedTrainStep) serves almost none of them.  A BatchCanvas fixes the shape:
+images are padded to (height, width) with zeros on the right and bottom, the padding mask with True, the target masks with zeros,
+and the target boxes are packed into a buffer of `boxes_per_image` rows per image with their offsets and their count kept in device
+memory.  That is the batch the reference's collate produces whenever one image of the batch has the canvas size, so the step computed
+on it is the existing code's step at an existing shape.
+
+`pad_on_host` is that definition in plain torch; `stage` is the same bytes written by ONE rt_batch_stage launch into buffers that
+stay where they are, which is what a captured step needs.  Opt-in: engine_vg's entry points take `canvas=None`.
+"""
+import torch
+
+from .. import hip as H
+from ..util.misc import NestedTensor
+
+
+def _token_shapes(samples):
+    """The fields a canvas leaves alone (sentence, phrase, their masks and positions ...): name -> shape without the batch axis."""
+    return tuple((k, tuple(v.shape[1:])) for k, v in sorted(samples.items()) if torch.is_tensor(v))
+
+
+class StagedBatch:
+    """The static buffers of one canvas batch: `samples` (the canvas-sized 'img' NestedTensor + the token fields), `targets_static`
+    = (boxes [B * boxes_per_image, 4] fp32, tgt_off [B + 1] int32, num_boxes [1] fp32) and `tgt_masks` (uint8 [B, 1, H, W] or None)."""
+
+    def __init__(self, samples, targets_static, tgt_masks):
+        self.samples, self.targets_static, self.tgt_masks = samples, targets_static, tgt_masks
+
+
+class BatchCanvas:
+    def __init__(self, height, width, boxes_per_image, masks=False, tokens=None):
+        self.height, self.width, self.boxes_per_image, self.masks = int(height), int(width), int(boxes_per_image), bool(masks)
+        assert self.height > 0 and self.width > 0 and self.boxes_per_image > 0
+        self.tokens = tokens                     # token field shapes, bound by the first batch (from_args / bind)
+
+    @classmethod
+    def from_args(cls, args, samples, masks=None):
+        """The canvas of a run: `max_img_size` squared (what datasets/transforms.py:84-102 can produce at most), as many boxes per
+        image as the batch has phrase slots (1 without a phrase field), target masks when the run trains the segmentation head."""
+        size = int(args.max_img_size)
+        cap = int(samples["phrase"].shape[1]) if "phrase" in samples else 1
+        if masks is None:
+            masks = bool(getattr(args, "masks", False))
+        return cls(size, size, cap, masks=masks).bind(samples)
+
+    def bind(self, samples):
+        """Fixes the token field shapes to those of `samples` (the datasets pad them to a fixed length)."""
+        self.tokens = _token_shapes(samples)
+        return self
+
+    def __repr__(self):
+        return f"BatchCanvas({self.height}, {self.width}, boxes_per_image={self.boxes_per_image}, masks={self.masks})"
+
+    def key(self, samples):
+        """What a capture on this canvas depends on: the canvas, the batch size and the token field shapes -- not the image size, not
+        the box counts, not the target mask sizes."""
+        return ("canvas", self.height, self.width, self.boxes_per_image, self.masks, int(samples["img"].tensors.shape[0]),
+                _token_shapes(samples))
+
+    def why_not(self, samples, targets):
+        """None when the batch fits, else the reason as a short phrase."""
+        img = samples.get("img")
+        if not isinstance(img, NestedTensor) or img.tensors.dim() != 4 or img.tensors.shape[1] != 3:
+            return "no [B, 3, h, w] image NestedTensor"
+        B, _, h, w = img.tensors.shape
+        if h > self.height or w > self.width:
+            return f"image {h} x {w} exceeds the canvas"
+        if B > H.BATCH_STAGE_MAX_B:
+            return f"more than {H.BATCH_STAGE_MAX_B} images"
+        if len(targets) != B:
+            return "targets do not match the batch"
+        if self.tokens is not None and _token_shapes(samples) != self.tokens:
+            return "token field shapes differ from the canvas's"
+        for t in targets:
+            n = int(t["boxes"].shape[0])
+            if "labels" in t and len(t["labels"]) != n:
+                # the existing criterion counts len(labels) into num_boxes, the staged count is the number of box rows: a canvas step is
+                # the existing step only where the two agree (they do in every dataset of the reference)
+                return f"{len(t['labels'])} labels for {n} boxes on an image"
+            if n > self.boxes_per_image:
+                return f"{n} boxes on an image, capacity {self.boxes_per_image}"
+            if self.masks:
+                m = t.get("masks")
+                if m is None or m.dim() != 3 or m.shape[0] != 1:
+                    return "no [1, h, w] target mask"
+                if m.shape[-2] > self.height or m.shape[-1] > self.width:
+                    return f"target mask {m.shape[-2]} x {m.shape[-1]} exceeds the canvas"
+        return None
+
+    def fits(self, samples, targets):
+        return self.why_not(samples, targets) is None
+
+    # ------------------------------------------------------------------ the definition, in plain torch
+    def pad_on_host(self, samples, targets):
+        """The batch as the reference's collate would deliver it with one canvas-sized image in it: new tensors, any device."""
+        assert self.fits(samples, targets), self.why_not(samples, targets)
+        img = samples["img"]
+        B, C, h, w = img.tensors.shape
+        t = img.tensors.new_zeros((B, C, self.height, self.width))
+        t[:, :, :h, :w] = img.tensors
+        m = torch.ones((B, self.height, self.width), dtype=torch.bool, device=img.mask.device)
+        m[:, :h, :w] = img.mask
+        s = dict(samples)
+        s["img"] = NestedTensor(t, m)
+        out_t = []
+        for tg in targets:
+            tg = dict(tg)
+            if self.masks:
+                src = tg["masks"]
+                pm = src.new_zeros((src.shape[0], self.height, self.width))
+                pm[:, :src.shape[-2], :src.shape[-1]] = src
+                tg["masks"] = pm
+            out_t.append(tg)
+        return s, out_t
+
+    # ------------------------------------------------------------------ the same bytes from one launch
+    def alloc(self, samples):
+        """Static buffers for batches like `samples` (B, token shapes, device); the token fields start as copies of `samples`'s."""
+        img = samples["img"]
+        dev, B = img.tensors.device, int(img.tensors.shape[0])
+        s = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in samples.items() if k != "img"}
+        s["img"] = NestedTensor(torch.empty((B, 3, self.height, self.width), dtype=torch.float32, device=dev),
+                                torch.empty((B, self.height, self.width), dtype=torch.bool, device=dev))
+        static = (torch.empty((B * self.boxes_per_image, 4), dtype=torch.float32, device=dev),
+                  torch.empty(B + 1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.float32, device=dev))
+        tm = torch.empty((B, 1, self.height, self.width), dtype=torch.uint8, device=dev) if self.masks else None
+        return StagedBatch(s, static, tm)
+
+    def stage(self, samples, targets, out=None, tokens=True):
+        """Writes the batch into `out` (a StagedBatch; a fresh one when None) with one rt_batch_stage launch on the current stream
+        and returns it.  `tokens=False` leaves the token fields to the caller (the engine copies them with its grouped copy)."""
+        assert self.fits(samples, targets), self.why_not(samples, targets)
+        fresh = out is None
+        if fresh:
+            out = self.alloc(samples)
+        img = samples["img"]
+        src = img.tensors if img.tensors.dtype == torch.float32 else img.tensors.float()
+        src_mask = img.mask if img.mask.element_size() == 1 else img.mask.bool()
+        boxes = [t["boxes"] if t["boxes"].dtype == torch.float32 else t["boxes"].float() for t in targets]
+        masks = None
+        if self.masks:
+            masks = [t["masks"] if t["masks"].element_size() == 1 else t["masks"].to(torch.uint8) for t in targets]
+            masks = [m.contiguous() for m in masks]
+        H.batch_stage(src.contiguous(), src_mask.contiguous(), out.samples["img"].tensors, out.samples["img"].mask,
+                      [b.contiguous() for b in boxes], self.boxes_per_image, *out.targets_static, mask_list=masks, tgt_masks=out.tgt_masks)
+        if tokens and not fresh:
+            for k, v in samples.items():
+                if torch.is_tensor(v):
+                    out.samples[k].copy_(v, non_blocking=True)
+        return out

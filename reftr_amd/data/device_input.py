@@ -15,8 +15,10 @@ STD = (0.229, 0.224, 0.225)
 
 
 class DeviceInputPipeline:
-    def __init__(self, size, max_size=None, mean=MEAN, std=STD, device="cuda"):
+    def __init__(self, size, max_size=None, mean=MEAN, std=STD, device="cuda", pad_to=None):
+        """pad_to = (H, W): every batch is collated straight to that size (a BatchCanvas's) instead of to its own largest image."""
         self.size, self.max_size, self.mean, self.std = size, max_size, mean, std
+        self.pad_to = None if pad_to is None else (int(pad_to[0]), int(pad_to[1]))
         self.device = torch.device(device)
         self._taps = {}
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -56,6 +58,10 @@ class DeviceInputPipeline:
             if targets is not None:
                 out_t.append(self._target(targets[i], (Hh, Ww), (oh, ow)))
         Hm = max(r.shape[0] for r in resized); Wm = max(r.shape[1] for r in resized)
+        if self.pad_to is not None:
+            if Hm > self.pad_to[0] or Wm > self.pad_to[1]:
+                raise ValueError(f"a resized image ({Hm} x {Wm} over the batch) exceeds pad_to = {self.pad_to}")
+            Hm, Wm = self.pad_to
         batch, mask = H.img_collate_norm(resized, Hm, Wm, self.mean, self.std)
         return NestedTensor(batch, mask.bool()), (out_t if targets is not None else None)
 

@@ -166,9 +166,54 @@ def _window_last(optimizer, accum_steps, window_end):
     return optimizer.accum_count + 1 >= accum_steps
 
 
-def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, accum_steps=1, window_end=None):
+def _canvas_single_process(model):
+    inner = _inner(model)
+    if model is not inner or getattr(inner, "dp_mode", False) or (utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1):
+        raise NotImplementedError("canvas= is not available under the data-parallel wrapper: the box count a canvas step reads is the "
+                                  "world average (one all-reduce per batch) and the choice between replay and capture is collective; "
+                                  "neither has been run on more than one rank with a canvas")
+
+
+def _canvas_fits(model, canvas, samples, targets):
+    """Whether this batch goes through the batch canvas (reftr_amd.data.canvas).  A batch that does not fit -- a larger image, more
+    boxes than the capacity, other token lengths -- takes the existing path at its own shape; said once per shape, because a run
+    that quietly leaves the canvas pays a capture or the eager launches (2-3x slower) for every such batch."""
+    _canvas_single_process(model)
+    inner = _inner(model)
+    why = canvas.why_not(samples, targets)
+    if why is None:
+        return True
+    seen = inner.__dict__.setdefault("_canvas_misfit_logged", set())
+    key = CapturedTrainStep.shape_key(samples, targets) if isinstance(samples.get("img"), utils.NestedTensor) else why
+    if key not in seen:
+        seen.add(key)
+        print(f"[reftr_amd] batch does not fit {canvas!r} ({why}): it runs at its own shape, captured if fewer than max_shapes shapes "
+              "are in use, else eagerly", file=sys.stderr)
+    return False
+
+
+def _train_step_canvas(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end, canvas):
+    """train_step on the canvas form of the batch: staged by rt_batch_stage into fresh buffers (device batches; the criterion reads
+    the staged targets), or padded by canvas.pad_on_host (host batches).  The same step as `train_step` of the padded batch."""
+    img = samples.get("img")
+    if not (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and hasattr(criterion, "targets_static")):
+        samples, targets = canvas.pad_on_host(samples, targets)
+        return train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end)
+    staged = canvas.stage(samples, targets)
+    criterion.targets_static, criterion.target_masks_static = staged.targets_static, staged.tgt_masks
+    try:
+        return train_step(model, criterion, staged.samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end)
+    finally:
+        criterion.targets_static = criterion.target_masks_static = None
+
+
+def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, accum_steps=1, window_end=None,
+               canvas=None):
     """The loop body, engine_vg.py:40-72.  Returns (loss_value, reduced scaled dict, reduced unscaled dict,
     grad_norm tensor).
+
+    canvas (a reftr_amd.data.canvas.BatchCanvas): the step is computed on the batch padded to the canvas -- what a replayed canvas
+    step computes; a batch that does not fit the canvas runs as without one.
 
     accum_steps = k > 1 (gradient accumulation: the published 8 x 8 global batch on one GPU): the call is ONE micro-batch of a
     window of k.  Micro-batches 1 ... k-1 run forward, criterion, the fast zero_grad, backward and optimizer.accumulate(); they
@@ -177,6 +222,8 @@ def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None,
     (optimizer.finish_accumulation(), s = 1 / r), then clips, updates and steps the scheduler ONCE and returns the norm of the
     averaged gradient.  The non-finite-loss stop and the cooperative decoder's re-run act on every micro-batch."""
     accum_steps = int(accum_steps)
+    if canvas is not None and _canvas_fits(model, canvas, samples, targets):
+        return _train_step_canvas(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end, canvas)
     if accum_steps > 1:
         _require_accumulation(optimizer)
     if hasattr(optimizer, "veto") and hasattr(_inner(model), "coop_failure_word"):
@@ -290,7 +337,7 @@ def _capture(graph, **kw):
 class CapturedTrainStep:
     """The loop body (engine_vg.py:40-72) captured into HIP graphs for one input shape.
 
-    A step is ~1500 kernel launches; replaying them from a hipGraph removes the per-launch host cost.  Everything
+    A step is 427 kernel launches; replaying them from a hipGraph removes the per-launch host cost.  Everything
     that changes from step to step lives in device memory (dropout step-seed word, optimizer step counter, the
     input batch copied into static buffers), so replays are real training steps.  With world_size > 1 the body is
     three graphs (forward + backward phase 1 | ResNet backward | clip + AdamW) around the two eager, asynchronous
@@ -308,16 +355,29 @@ class CapturedTrainStep:
     `accumulate=True` (gradient accumulation, begin_train_step(accum_steps > 1)): the graph is forward + loss + backward ONLY -- no
     optimizer node of any kind, so no update can run between the micro-batches of a window.  The caller launches
     optimizer.accumulate(), or finish_accumulation() + clip + update, eagerly between replays.
+
+    `canvas` (reftr_amd.data.canvas.BatchCanvas): the static buffers have the canvas's size and the criterion reads boxes, offsets,
+    box count and target masks from device buffers (`criterion.targets_static`), all of them rewritten by ONE rt_batch_stage launch
+    per batch -- so the one capture serves every batch that fits the canvas, whatever its image size, box counts and mask sizes.
     """
 
     def __init__(self, model, criterion, optimizer, max_norm, samples, targets, warmup=2, force_two_phase=False, force_phases=None,
-                 accumulate=False):
+                 accumulate=False, canvas=None):
         self.model, self.criterion, self.optimizer, self.max_norm = model, criterion, optimizer, max_norm
         self.accumulate = bool(accumulate)
         self.inner = getattr(model, "module", model)
         self.ddp = model if model is not self.inner else None
-        self.s, self.t = _clone_batch(samples, targets)
-        self.key = self.shape_key(samples, targets)
+        self.canvas, self.staged = canvas, None
+        if canvas is None:
+            self.s, self.t = _clone_batch(samples, targets)
+            self.key = self.shape_key(samples, targets)
+        else:
+            assert self.ddp is None, "the canvas is a single-process schedule"
+            if canvas.tokens is None:
+                canvas.bind(samples)                 # the token field shapes of the capture: other lengths no longer fit
+            self.staged = canvas.stage(samples, targets)              # fresh canvas-sized buffers, filled with this batch
+            self.s, self.t = self.staged.samples, [{} for _ in targets]      # the criterion reads the staged targets alone
+            self.key = canvas.key(samples)
         self._lrs = [g["lr"] for g in optimizer.param_groups]
         inner = self.inner
         # the cooperative decoder's failure word vetoes an iteration's update on the device and travels in the stats vector
@@ -370,6 +430,7 @@ class CapturedTrainStep:
             tail = lambda: None                      # noqa: E731  (the optimizer's launches stay outside the graph)
             self.grad_norm = None                    # (the window's norm is the eager clip's: _AccumInFlight)
         try:
+            self._static_targets(True)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -405,6 +466,13 @@ class CapturedTrainStep:
             inner._phase_hooks, inner._post_backward_hooks = self._phase_hooks, self._post
             inner._stops = frozenset()
             criterion.num_boxes_static = None
+            self._static_targets(False)
+
+    def _static_targets(self, on):
+        """On a canvas the criterion reads the staged targets while this capture is built (inside the constructor's try / finally)."""
+        if self.staged is not None:
+            st = self.staged
+            self.criterion.targets_static, self.criterion.target_masks_static = (st.targets_static, st.tgt_masks) if on else (None, None)
 
     # ------------------------------------------------------------------ deferred optimizer schedule
     def _deferred_hooks(self):
@@ -434,6 +502,7 @@ class CapturedTrainStep:
         inner, opt = self.inner, self.optimizer
         self._deferred_hooks()
         try:
+            self._static_targets(True)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -455,6 +524,7 @@ class CapturedTrainStep:
             inner._phase_hooks, inner._post_backward_hooks = self._phase_hooks, self._post
             inner._stops = frozenset()
             self.criterion.num_boxes_static = None
+            self._static_targets(False)
 
     def _set_flush(self, on):
         f = self.flush if on else None
@@ -652,24 +722,40 @@ class CapturedTrainStep:
         any other batch of the captured shape is copied in (one small copy per field) before the replay."""
         return self.s, self.t
 
+    def accepts(self, samples, targets):
+        """Whether this capture can replay the batch: its shape key -- or, on a canvas, any batch that fits."""
+        if self.canvas is not None:
+            return self.canvas.key(samples) == self.key and self.canvas.fits(samples, targets)
+        return self.shape_key(samples, targets) == self.key
+
+    def _fill(self, samples, targets):
+        """The batch into the static buffers: the grouped copy, or on a canvas one rt_batch_stage launch for image, padding mask,
+        boxes, offsets, box count and target masks plus the grouped copy for the fixed-shape token fields."""
+        if self.canvas is None:
+            return _copy_batch(self.s, self.t, samples, targets)
+        if samples is self.s:
+            return
+        self.canvas.stage(samples, targets, out=self.staged, tokens=False)
+        _copy_batch(self.s, [], {k: v for k, v in samples.items() if k != "img"}, [])
+
     def stage(self, samples, targets):
         """Copies the NEXT batch into the static input buffers now -- stream-ordered behind the replay that is still running,
         while the host would otherwise idle in front of the iteration's device -> host copy -- so that the next call only has to
         launch the graph.  Returns False (and does nothing) for a batch of another shape."""
-        if samples is None or self.shape_key(samples, targets) != self.key:
+        if samples is None or not self.accepts(samples, targets):
             return False
-        _copy_batch(self.s, self.t, samples, targets)
+        self._fill(samples, targets)
         self._staged = (samples, targets)
         return True
 
     def _stage_in(self, samples, targets):
         staged, self._staged = self._staged, None
         if staged is None or staged[0] is not samples or staged[1] is not targets:
-            _copy_batch(self.s, self.t, samples, targets)
+            self._fill(samples, targets)
 
     def __call__(self, samples, targets, nb_reduced=None):
         staged = self._staged is not None and self._staged[0] is samples and self._staged[1] is targets
-        assert staged or (samples is self.s and targets is self.t) or self.shape_key(samples, targets) == self.key, \
+        assert staged or (samples is self.s and targets is self.t) or self.accepts(samples, targets), \
             "captured for another input shape; use train_step"
         if self.inner._operands_dirty:        # the masters were changed outside an optimizer step (load_state_dict, a restored
             self.inner.refresh_now()          # snapshot): the graph no longer carries an operand refresh of its own
@@ -840,7 +926,7 @@ class _AccumInFlight:
 
 
 def _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead, accum_steps,
-                      window_end):
+                      window_end, canvas=None):
     """begin_train_step for accum_steps > 1: forward + loss + backward replayed from one hipGraph per input shape
     (CapturedTrainStep(accumulate=True)); accumulate / average + clip + update launched eagerly behind it (_AccumInFlight)."""
     _require_accumulation(optimizer)
@@ -851,20 +937,24 @@ def _begin_accum_step(model, criterion, samples, targets, optimizer, lr_schedule
     ok = (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and not dist_on and model is inner
           and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1")
     key = None
+    if canvas is not None and not _canvas_fits(model, canvas, samples, targets):
+        canvas = None                                 # the existing path, at the batch's own shape
     if ok:
-        key = (CapturedTrainStep.shape_key(samples, targets), id(criterion), id(optimizer), "accumulate", model.training)
+        skey = canvas.key(samples) if canvas is not None else CapturedTrainStep.shape_key(samples, targets)
+        key = (skey, id(criterion), id(optimizer), "accumulate", model.training)
         ok = key in caps or len(caps) < max_shapes
     for k_, other in caps.items():                # a pending (deferred) update of a plain capture lands before anything else runs
         if k_ != key:
             other.flush()
     inner.__dict__["_staged_cap"] = None
     if not ok:
-        return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end))
+        return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end,
+                                       canvas=canvas))
     cap = caps.get(key)
     if cap is None:
         # the capture's warm-up iterations are forward + backward only: no weight or optimizer state moves, but the dropout seed does
         snap = (inner.seed_dev.clone(), inner._step)
-        cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, accumulate=True)
+        cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, accumulate=True, canvas=canvas)
         cap.training = model.training
         inner.seed_dev.copy_(snap[0]); inner._step = snap[1]
     last = _window_last(optimizer, accum_steps, window_end)
@@ -881,12 +971,12 @@ def _begin_accum_step(model, criterion, samples, targets, optimizer, lr_schedule
         _coop_fallback(model)
         _restore_seed(model, seed_back)
         return _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, None,
-                                 accum_steps, last).finish()
+                                 accum_steps, last, canvas).finish()
     return _AccumInFlight(cap, criterion, optimizer, lr_scheduler, max_norm, last, _retry, slot)
 
 
 def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None,
-                     accum_steps=1, window_end=None):
+                     accum_steps=1, window_end=None, canvas=None):
     """Launches one iteration of the loop body and returns a handle; `handle.finish()` waits for it and returns what
     `train_step` returns.  Between the two the caller may do host work (the epoch loop books the previous iteration's meters).
 
@@ -902,17 +992,24 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
     accum_steps > 1 (see train_step): one micro-batch of an accumulation window.  The replayed graph is forward + loss + backward
     alone; `finish` reads the losses and then launches accumulate() -- or, for the window's last micro-batch, the average, the clip,
     the update and the scheduler step -- eagerly, so the update of a window is applied at its end and never between two of its
-    micro-batches."""
+    micro-batches.
+
+    canvas (reftr_amd.data.canvas.BatchCanvas; single process): every batch that fits the canvas is staged into ONE capture's
+    canvas-sized buffers by one rt_batch_stage launch and replayed -- the capture key is the canvas, the batch size and the token field
+    shapes, not the batch's own shape.  A batch that does not fit runs exactly as without a canvas (own shape, `max_shapes`)."""
+    if canvas is not None:
+        _canvas_single_process(model)                 # refused before anything is launched
     if int(accum_steps) > 1:
         return _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead,
-                                 int(accum_steps), window_end)
+                                 int(accum_steps), window_end, canvas)
     inner = getattr(model, "module", model)
     caps = inner.__dict__.setdefault("_captured_steps", {})
     dist_on = utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1
     nb_reduced = None
     cap = inner.__dict__.get("_staged_cap")
     if cap is not None and not dist_on and cap._staged is not None and cap._staged[0] is samples and cap._staged[1] is targets \
-            and cap.criterion is criterion and cap.optimizer is optimizer and cap.max_norm == max_norm and cap.training == model.training:
+            and cap.criterion is criterion and cap.optimizer is optimizer and cap.max_norm == max_norm and cap.training == model.training \
+            and cap.canvas is canvas:
         pass                                                   # steady state: staged by the previous iteration's lookahead
     else:
         cap = None
@@ -920,8 +1017,10 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
         ok = (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and hasattr(optimizer, "clip_grad_norm_")
               and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1")
         key = None
+        on_canvas = canvas if canvas is not None and _canvas_fits(model, canvas, samples, targets) else None
         if ok:
-            key = (CapturedTrainStep.shape_key(samples, targets), id(criterion), id(optimizer), float(max_norm), model.training)
+            skey = on_canvas.key(samples) if on_canvas is not None else CapturedTrainStep.shape_key(samples, targets)
+            key = (skey, id(criterion), id(optimizer), float(max_norm), model.training)
             ok = key in caps or len(caps) < max_shapes
         if dist_on:
             # Data parallel: replaying, capturing and the eager loop issue DIFFERENT collective sequences (a capture adds the
@@ -948,7 +1047,7 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
         if not ok:
             for other in caps.values():             # a pending (deferred) update must land before the eager forward
                 other.flush()
-            return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm))
+            return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, canvas=on_canvas))
         cap = caps.get(key)
         if cap is None:
             for other in caps.values():             # one pending (deferred) update at a time
@@ -958,7 +1057,7 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
             st = inner.store
             snap = (st.flat_p.clone(), optimizer.m.clone(), optimizer.v.clone(), optimizer.step_dev.clone(), optimizer.step_count,
                     inner.seed_dev.clone(), inner._step)
-            cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets)
+            cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, canvas=on_canvas)
             cap.training = model.training
             cap.reset_pending()
             st.flat_p.copy_(snap[0]); optimizer.m.copy_(snap[1]); optimizer.v.copy_(snap[2]); optimizer.step_dev.copy_(snap[3])
@@ -1006,7 +1105,8 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
         for g, lr in zip(optimizer.param_groups, lrs_now):
             g["lr"] = lr
         try:
-            return begin_train_step(model, criterion, samples, targets, optimizer, None, max_norm, max_shapes, None).finish()
+            return begin_train_step(model, criterion, samples, targets, optimizer, None, max_norm, max_shapes, None,
+                                    canvas=canvas).finish()
         finally:
             for g, lr in zip(optimizer.param_groups, after):
                 g["lr"] = lr
@@ -1014,10 +1114,10 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
 
 
 def captured_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None,
-                        accum_steps=1, window_end=None):
+                        accum_steps=1, window_end=None, canvas=None):
     """`train_step` with the same return value, on `begin_train_step` (launch) + `finish` (read-out)."""
     return begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead,
-                            accum_steps, window_end).finish()
+                            accum_steps, window_end, canvas).finish()
 
 
 def _check_cooperative(model):
@@ -1029,13 +1129,17 @@ def _check_cooperative(model):
         raise RuntimeError("rt_decoder_fwd: a stage hand-off timed out (workgroups not co-resident?) -- set REFTR_DEC_COOP=0")
 
 
-def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, device, epoch, max_norm=0, accum_steps=1):
+def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, device, epoch, max_norm=0, accum_steps=1, canvas=None):
     """engine_vg.py:22-79.  accum_steps = k > 1: every k batches of the loader form one accumulation window -- one clip, one update
     and one lr_scheduler.step() per window, on the mean of its gradients (see train_step).  The last window of an epoch may be cut
     short: it is finished with the r < k batches it has (s = 1 / r); no batch is dropped and nothing is carried into the next epoch.
     The stats board receives one row per micro-batch (its loss terms and the learning rate); `grad_norm` -- the norm of the window's
-    averaged gradient -- is booked once per window, on the row of its last micro-batch."""
+    averaged gradient -- is booked once per window, on the row of its last micro-batch.
+    canvas (reftr_amd.data.canvas.BatchCanvas, e.g. BatchCanvas.from_args(args, first_samples)): variable-shape data -- per-batch
+    image padding, ragged box counts, per-image mask sizes -- replayed from ONE capture (see begin_train_step)."""
     accum_steps = int(accum_steps)
+    if canvas is not None:
+        _canvas_single_process(model)
     if accum_steps > 1:
         _require_accumulation(optimizer)
         optimizer.accum_count = 0                 # a window never spans two epochs
@@ -1064,14 +1168,15 @@ def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, devi
         return row
 
     for it in board.log_every(range(n_batches), 50, header):
-        # the loop body of engine_vg.py:40-72 -- replayed from hipGraphs for fixed-shape data (RefCOCO: 640 x 640, L = 40);
+        # the loop body of engine_vg.py:40-72 -- replayed from hipGraphs for fixed-shape data (RefCOCO: 640 x 640, L = 40), or, with a
+        # canvas, for every batch that fits it;
         # the replayed path hands back host numbers (one stacked copy per iteration), the eager one device scalars.
         ahead = Lookahead(prefetcher.next)
         if accum_steps > 1:
             step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead,
-                                    accum_steps=accum_steps, window_end=(it + 1) % accum_steps == 0 or it + 1 == n_batches)
+                                    accum_steps=accum_steps, window_end=(it + 1) % accum_steps == 0 or it + 1 == n_batches, canvas=canvas)
         else:
-            step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead)
+            step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead, canvas=canvas)
         step.lr_logged = optimizer.param_groups[0]["lr"]      # what the reference's meter shows: the rate after this iteration's scheduler step
         if booked is not None:
             board.add(**booked)

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2, 3
 _c_float_p = POINTER(c_float)
@@ -360,6 +360,9 @@ _SIGNATURES = {
     "rt_small_wgrad_grouped": (c_int, [POINTER(SmallWgradJob), c_int, c_void_p]),
     "rt_resample_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rt_img_collate_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p]),
+    "rt_batch_stage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, POINTER(c_void_p),
+                               POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(ctypes.c_int32),
+                               c_void_p, c_void_p]),
     "rt_gn_nhwc_fwd": (c_int, [POINTER(GnNhwcDesc), c_void_p]),
     "rt_gn_nhwc_bwd": (c_int, [POINTER(GnNhwcBwdDesc), c_void_p]),
     "rt_upsample_add": (c_int, [POINTER(UpsampleAddDesc), c_void_p]),
@@ -1636,6 +1639,39 @@ def img_collate_norm(images, H, W, mean, std):
     m = (c_float * 3)(*[float(v) for v in mean]); s_ = (c_float * 3)(*[float(v) for v in std])
     _check(lib().rt_img_collate_norm(_p(tab), _p(out), _p(mask), B, H, W, m, s_, _stream()), "rt_img_collate_norm")
     return out, mask
+
+
+BATCH_STAGE_MAX_B = 64          # RT_BATCH_STAGE_MAX_B: what fits the kernel's argument block
+
+
+def batch_stage(src_img, src_mask, img, mask, box_list, boxes_per_image, boxes, tgt_off, num_boxes, mask_list=None, tgt_masks=None):
+    """rt_batch_stage: one batch of any size into fixed canvas buffers, one launch, every destination byte rewritten.
+    src_img fp32 [B,3,hs,ws] / src_mask bool|u8 [B,hs,ws] -> img fp32 [B,3,Hc,Wc] (zero padded) / mask [B,Hc,Wc] (1 = padding);
+    box_list: B fp32 [n_b, 4] device tensors -> boxes [B*boxes_per_image, 4] packed, tgt_off int32 [B+1], num_boxes fp32 [1];
+    mask_list (optional): B one-byte [1, h_b, w_b] device tensors -> tgt_masks u8 [B,1,Hc,Wc].  The pointers and sizes go by value in
+    the kernel arguments: nothing is copied to the device and nothing synchronises."""
+    _req(src_img, torch.float32, "src_img"); _req(img, torch.float32, "img")
+    _req(boxes, torch.float32, "boxes"); _req(tgt_off, torch.int32, "tgt_off"); _req(num_boxes, torch.float32, "num_boxes")
+    B, _, hs, ws = src_img.shape
+    Hc, Wc = img.shape[-2:]
+    assert src_img.is_contiguous() and src_mask.is_contiguous() and src_mask.element_size() == 1
+    assert img.is_contiguous() and mask.is_contiguous() and mask.element_size() == 1
+    assert tuple(img.shape) == (B, 3, Hc, Wc) and tuple(mask.shape) == (B, Hc, Wc) and tuple(src_mask.shape) == (B, hs, ws)
+    assert len(box_list) == B and boxes.numel() == B * boxes_per_image * 4 and tgt_off.numel() == B + 1 and num_boxes.numel() == 1
+    for t in box_list:
+        assert t.numel() == 0 or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4)
+    bp = (c_void_p * B)(*[t.data_ptr() if t.numel() else None for t in box_list])
+    bn = (ctypes.c_int32 * B)(*[t.shape[0] for t in box_list])
+    tp = thw = None
+    if mask_list is not None:
+        assert len(mask_list) == B and tgt_masks is not None and tgt_masks.numel() == B * Hc * Wc and tgt_masks.element_size() == 1
+        for t in mask_list:
+            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous() and t.numel() == t.shape[-2] * t.shape[-1]
+        tp = (c_void_p * B)(*[t.data_ptr() for t in mask_list])
+        thw = (ctypes.c_int32 * (2 * B))(*[v for t in mask_list for v in t.shape[-2:]])
+    _check(lib().rt_batch_stage(_p(src_img), _p(src_mask), B, hs, ws, _p(img), _p(mask), Hc, Wc, bp, bn, int(boxes_per_image), _p(boxes),
+                                _p(tgt_off), _p(num_boxes), tp, thw, _p(tgt_masks) if mask_list is not None else None, _stream()),
+           "rt_batch_stage")
 
 
 # --------------------------------------------------------------------------------------------

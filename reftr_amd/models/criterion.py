@@ -36,6 +36,11 @@ class CriterionVGMultiPhrase(nn.Module):
         self._off_cache = {}
         self._nb_cache = {}
         self.num_boxes_static = None      # CapturedTrainStep: device scalar it refreshes (all-reduced) before every replay
+        # batch canvas (reftr_amd.data.canvas): (boxes [cap, 4], tgt_off [B + 1], num_boxes [1]) staged on the device by rt_batch_stage.
+        # While it is set the criterion reads the targets from there alone -- `targets` is not looked at, no host-built offsets or
+        # counts (_off_cache / _nb_cache) enter -- and the segmentation criterion reads `target_masks_static` (uint8 [B, 1, H, W])
+        self.targets_static = None
+        self.target_masks_static = None
 
     def _targets(self, targets, device):
         lens = tuple(int(t["boxes"].shape[0]) for t in targets)
@@ -73,8 +78,7 @@ class CriterionVGMultiPhrase(nn.Module):
             logits = logits[-1:]
         logits = logits.contiguous()
         device = logits.device
-        num_boxes = self.num_boxes(targets, device)
-        boxes, off = self._targets(targets, device)
+        boxes, off, num_boxes = self.prepare(targets, device)
         valid = H.as_u8(outputs["phrase_mask"])
         losses = _BoxLossFunction.apply(logits, valid, boxes, off, num_boxes)     # [NL, 2]
         return self._loss_dict(losses)
@@ -91,6 +95,8 @@ class CriterionVGMultiPhrase(nn.Module):
     def prepare(self, targets, device):
         """The part of `forward` that only reads the targets: (boxes [sum n_i, 4] fp32, offsets, num_boxes).  The captured
         training step issues it at the head of the step on the side stream, off the chain the model's forward runs on."""
+        if self.targets_static is not None:
+            return self.targets_static
         num_boxes = self.num_boxes(targets, device)
         boxes, off = self._targets(targets, device)
         return boxes, off, num_boxes
@@ -188,7 +194,11 @@ class CriterionVGOnePhraseSeg(CriterionVGMultiPhrase):
             pm = outputs["pred_masks"]
             bs, nq = pm.shape[:2]
             assert nq == 1, "RefTRSeg predicts one mask per image (n_ph = n_q = 1)"
-            tgt = self._padded_masks(targets, pm.device)
+            if self.targets_static is not None:
+                tgt = self.target_masks_static
+                assert tgt is not None, "the batch canvas was built without masks=True"
+            else:
+                tgt = self._padded_masks(targets, pm.device)
             lm = _MaskLossFunction.apply(pm, tgt, float(bs * nq))
             self._last_mask = lm
             losses["loss_mask"], losses["loss_dice"] = lm[0], lm[1]
