@@ -85,6 +85,33 @@ def _inner(model):
     return getattr(model, "module", model)
 
 
+def _multi_rank():
+    return utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1
+
+
+class _StepState:
+    """What the step machinery keeps per model beside `model._captured_steps`: the capture that holds the staged next batch, the
+    count of cooperative-decoder fall-backs (CapturedForward drops its graphs when it moves), and what was already said once."""
+
+    def __init__(self):
+        self.staged_cap, self.coop_generation, self.said = None, 0, set()
+
+
+def _state(model):
+    d = _inner(model).__dict__
+    st = d.get("_step_state")
+    if st is None:
+        st = d["_step_state"] = _StepState()
+    return st
+
+
+def _say_once(model, key, text):
+    said = _state(model).said
+    if key not in said:
+        said.add(key)
+        print(text, file=sys.stderr)
+
+
 def _seed_state(model):
     """(device dropout step-seed word, host step count) BEFORE this iteration's forward advanced them (train_step reads them
     after the forward: one step back)."""
@@ -113,7 +140,7 @@ def _cooperative_failed(model):
     if fw is None:                                     # no cooperative launches in this build / configuration: the same on every rank
         return False
     launched = getattr(inner.net, "dec_counters", None) is not None      # rank-local (depends on this rank's batch shape)
-    if utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1:
+    if _multi_rank():
         # every rank enters the collective; a rank that has not launched the cooperative decoder yet contributes 0
         f = fw.to(torch.int32).clone() if launched else torch.zeros_like(fw, dtype=torch.int32)
         torch.distributed.all_reduce(f, op=torch.distributed.ReduceOp.MAX)
@@ -142,8 +169,9 @@ def _coop_fallback(model):
         if getattr(cap.optimizer, "veto", None) is not None:
             cap.optimizer.veto = None
     caps.clear()
-    inner.__dict__["_staged_cap"] = None
-    inner.__dict__["_coop_generation"] = inner.__dict__.get("_coop_generation", 0) + 1     # CapturedForward drops its graphs
+    state = _state(model)
+    state.staged_cap = None
+    state.coop_generation += 1                         # CapturedForward drops its graphs
     if not _COOP_LOGGED:
         _COOP_LOGGED = True
         print("[reftr_amd] rt_decoder_fwd / rt_decoder_bwd: a stage hand-off timed out (workgroups not co-resident?). The iteration "
@@ -168,7 +196,7 @@ def _window_last(optimizer, accum_steps, window_end):
 
 def _canvas_single_process(model):
     inner = _inner(model)
-    if model is not inner or getattr(inner, "dp_mode", False) or (utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1):
+    if model is not inner or getattr(inner, "dp_mode", False) or _multi_rank():
         raise NotImplementedError("canvas= is not available under the data-parallel wrapper: the box count a canvas step reads is the "
                                   "world average (one all-reduce per batch) and the choice between replay and capture is collective; "
                                   "neither has been run on more than one rank with a canvas")
@@ -179,17 +207,45 @@ def _canvas_fits(model, canvas, samples, targets):
     boxes than the capacity, other token lengths -- takes the existing path at its own shape; said once per shape, because a run
     that quietly leaves the canvas pays a capture or the eager launches (2-3x slower) for every such batch."""
     _canvas_single_process(model)
-    inner = _inner(model)
     why = canvas.why_not(samples, targets)
     if why is None:
         return True
-    seen = inner.__dict__.setdefault("_canvas_misfit_logged", set())
     key = CapturedTrainStep.shape_key(samples, targets) if isinstance(samples.get("img"), utils.NestedTensor) else why
-    if key not in seen:
-        seen.add(key)
-        print(f"[reftr_amd] batch does not fit {canvas!r} ({why}): it runs at its own shape, captured if fewer than max_shapes shapes "
-              "are in use, else eagerly", file=sys.stderr)
+    _say_once(model, ("canvas", key), f"[reftr_amd] batch does not fit {canvas!r} ({why}): it runs at its own shape, captured if fewer "
+              "than max_shapes shapes are in use, else eagerly")
     return False
+
+
+_UNSCALED = "{}_unscaled".format          # a loss term's name on the stats board beside its weighted value
+
+
+def _read_out(values, weight_dict):
+    """The loop's read-out of one iteration (engine_vg.py:46-58): named loss values -- reduced device scalars on the eager path, host
+    floats on the replayed one -- to (loss_value, weighted dict, unweighted dict); a non-finite total stops the run before the update.
+    loss_value is a Python float either way (one .item() for device scalars); the dicts keep the type of what came in."""
+    unscaled = {_UNSCALED(k): v for k, v in values.items()}
+    scaled = {k: v * weight_dict[k] for k, v in values.items() if k in weight_dict}
+    loss_value = sum(scaled.values())
+    on_device = torch.is_tensor(loss_value)
+    if on_device:
+        loss_value = loss_value.item()
+    if not math.isfinite(loss_value):
+        print("Loss is {}, stopping training".format(loss_value))
+        print(values if on_device else unscaled)
+        sys.exit(1)
+    return loss_value, scaled, unscaled
+
+
+def _eager_iteration(model, criterion, samples, targets, optimizer):
+    """Forward, criterion, total, the reduced read-out with its non-finite stop, gradient clear and backward of one (micro-)batch:
+    what train_step runs once, and once more after a cooperative decoder fall-back.  Returns what _read_out returns."""
+    outputs = model(samples)
+    loss_dict = criterion(outputs, targets)
+    losses = _total(criterion, loss_dict)
+    res = _read_out(utils.reduce_dict(loss_dict), criterion.weight_dict)
+    _zero_grad(optimizer)
+    losses.backward()
+    return res
 
 
 def _train_step_canvas(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end, canvas):
@@ -228,41 +284,29 @@ def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None,
         _require_accumulation(optimizer)
     if hasattr(optimizer, "veto") and hasattr(_inner(model), "coop_failure_word"):
         optimizer.veto = _inner(model).coop_failure_word()
-    outputs = model(samples)
-    loss_dict = criterion(outputs, targets)
-    weight_dict = criterion.weight_dict
-    losses = _total(criterion, loss_dict)
-    loss_dict_reduced = utils.reduce_dict(loss_dict)
-    unscaled = {f"{k}_unscaled": v for k, v in loss_dict_reduced.items()}
-    scaled = {k: v * weight_dict[k] for k, v in loss_dict_reduced.items() if k in weight_dict}
-    loss_value = sum(scaled.values()).item()
-    if not math.isfinite(loss_value):
-        print("Loss is {}, stopping training".format(loss_value))
-        print(loss_dict_reduced)
-        sys.exit(1)
-    _zero_grad(optimizer)
-    seed0 = _seed_state(model)
-    losses.backward()
+    res = _eager_iteration(model, criterion, samples, targets, optimizer)
     if _cooperative_failed(model):
         # a stage hand-off of the cooperative decoder launches timed out: this iteration's activations / gradients are void.
         # The reference stops BEFORE the update when an iteration is bad (engine_vg.py:55-58); here the launches are switched
         # off for the process and the iteration is run again on the launched chain (same dropout seeds), then updated as usual
         _coop_fallback(model)
-        _restore_seed(model, seed0)
-        outputs = model(samples)
-        loss_dict = criterion(outputs, targets)
-        losses = _total(criterion, loss_dict)
-        loss_dict_reduced = utils.reduce_dict(loss_dict)
-        unscaled = {f"{k}_unscaled": v for k, v in loss_dict_reduced.items()}
-        scaled = {k: v * weight_dict[k] for k, v in loss_dict_reduced.items() if k in weight_dict}
-        loss_value = sum(scaled.values()).item()
-        _zero_grad(optimizer)
-        losses.backward()
-    if accum_steps > 1:
-        if not _window_last(optimizer, accum_steps, window_end):
+        _restore_seed(model, _seed_state(model))
+        res = _eager_iteration(model, criterion, samples, targets, optimizer)
+    last = _window_last(optimizer, accum_steps, window_end) if accum_steps > 1 else None
+    return (*res, _update(model, optimizer, lr_scheduler, max_norm, last))
+
+
+def _update(model, optimizer, lr_scheduler, max_norm, last=None, sync_lr=False):
+    """What follows an iteration's backward, eager or replayed; returns the gradient norm.  `last` says that the iteration is a
+    micro-batch of an accumulation window and whether it closes it: inside the window the gradients go to the accumulator and
+    nothing else happens (None); the last one averages the window first.  Then clip, update and scheduler step, once."""
+    if last is not None:
+        if not last:
             optimizer.accumulate()
-            return loss_value, scaled, unscaled, None
+            return None
         optimizer.finish_accumulation()
+    if sync_lr and getattr(optimizer, "lr_dev", None) is not None:
+        optimizer.sync_lr()                  # a capture of this optimizer switched the kernel to device learning rates
     if hasattr(optimizer, "clip_grad_norm_"):
         grad_total_norm = optimizer.clip_grad_norm_(max_norm)
     elif max_norm > 0:
@@ -272,7 +316,13 @@ def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None,
     optimizer.step()
     if lr_scheduler is not None:
         lr_scheduler.step()
-    return loss_value, scaled, unscaled, grad_total_norm
+    return grad_total_norm
+
+
+def _sample_shapes(samples):
+    """((field, shape), ...) of a batch's samples: what a capture's static input buffers are sized by."""
+    return tuple((n, tuple(v.tensors.shape) if isinstance(v, utils.NestedTensor) else tuple(v.shape))
+                 for n, v in sorted(samples.items()) if isinstance(v, utils.NestedTensor) or torch.is_tensor(v))
 
 
 def _clone_batch(samples, targets):
@@ -334,6 +384,18 @@ def _capture(graph, **kw):
             gc.enable()
 
 
+def _warm_up(fn, n):
+    """`fn` n times on a side stream before it is captured (operand refresh, workspaces, descriptor tables), joined and synchronized:
+    no collective is in flight while capturing (see _CAPTURE_MODE)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(n):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+
+
 class CapturedTrainStep:
     """The loop body (engine_vg.py:40-72) captured into HIP graphs for one input shape.
 
@@ -365,7 +427,7 @@ class CapturedTrainStep:
                  accumulate=False, canvas=None):
         self.model, self.criterion, self.optimizer, self.max_norm = model, criterion, optimizer, max_norm
         self.accumulate = bool(accumulate)
-        self.inner = getattr(model, "module", model)
+        self.inner = _inner(model)
         self.ddp = model if model is not self.inner else None
         self.canvas, self.staged = canvas, None
         if canvas is None:
@@ -391,10 +453,8 @@ class CapturedTrainStep:
         if utils.is_dist_avail_and_initialized():
             self.nb = torch.zeros(1, dtype=torch.float32, device=self.s["sentence"].device)
             self._refresh_num_boxes(targets)
-            criterion.num_boxes_static = self.nb
         # collectives stay outside the graphs: the engine calls the hooks between replays
-        self._phase_hooks, inner._phase_hooks = inner._phase_hooks, {}
-        self._post, inner._post_backward_hooks = inner._post_backward_hooks, []
+        self._phase_hooks, self._post = inner._phase_hooks, inner._post_backward_hooks
         # data parallel: backward is captured as one graph per segment between the exchange points the wrapper registered
         # (RefTR.BOUNDARIES), so that each slice's all-reduce is issued the moment it is final and runs under the next graphs
         self.phases = [b for b in inner.active_boundaries() if self._phase_hooks.get(b)]
@@ -404,44 +464,45 @@ class CapturedTrainStep:
             # serial schedule: [everything but the ResNet | the ResNet]; interleaved: [... transformer backward | BERT || ResNet]
             self.phases = ["bert"] if inner.dp_schedule == "serial" else ["main"]
         self.two_phase = bool(self.phases)
-        inner._stops = frozenset(self.phases)
         can_defer = hasattr(optimizer, "enable_deferred") and os.environ.get("REFTR_DEFER_OPT", "1") == "1"
         can_defer = can_defer and not self.accumulate
         self.deferred = can_defer and not self.two_phase and not self._post
-        # data parallel (round 3): the same deferred schedule across the segment graphs -- the AdamW pass of iteration i sits at
-        # the head of iteration i+1's FIRST graph (its BERT slice on the language stream under the ResNet forward, reading the
-        # all-reduced bf16 gradients of iteration i, which nothing rewrites before this iteration's first exchange boundary), the
-        # last graph ends with the gradient norm.  (Optimizers without the deferred interface: clip + step in the last graph.)
+        # data parallel: the same deferred schedule across the segment graphs -- the AdamW pass of iteration i sits at the head of
+        # iteration i+1's FIRST graph (its BERT slice on the language stream under the ResNet forward, reading the all-reduced bf16
+        # gradients of iteration i, which nothing rewrites before this iteration's first exchange boundary), the last graph ends
+        # with the gradient norm.  (Optimizers without the deferred interface: clip + step in the last graph.)
         self.deferred_dp = can_defer and not self.deferred
         self._pending = False
         self._staged = None
+        # a schedule is [head graph | per phase: its exchange hooks, then the segment graph that follows | tail graph]; tail None:
+        # the head is the whole step
         if self.deferred:
-            self._init_deferred(warmup)
-            return
-        if hasattr(optimizer, "enable_device_lr") and not self.accumulate:
-            optimizer.enable_device_lr()
-        if self.deferred_dp:
             self._deferred_hooks()
-        head = self._head_deferred if self.deferred_dp else self._fwd_bwd
-        tail = self._tail_deferred if self.deferred_dp else self._opt
-        if self.accumulate:
-            assert not self.phases and not self._post, "accumulation is a single-process schedule"
-            head = self._fwd_bwd_stats               # the stats vector is packed inside the graph, as _opt / _tail_deferred do
-            tail = lambda: None                      # noqa: E731  (the optimizer's launches stay outside the graph)
-            self.grad_norm = None                    # (the window's norm is the eager clip's: _AccumInFlight)
-        try:
-            self._static_targets(True)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    head()
-                    for name in self.phases:
-                        self._run(self._phase_hooks.get(name, ()))
-                        inner.continue_backward()
-                    self._run(self._post); tail()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()     # no collective in flight while capturing (see _CAPTURE_MODE)
+            head, tail = self._step_deferred, None
+        else:
+            if hasattr(optimizer, "enable_device_lr") and not self.accumulate:
+                optimizer.enable_device_lr()
+            if self.deferred_dp:
+                self._deferred_hooks()
+                head, tail = self._head_deferred, self._tail_deferred
+            elif self.accumulate:
+                assert not self.phases and not self._post, "accumulation is a single-process schedule"
+                # the stats vector is packed inside the graph, as _opt / _tail_deferred do; the optimizer's launches stay outside
+                # it, and the window's norm is the eager clip's (_update)
+                head, tail, self.grad_norm = self._fwd_bwd_stats, None, None
+            else:
+                head, tail = self._fwd_bwd, self._opt
+
+        def iteration():
+            head()
+            for name in self.phases:
+                self._run(self._phase_hooks.get(name, ()))
+                inner.continue_backward()
+            self._run(self._post)
+            if tail is not None:
+                tail()
+        with self._building():
+            _warm_up(iteration, warmup)
             self.g_fb = torch.cuda.CUDAGraph()
             with _capture(self.g_fb):
                 self.out = head()
@@ -449,30 +510,43 @@ class CapturedTrainStep:
             for name in self.phases:                 # the segment that FOLLOWS boundary `name`
                 g = torch.cuda.CUDAGraph()
                 with _capture(g, pool=self.g_fb.pool()):
-                    stopped = inner.continue_backward()
+                    inner.continue_backward()
                 self.g_seg.append(g)
             assert inner._bwd_gen is None, "backward did not run to its end during capture"
             self.g_bb = self.g_seg[-1] if self.g_seg else None
             self.g_opt = None
-            if not self.accumulate:
+            if tail is not None:
                 self.g_opt = torch.cuda.CUDAGraph()
                 with _capture(self.g_opt, pool=self.g_fb.pool()):
                     tail()
-            if self.deferred_dp:
+            if self.deferred or self.deferred_dp:
                 self.grad_norm = optimizer.grad_norm
+                if self.deferred and getattr(optimizer, "_emit", False):
+                    optimizer._emit_tables(None)       # flush() applies the update over the WHOLE buffer: its job / chunk tables are built
+                                                       # now (a pageable host -> device copy later would stall the host behind queued work)
                 self._pending = True                   # the last warm-up iteration's update
                 self._set_flush(True)
+
+    @contextlib.contextmanager
+    def _building(self):
+        """While this capture is warmed up and captured: the model's exchange hooks are parked (the capture calls them itself,
+        between its graphs), backward stops at this schedule's phases, and the criterion reads the static box count and, on a canvas,
+        the staged targets.  All of it is undone on the way out, also after an error."""
+        inner, crit, st = self.inner, self.criterion, self.staged
+        inner._phase_hooks, inner._post_backward_hooks = {}, []
+        inner._stops = frozenset(self.phases)
+        if self.nb is not None:
+            crit.num_boxes_static = self.nb
+        if st is not None:
+            crit.targets_static, crit.target_masks_static = st.targets_static, st.tgt_masks
+        try:
+            yield
         finally:
             inner._phase_hooks, inner._post_backward_hooks = self._phase_hooks, self._post
             inner._stops = frozenset()
-            criterion.num_boxes_static = None
-            self._static_targets(False)
-
-    def _static_targets(self, on):
-        """On a canvas the criterion reads the staged targets while this capture is built (inside the constructor's try / finally)."""
-        if self.staged is not None:
-            st = self.staged
-            self.criterion.targets_static, self.criterion.target_masks_static = (st.targets_static, st.tgt_masks) if on else (None, None)
+            crit.num_boxes_static = None
+            if st is not None:
+                crit.targets_static = crit.target_masks_static = None
 
     # ------------------------------------------------------------------ deferred optimizer schedule
     def _deferred_hooks(self):
@@ -497,34 +571,6 @@ class CapturedTrainStep:
     def _tail_deferred(self):
         self.grad_norm = self.optimizer.finish_step(self.max_norm)
         self._pack_stats()
-
-    def _init_deferred(self, warmup):
-        inner, opt = self.inner, self.optimizer
-        self._deferred_hooks()
-        try:
-            self._static_targets(True)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    self._step_deferred()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.g_fb = torch.cuda.CUDAGraph()
-            with _capture(self.g_fb):
-                self.out = self._step_deferred()
-            self.g_bb = self.g_opt = None
-            self.grad_norm = opt.grad_norm
-            if getattr(opt, "_emit", False):
-                opt._emit_tables(None)                 # flush() applies the update over the WHOLE buffer: its job / chunk tables are built
-                                                       # now (a pageable host -> device copy later would stall the host behind queued work)
-            self._pending = True                       # the last warm-up iteration's update
-            self._set_flush(True)
-        finally:
-            inner._phase_hooks, inner._post_backward_hooks = self._phase_hooks, self._post
-            inner._stops = frozenset()
-            self.criterion.num_boxes_static = None
-            self._static_targets(False)
 
     def _set_flush(self, on):
         f = self.flush if on else None
@@ -588,14 +634,10 @@ class CapturedTrainStep:
 
     @staticmethod
     def shape_key(samples, targets):
-        k = []
-        for n, v in sorted(samples.items()):
-            k.append((n, tuple(v.tensors.shape) if isinstance(v, utils.NestedTensor) else tuple(v.shape)))
         # every tensor field of the targets is copied into the static batch (_copy_batch) and read by the criterion at its
         # captured shape: boxes, labels, masks (RefTRSeg), sizes ... all belong to the key
-        for t in targets:
-            k.append(tuple((n, tuple(v.shape)) for n, v in sorted(t.items()) if torch.is_tensor(v)))
-        return tuple(k)
+        return _sample_shapes(samples) + tuple(tuple((n, tuple(v.shape)) for n, v in sorted(t.items()) if torch.is_tensor(v))
+                                               for t in targets)
 
     def _direct_loss_ok(self):
         """The direct loss path applies when the total is the weighted sum of the box losses of THIS process's model: no wrapper
@@ -773,27 +815,18 @@ class CapturedTrainStep:
         if self.deferred:
             self._stage_in(samples, targets)
             self.g_fb.replay()                # applies iteration i-1's update with the rates synced at iteration i-1
-            lrs = [g["lr"] for g in self.optimizer.param_groups]
-            if lrs != self._lrs:              # this iteration's rates, for the update the NEXT replay (or flush) applies
-                self._lrs = lrs
-                self.optimizer.sync_lr()
+            self._sync_lr_if_changed()        # this iteration's rates, for the update the NEXT replay (or flush) applies
             self.optimizer.step_count += 1
             self._pending = True
             self._set_flush(True)
             return self.out[0], self.out[1], self.grad_norm
-        lrs = [g["lr"] for g in self.optimizer.param_groups]
-        if lrs != self._lrs and not self.deferred_dp:
-            if getattr(self.optimizer, "lr_dev", None) is not None:
-                self._lrs = lrs
-                self.optimizer.sync_lr()          # stream-ordered, in front of this iteration's optimizer graph
-            else:
-                self.refresh_lr()
+        if not self.deferred_dp:
+            self._sync_lr_if_changed()        # stream-ordered, in front of this iteration's optimizer graph
         self._stage_in(samples, targets)
         self._refresh_num_boxes(targets, reduced=nb_reduced)
         self.g_fb.replay()                # deferred: applies iteration i-1's update with the rates synced at iteration i-1
-        if self.deferred_dp and lrs != self._lrs:
-            self._lrs = lrs
-            self.optimizer.sync_lr()      # this iteration's rates, for the update the NEXT replay (or flush) applies
+        if self.deferred_dp:
+            self._sync_lr_if_changed()    # this iteration's rates, for the update the NEXT replay (or flush) applies
         for name, g in zip(self.phases, self.g_seg):
             self._run(self._phase_hooks.get(name, ()))       # this slice is final: its all-reduce goes out now ...
             g.replay()                                       # ... and runs under the next segment of backward
@@ -806,6 +839,18 @@ class CapturedTrainStep:
         elif not getattr(self.optimizer, "_last_emitted", False):
             self.inner.mark_dirty()      # eager forwards after a replay must rebuild the bf16 operands
         return self.out[0], self.out[1], self.grad_norm
+
+    def _sync_lr_if_changed(self):
+        """The param groups' learning rates to the device words the optimizer's launches read, when the schedule moved them since
+        the last call; an optimizer without device rates has its graph captured again."""
+        lrs = [g["lr"] for g in self.optimizer.param_groups]
+        if lrs == self._lrs:
+            return
+        if getattr(self.optimizer, "lr_dev", None) is not None:
+            self._lrs = lrs
+            self.optimizer.sync_lr()
+        else:
+            self.refresh_lr()
 
     def refresh_lr(self):
         self._lrs = [g["lr"] for g in self.optimizer.param_groups]
@@ -855,9 +900,9 @@ class _EagerResult:
 
 
 def _read_stats(cap, criterion, slot, retry):
-    """The host read-out of a replayed iteration, shared by every in-flight handle: waits for the stats copy and returns
-    (host vector, (loss_value, scaled dict, unscaled dict)).  A raised cooperative-decoder failure word re-runs the iteration
-    instead -- (None, what `retry` returned) -- and a non-finite loss stops the run (engine_vg.py:55-58)."""
+    """The host read-out of a replayed iteration: waits for the stats copy and returns (host vector, (loss_value, scaled dict,
+    unscaled dict)).  A raised cooperative-decoder failure word re-runs the iteration instead -- (None, what `retry` returned) --
+    and a non-finite loss stops the run (engine_vg.py:55-58)."""
     host_buf, event = slot
     event.synchronize()
     host = host_buf.tolist()
@@ -873,106 +918,126 @@ def _read_stats(cap, criterion, slot, retry):
             raise RuntimeError("rt_decoder_fwd: a stage hand-off timed out and the iteration cannot be re-run from here "
                                "(replayed without begin_train_step); the launches are now off (REFTR_DEC_COOP=0)")
         return None, retry()
-    weight_dict = criterion.weight_dict
-    unscaled = {f"{n}_unscaled": v for n, v in zip(cap.stat_names, host)}
-    scaled = {n: v * weight_dict[n] for n, v in zip(cap.stat_names, host) if n in weight_dict}
-    loss_value = sum(scaled.values())
-    if not math.isfinite(loss_value):
-        print("Loss is {}, stopping training".format(loss_value))
-        print(unscaled)
-        sys.exit(1)
-    return host, (loss_value, scaled, unscaled)
+    return host, _read_out(dict(zip(cap.stat_names, host)), criterion.weight_dict)
 
 
 class _ReplayInFlight:
-    """A replayed step between its launch and its host read-out (`finish`)."""
+    """A replayed step between its launch and its host read-out (`finish`).  `then` is what follows the read-out and yields the
+    gradient norm: nothing for the plain step, whose norm is the last word of the stats vector; for a micro-batch of an accumulation
+    window `_update` -- its losses are read first, so the non-finite stop and the cooperative decoder's re-run come BEFORE
+    its gradients go anywhere, as in the eager loop body."""
 
-    def __init__(self, cap, criterion, retry=None, slot=None):
-        self.cap, self.criterion, self.retry = cap, criterion, retry
+    def __init__(self, cap, criterion, retry=None, slot=None, then=None):
+        self.cap, self.criterion, self.retry, self.then = cap, criterion, retry, then
         self.slot = slot if slot is not None else (cap._stats_host[0], cap._stats_event[0])
 
     def finish(self):
         host, res = _read_stats(self.cap, self.criterion, self.slot, self.retry)
         if host is None:
             return res
-        return (*res, host[-1])
+        return (*res, host[-1] if self.then is None else self.then())
 
 
-class _AccumInFlight:
-    """A replayed micro-batch of an accumulation window between its launch and its read-out.  `finish` reads the micro-batch's
-    losses first -- the non-finite stop and the cooperative decoder's re-run come BEFORE its gradients go anywhere, as in the eager
-    loop body -- and then launches what follows the backward: accumulate(), or the window's average + clip + update."""
-
-    def __init__(self, cap, criterion, optimizer, lr_scheduler, max_norm, last, retry, slot):
-        self.cap, self.criterion, self.optimizer, self.lr_scheduler, self.max_norm = cap, criterion, optimizer, lr_scheduler, max_norm
-        self.last, self.retry, self.slot = last, retry, slot
-
-    def finish(self):
-        opt = self.optimizer
-        host, res = _read_stats(self.cap, self.criterion, self.slot, self.retry)
-        if host is None:
-            return res
-        if not self.last:
-            opt.accumulate()
-            return (*res, None)
-        opt.finish_accumulation()
-        if getattr(opt, "lr_dev", None) is not None:
-            opt.sync_lr()                    # another capture of this optimizer switched the kernel to device learning rates
-        gnorm = opt.clip_grad_norm_(self.max_norm)
-        opt.step()
-        if self.lr_scheduler is not None:
-            self.lr_scheduler.step()
-        return (*res, gnorm)
+def _new_capture(model, criterion, optimizer, max_norm, samples, targets, accumulate, canvas):
+    """A CapturedTrainStep for this batch, with what its warm-up iterations moved taken back, so that the loop sees exactly one
+    update per batch, like the eager loop.  The plain step's warm-up iterations are real updates on this batch: weights, both
+    moments, the step counters and the dropout seed go back.  An accumulating capture's are forward + backward only: no weight or
+    optimizer state moves, but the dropout seed does."""
+    inner = _inner(model)
+    st = inner.store
+    seed = (inner.seed_dev.clone(), inner._step)
+    snap = None if accumulate else (st.flat_p.clone(), optimizer.m.clone(), optimizer.v.clone(), optimizer.step_dev.clone(),
+                                    optimizer.step_count)
+    cap = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, accumulate=accumulate, canvas=canvas)
+    cap.training = model.training
+    if snap is not None:
+        cap.reset_pending()
+        st.flat_p.copy_(snap[0]); optimizer.m.copy_(snap[1]); optimizer.v.copy_(snap[2]); optimizer.step_dev.copy_(snap[3])
+        optimizer.step_count = snap[4]
+    inner.seed_dev.copy_(seed[0]); inner._step = seed[1]
+    if snap is not None:
+        inner.mark_dirty(full=True)      # the replay's first act finds the operands dirty and rebuilds them from the restored masters
+    return cap
 
 
-def _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead, accum_steps,
-                      window_end, canvas=None):
-    """begin_train_step for accum_steps > 1: forward + loss + backward replayed from one hipGraph per input shape
-    (CapturedTrainStep(accumulate=True)); accumulate / average + clip + update launched eagerly behind it (_AccumInFlight)."""
-    _require_accumulation(optimizer)
+def _find_capture(model, criterion, samples, targets, optimizer, max_norm, max_shapes, canvas, accumulate):
+    """How this batch runs, and on what: ("staged" | "replay" | "capture" | "eager", the CapturedTrainStep or None, the canvas if
+    the batch goes through it, the world-average box count if the data-parallel decision already carries it).  The captures live
+    in `model._captured_steps`, keyed by (shape key or canvas key, criterion, optimizer, max_norm or "accumulate", training)."""
+    state = _state(model)
+    dist_on = _multi_rank()
+    cap = state.staged_cap
+    if cap is not None and not dist_on and cap._staged is not None and cap._staged[0] is samples and cap._staged[1] is targets \
+            and cap.criterion is criterion and cap.optimizer is optimizer and cap.max_norm == max_norm and cap.training == model.training \
+            and cap.canvas is canvas and not accumulate:
+        return "staged", cap, canvas, None                     # steady state: staged by the previous iteration's lookahead
+    state.staged_cap = None
     inner = _inner(model)
     caps = inner.__dict__.setdefault("_captured_steps", {})
-    dist_on = utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1
     img = samples.get("img")
-    ok = (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and not dist_on and model is inner
-          and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1")
-    key = None
+    ok = isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1"
+    if accumulate:                                    # (the caller has checked _require_accumulation)
+        ok = ok and not dist_on and model is inner
+    else:
+        ok = ok and hasattr(optimizer, "clip_grad_norm_")
     if canvas is not None and not _canvas_fits(model, canvas, samples, targets):
         canvas = None                                 # the existing path, at the batch's own shape
+    key = None
     if ok:
         skey = canvas.key(samples) if canvas is not None else CapturedTrainStep.shape_key(samples, targets)
-        key = (skey, id(criterion), id(optimizer), "accumulate", model.training)
+        key = (skey, id(criterion), id(optimizer), "accumulate" if accumulate else float(max_norm), model.training)
         ok = key in caps or len(caps) < max_shapes
-    for k_, other in caps.items():                # a pending (deferred) update of a plain capture lands before anything else runs
-        if k_ != key:
+    nb_reduced = None
+    if dist_on and not accumulate:
+        # Data parallel: replaying, capturing and the eager loop issue DIFFERENT collective sequences (a capture adds the
+        # num_boxes all-reduce of its constructor and warm-up iterations with real gradient exchanges), and both the shape
+        # key (per-image box counts, image sizes) and the capture budget are rank-local.  The choice is therefore made
+        # collectively: replay only if EVERY rank holds a capture for its batch, capture only if every rank would capture,
+        # otherwise every rank runs the eager step.  One 3-word all-reduce per iteration, issued while the device is
+        # idle behind the previous iteration's read-out.
+        mine = ok
+        decision, nb_reduced = dp_capture_decision(ok and key in caps, ok and key not in caps, inner.store.device,
+                                                   num_boxes=sum(len(t["labels"]) for t in targets))
+        ok = decision != "eager"
+        if decision != "replay":
+            nb_reduced = None                   # the capture / eager paths reduce the box count themselves
+        if mine and not ok:
+            # this rank could have replayed / captured, another one could not (its capture budget is spent, or its batch has a
+            # shape this rank already holds while the other must still capture): the whole job runs this iteration eagerly.
+            # Said once per shape -- a run that quietly degrades to eager launches is 2-3x slower.
+            _say_once(model, ("dp", key), f"[reftr_amd] rank {utils.get_rank()}: data-parallel step runs eagerly (ranks disagree on "
+                      f"replay/capture for this input shape; {len(caps)} of {max_shapes} captures in use)")
+    cap = caps.get(key) if ok else None
+    # one pending (deferred) update at a time, and it lands before anything else runs -- an eager forward, a capture's warm-up,
+    # another capture's replay: every capture but the one about to replay is flushed
+    for other in caps.values():
+        if other is not cap:
             other.flush()
-    inner.__dict__["_staged_cap"] = None
     if not ok:
-        return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end,
-                                       canvas=canvas))
-    cap = caps.get(key)
-    if cap is None:
-        # the capture's warm-up iterations are forward + backward only: no weight or optimizer state moves, but the dropout seed does
-        snap = (inner.seed_dev.clone(), inner._step)
-        cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, accumulate=True, canvas=canvas)
-        cap.training = model.training
-        inner.seed_dev.copy_(snap[0]); inner._step = snap[1]
-    last = _window_last(optimizer, accum_steps, window_end)
-    seed_back = (1 if model.training else 0, 1)
-    cap(samples, targets)
-    slot = cap.queue_stats()
-    if lookahead is not None:
-        nxt = lookahead()
-        if nxt is not None and nxt[0] is not None:
-            cap.stage(*nxt)
+        return "eager", None, canvas, None
+    if cap is not None:
+        return "replay", cap, canvas, nb_reduced
+    cap = caps[key] = _new_capture(model, criterion, optimizer, max_norm, samples, targets, accumulate, canvas)
+    return "capture", cap, canvas, None
 
-    def _retry():
-        # nothing of the failed micro-batch has reached the accumulator, the weights or the scheduler: the same call, eagerly wired
-        _coop_fallback(model)
-        _restore_seed(model, seed_back)
-        return _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, None,
-                                 accum_steps, last, canvas).finish()
-    return _AccumInFlight(cap, criterion, optimizer, lr_scheduler, max_norm, last, _retry, slot)
+
+@contextlib.contextmanager
+def _update_rewound(optimizer, lrs):
+    """Around the re-run of a replayed plain step whose update was vetoed: what the failed iteration advanced goes back -- the host
+    step count and, while the re-run lasts, the learning rates it ran with (its scheduler step has already happened)."""
+    optimizer.step_count -= 1
+    # The veto is a per-rank device word, the decision to run the iteration again is collective: a healthy rank's finish_step
+    # has advanced its device counter, the failing rank's was vetoed.  Every rank re-bases the device counter on the host count
+    # (the same on all ranks), otherwise the AdamW bias corrections of the replicas differ from here on.
+    optimizer.step_dev.fill_(optimizer.step_count)
+    after = [g["lr"] for g in optimizer.param_groups]
+    for g, lr in zip(optimizer.param_groups, lrs):
+        g["lr"] = lr
+    try:
+        yield
+    finally:
+        for g, lr in zip(optimizer.param_groups, after):
+            g["lr"] = lr
 
 
 def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None,
@@ -990,85 +1055,24 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
     scheduler step and the stats copy are issued right behind the launch.
 
     accum_steps > 1 (see train_step): one micro-batch of an accumulation window.  The replayed graph is forward + loss + backward
-    alone; `finish` reads the losses and then launches accumulate() -- or, for the window's last micro-batch, the average, the clip,
-    the update and the scheduler step -- eagerly, so the update of a window is applied at its end and never between two of its
-    micro-batches.
+    alone (CapturedTrainStep(accumulate=True)); `finish` reads the losses and then launches accumulate() -- or, for the window's
+    last micro-batch, the average, the clip, the update and the scheduler step -- eagerly, so the update of a window is applied at
+    its end and never between two of its micro-batches.
 
     canvas (reftr_amd.data.canvas.BatchCanvas; single process): every batch that fits the canvas is staged into ONE capture's
     canvas-sized buffers by one rt_batch_stage launch and replayed -- the capture key is the canvas, the batch size and the token field
     shapes, not the batch's own shape.  A batch that does not fit runs exactly as without a canvas (own shape, `max_shapes`)."""
     if canvas is not None:
         _canvas_single_process(model)                 # refused before anything is launched
-    if int(accum_steps) > 1:
-        return _begin_accum_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, max_shapes, lookahead,
-                                 int(accum_steps), window_end, canvas)
-    inner = getattr(model, "module", model)
-    caps = inner.__dict__.setdefault("_captured_steps", {})
-    dist_on = utils.is_dist_avail_and_initialized() and utils.get_world_size() > 1
-    nb_reduced = None
-    cap = inner.__dict__.get("_staged_cap")
-    if cap is not None and not dist_on and cap._staged is not None and cap._staged[0] is samples and cap._staged[1] is targets \
-            and cap.criterion is criterion and cap.optimizer is optimizer and cap.max_norm == max_norm and cap.training == model.training \
-            and cap.canvas is canvas:
-        pass                                                   # steady state: staged by the previous iteration's lookahead
-    else:
-        cap = None
-        img = samples.get("img")
-        ok = (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and hasattr(optimizer, "clip_grad_norm_")
-              and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1")
-        key = None
-        on_canvas = canvas if canvas is not None and _canvas_fits(model, canvas, samples, targets) else None
-        if ok:
-            skey = on_canvas.key(samples) if on_canvas is not None else CapturedTrainStep.shape_key(samples, targets)
-            key = (skey, id(criterion), id(optimizer), float(max_norm), model.training)
-            ok = key in caps or len(caps) < max_shapes
-        if dist_on:
-            # Data parallel: replaying, capturing and the eager loop issue DIFFERENT collective sequences (a capture adds the
-            # num_boxes all-reduce of its constructor and warm-up iterations with real gradient exchanges), and both the shape
-            # key (per-image box counts, image sizes) and the capture budget are rank-local.  The choice is therefore made
-            # collectively: replay only if EVERY rank holds a capture for its batch, capture only if every rank would capture,
-            # otherwise every rank runs the eager step.  One 2-word MIN all-reduce per iteration, issued while the device is
-            # idle behind the previous iteration's read-out.
-            mine = ok
-            decision, nb_reduced = dp_capture_decision(ok and key in caps, ok and key not in caps, inner.store.device,
-                                                       num_boxes=sum(len(t["labels"]) for t in targets))
-            ok = decision != "eager"
-            if decision != "replay":
-                nb_reduced = None                   # the capture / eager paths reduce the box count themselves
-            if mine and not ok:
-                # this rank could have replayed / captured, another one could not (its capture budget is spent, or its batch has a
-                # shape this rank already holds while the other must still capture): the whole job runs this iteration eagerly.
-                # Said once per shape -- a run that quietly degrades to eager launches is 2-3x slower.
-                seen = inner.__dict__.setdefault("_dp_eager_logged", set())
-                if key not in seen:
-                    seen.add(key)
-                    print(f"[reftr_amd] rank {utils.get_rank()}: data-parallel step runs eagerly (ranks disagree on replay/capture for "
-                          f"this input shape; {len(caps)} of {max_shapes} captures in use)", file=sys.stderr)
-        if not ok:
-            for other in caps.values():             # a pending (deferred) update must land before the eager forward
-                other.flush()
-            return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, canvas=on_canvas))
-        cap = caps.get(key)
-        if cap is None:
-            for other in caps.values():             # one pending (deferred) update at a time
-                other.flush()
-            # the capture's warm-up iterations are real updates on this batch: take them back, so that the loop sees exactly one
-            # update per batch, like the eager loop
-            st = inner.store
-            snap = (st.flat_p.clone(), optimizer.m.clone(), optimizer.v.clone(), optimizer.step_dev.clone(), optimizer.step_count,
-                    inner.seed_dev.clone(), inner._step)
-            cap = caps[key] = CapturedTrainStep(model, criterion, optimizer, max_norm, samples, targets, canvas=on_canvas)
-            cap.training = model.training
-            cap.reset_pending()
-            st.flat_p.copy_(snap[0]); optimizer.m.copy_(snap[1]); optimizer.v.copy_(snap[2]); optimizer.step_dev.copy_(snap[3])
-            optimizer.step_count = snap[4]
-            inner.seed_dev.copy_(snap[5]); inner._step = snap[6]
-            inner.mark_dirty(full=True)      # the replay's first act finds the operands dirty and rebuilds them from the restored masters
-            del snap
-        else:
-            for other in caps.values():
-                if other is not cap:
-                    other.flush()
+    accum_steps = int(accum_steps)
+    accumulate = accum_steps > 1
+    if accumulate:
+        _require_accumulation(optimizer)
+    how, cap, on_canvas, nb_reduced = _find_capture(model, criterion, samples, targets, optimizer, max_norm, max_shapes, canvas, accumulate)
+    if how == "eager":
+        return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end,
+                                       canvas=on_canvas))
+    last = _window_last(optimizer, accum_steps, window_end) if accumulate else None
     lrs_now = [g["lr"] for g in optimizer.param_groups]
     seed_back = (1 if model.training else 0, 1)
     cap(samples, targets, nb_reduced)
@@ -1078,39 +1082,34 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
     # scheduler, on fetching and staging the NEXT batch (H2D hand-over, copies into the graph's input buffers -- stream-ordered
     # BEHIND the stats copy) and only then waits for the copy's event.
     stats = cap.stats
-    if dist_on:
+    if _multi_rank():
         k = len(cap.stat_names)
         kf = k + (1 if cap.fail_word is not None else 0)      # the failure word rides along: SUM over ranks, non-zero = some rank failed
         stats = stats.clone()
         torch.distributed.all_reduce(stats[:kf])
         stats[:k] /= utils.get_world_size()
     slot = cap.queue_stats(stats)
-    if lr_scheduler is not None:
+    if lr_scheduler is not None and not accumulate:
         lr_scheduler.step()          # host state only; the device reads the new rates when the next launch syncs them
-    inner.__dict__["_staged_cap"] = None
+    state = _state(model)
+    state.staged_cap = None
     if lookahead is not None:
         nxt = lookahead()
-        if nxt is not None and nxt[0] is not None and cap.stage(*nxt):
-            inner.__dict__["_staged_cap"] = cap
+        if nxt is not None and nxt[0] is not None and cap.stage(*nxt) and not accumulate:
+            state.staged_cap = cap           # (the identity fast path is the plain step's: a micro-batch always flushes the others)
+
     def _retry():
-        # what the failed iteration advanced: host step count (the device counter was vetoed), dropout seed / step, learning rates
+        # Nothing of the failed iteration has reached the weights (the device-side veto) or, for a micro-batch, the accumulator and
+        # the scheduler: the same call again, without lookahead, on the launched chain and the dropout seeds it had.  The plain
+        # step has already counted the update and stepped the scheduler: both are rewound around the re-run.
         _coop_fallback(model)
-        optimizer.step_count -= 1
-        # The veto is a per-rank device word, the decision to run the iteration again is collective: a healthy rank's finish_step
-        # has advanced its device counter, the failing rank's was vetoed.  Every rank re-bases the device counter on the host count
-        # (the same on all ranks), otherwise the AdamW bias corrections of the replicas differ from here on.
-        optimizer.step_dev.fill_(optimizer.step_count)
-        _restore_seed(model, seed_back)
-        after = [g["lr"] for g in optimizer.param_groups]
-        for g, lr in zip(optimizer.param_groups, lrs_now):
-            g["lr"] = lr
-        try:
-            return begin_train_step(model, criterion, samples, targets, optimizer, None, max_norm, max_shapes, None,
-                                    canvas=canvas).finish()
-        finally:
-            for g, lr in zip(optimizer.param_groups, after):
-                g["lr"] = lr
-    return _ReplayInFlight(cap, criterion, retry=_retry, slot=slot)
+        with contextlib.nullcontext() if accumulate else _update_rewound(optimizer, lrs_now):
+            _restore_seed(model, seed_back)
+            return begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler if accumulate else None, max_norm,
+                                    max_shapes, None, accum_steps, last, canvas).finish()
+    # a micro-batch's graph ends with the backward: what follows it is launched eagerly behind the read-out
+    then = (lambda: _update(model, optimizer, lr_scheduler, max_norm, last, sync_lr=True)) if accumulate else None
+    return _ReplayInFlight(cap, criterion, retry=_retry, slot=slot, then=then)
 
 
 def captured_train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None, max_norm=0.0, max_shapes=4, lookahead=None,
@@ -1123,8 +1122,7 @@ def captured_train_step(model, criterion, samples, targets, optimizer, lr_schedu
 def _check_cooperative(model):
     """rt_decoder_fwd reports a consumer that gave up waiting (a workgroup that never became resident) through a device word;
     a loop that produced numbers from such a launch must not return them."""
-    inner = getattr(model, "module", model)
-    dc = getattr(getattr(inner, "net", None), "dec_counters", None)
+    dc = getattr(getattr(_inner(model), "net", None), "dec_counters", None)
     if dc is not None and int(dc[-1]) != 0:
         raise RuntimeError("rt_decoder_fwd: a stage hand-off timed out (workgroups not co-resident?) -- set REFTR_DEC_COOP=0")
 
@@ -1172,11 +1170,9 @@ def train_one_epoch(model, criterion, data_loader, optimizer, lr_scheduler, devi
         # canvas, for every batch that fits it;
         # the replayed path hands back host numbers (one stacked copy per iteration), the eager one device scalars.
         ahead = Lookahead(prefetcher.next)
-        if accum_steps > 1:
-            step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead,
-                                    accum_steps=accum_steps, window_end=(it + 1) % accum_steps == 0 or it + 1 == n_batches, canvas=canvas)
-        else:
-            step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead, canvas=canvas)
+        # (window_end is only read when accum_steps > 1)
+        step = begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, lookahead=ahead,
+                                accum_steps=accum_steps, window_end=(it + 1) % accum_steps == 0 or it + 1 == n_batches, canvas=canvas)
         step.lr_logged = optimizer.param_groups[0]["lr"]      # what the reference's meter shows: the rate after this iteration's scheduler step
         if booked is not None:
             board.add(**booked)
@@ -1199,18 +1195,15 @@ class CapturedForward:
 
     def __init__(self, model, max_shapes=4):
         self.model, self.graphs, self.max_shapes = model, {}, max_shapes
-        self._gen = _inner(model).__dict__.get("_coop_generation", 0)
+        self._gen = _state(model).coop_generation
 
-    @staticmethod
-    def shape_key(samples):
-        return tuple((n, tuple(v.tensors.shape) if isinstance(v, utils.NestedTensor) else tuple(v.shape))
-                     for n, v in sorted(samples.items()) if isinstance(v, utils.NestedTensor) or torch.is_tensor(v))
+    shape_key = staticmethod(_sample_shapes)
 
     @torch.no_grad()
     def __call__(self, samples):
         if not isinstance(samples.get("img"), utils.NestedTensor):
             return self.model(samples)
-        gen = _inner(self.model).__dict__.get("_coop_generation", 0)
+        gen = _state(self.model).coop_generation
         if gen != self._gen:                     # the cooperative launches were switched off: the graphs that contain them go
             self.graphs, self._gen = {}, gen
         key = self.shape_key(samples)
@@ -1219,18 +1212,13 @@ class CapturedForward:
             return self.model(samples)
         if ent is None:
             s, _ = _clone_batch(samples, [])
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self.model(s)                        # warm-up: operand refresh, workspaces, descriptor tables
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            _warm_up(lambda: self.model(s), 1)
             g = torch.cuda.CUDAGraph()
             with _capture(g):
                 out = self.model(s)
             ent = self.graphs[key] = (g, s, out)
         g, s, out = ent
-        inner = getattr(self.model, "module", self.model)
+        inner = _inner(self.model)
         if inner._flush_pending is not None:
             inner._flush_pending()
         if inner._operands_dirty:                    # weights changed since the capture: rebuild the bf16 operands eagerly
@@ -1363,7 +1351,7 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
             wvec = (names, torch.tensor([weight_dict[k] for k in wn], dtype=torch.float32, device=red[names[0]].device))
         un = torch.stack([red[k].reshape(()).float() for k in names])
         sc = torch.stack([red[k].reshape(()).float() for k in wn]) * wvec[1]
-        board.add_device([f"{k}_unscaled" for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]))
+        board.add_device([_UNSCALED(k) for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]))
         key = "orig_size" if "orig_size" in targets[0] else "size"
         orig_sizes = torch.stack([t[key] for t in targets], dim=0)
         if meter is not None:

@@ -558,6 +558,237 @@ def test_replayed_iteration_with_a_raised_failure_word_is_run_again_not_returned
     assert E._ReplayInFlight(cap_nofail, crit, slot=(torch.tensor([0.5, 0.25, 3.0]), Ev())).finish()[3] == 3.0   # [losses | norm]
 
 
+def test_read_out_gives_device_scalars_and_host_floats_the_same_numbers_and_the_same_stop(capsys):
+    """_read_out(): the eager path hands it reduced device scalars, the replayed path host floats; both get the same loss_value (a
+    Python float), the same keys, the weighted values only for the names weight_dict has, and exit status 1 on a non-finite total."""
+    from reftr_amd import engine_vg as E
+    wd = {"loss_bbox": 5.0, "loss_giou": 2.0}                          # no weight for class_error: logged unweighted only
+    vals = {"loss_bbox": 0.5, "loss_giou": 0.25, "class_error": 7.0}   # (every product and the sum are exact in fp32)
+    lf, sf, uf = E._read_out(vals, wd)
+    lt, st, ut = E._read_out({k: torch.tensor(v) for k, v in vals.items()}, wd)
+    assert type(lf) is float and type(lt) is float and lf == lt == 3.0
+    assert sf == {"loss_bbox": 2.5, "loss_giou": 0.5}
+    assert uf == {"loss_bbox_unscaled": 0.5, "loss_giou_unscaled": 0.25, "class_error_unscaled": 7.0}
+    assert all(type(v) is float for v in (*sf.values(), *uf.values()))
+    assert all(torch.is_tensor(v) for v in (*st.values(), *ut.values()))
+    assert {k: float(v) for k, v in st.items()} == sf and {k: float(v) for k, v in ut.items()} == uf
+    for bad in (float("nan"), torch.tensor(float("nan")), float("inf")):
+        with pytest.raises(SystemExit) as stop:
+            E._read_out(dict(vals, loss_giou=bad), wd)
+        assert stop.value.code == 1
+        assert ", stopping training" in capsys.readouterr().out
+    assert E._read_out(dict(vals, class_error=float("nan")), wd)[0] == 3.0     # an unweighted term is not part of the total
+
+
+def test_replayed_micro_batch_reads_its_losses_before_its_gradients_go_anywhere():
+    """The one in-flight handle with a "what follows the read-out" step (an accumulation window's micro-batch, whose graph ends
+    with the backward): inside the window accumulate() and no norm; the window's last one average -> clip -> update -> scheduler,
+    the norm being the clip's; a raised failure word hands back the retry's result and launches none of it."""
+    import types
+    from reftr_amd import engine_vg as E
+
+    class Ev:
+        def synchronize(self):
+            pass
+    calls = []
+
+    def rec(name, ret=None):
+        return lambda *a: (calls.append((name, *a)), ret)[1]
+    opt = types.SimpleNamespace(accumulate=rec("accumulate"), finish_accumulation=rec("finish"), clip_grad_norm_=rec("clip", "the norm"),
+                                step=rec("step"), sync_lr=rec("sync_lr"), lr_dev=None)
+    sched = types.SimpleNamespace(step=rec("scheduler"))
+    crit = types.SimpleNamespace(weight_dict={"loss_bbox": 5.0, "loss_giou": 2.0})
+    cap = types.SimpleNamespace(stat_names=("loss_bbox", "loss_giou"), fail_word=object(), model=None)      # [losses | failure word]
+
+    def handle(last, word=0.0):
+        return E._ReplayInFlight(cap, crit, retry=lambda: "again", slot=(torch.tensor([0.5, 0.25, word]), Ev()),
+                                 then=lambda: E._update(None, opt, sched, 0.1, last, sync_lr=True))
+    loss, scaled, unscaled, gn = handle(last=False).finish()
+    assert gn is None and calls == [("accumulate",)]
+    assert loss == 3.0 and scaled == {"loss_bbox": 2.5, "loss_giou": 0.5} and unscaled["loss_giou_unscaled"] == 0.25
+    calls.clear()
+    assert handle(last=True).finish() == (3.0, scaled, unscaled, "the norm")
+    assert calls == [("finish",), ("clip", 0.1), ("step",), ("scheduler",)]
+    calls.clear()
+    opt.lr_dev = object()                      # a plain capture of the same optimizer moved the rates to device words
+    handle(last=True).finish()
+    assert calls == [("finish",), ("sync_lr",), ("clip", 0.1), ("step",), ("scheduler",)]
+    calls.clear()
+    assert handle(last=True, word=1.0).finish() == "again" and handle(last=False, word=2.0).finish() == "again" and calls == []
+
+
+def _lookup_world(monkeypatch, on_device=True):
+    """Fakes for _find_capture: a model with a capture table, a batch whose image says where it lives, a CapturedTrainStep stand-in
+    whose construction moves what a warm-up moves (so the lookup has something to take back)."""
+    import types
+    from reftr_amd import engine_vg as E
+    from reftr_amd.util.misc import NestedTensor
+
+    class Cap:
+        shape_key = staticmethod(E.CapturedTrainStep.shape_key)
+
+        def __init__(self, model=None, criterion=None, optimizer=None, max_norm=None, samples=None, targets=None, accumulate=False,
+                     canvas=None):
+            self.flushed = self.resets = 0
+            self.accumulate, self.canvas = accumulate, canvas
+            if model is not None:                              # "warm-up": two updates on this batch
+                model.seed_dev += 2; model._step += 2
+                if not accumulate:
+                    model.store.flat_p += 1; optimizer.m += 1; optimizer.v += 1; optimizer.step_dev += 2; optimizer.step_count += 2
+
+        def flush(self):
+            self.flushed += 1
+
+        def reset_pending(self):
+            self.resets += 1
+    monkeypatch.setattr(E, "CapturedTrainStep", Cap)
+    monkeypatch.delenv("REFTR_TRAIN_GRAPH", raising=False)
+    model = types.SimpleNamespace(training=True, _captured_steps={}, seed_dev=torch.tensor([5]), _step=5, dirty=[],
+                                  store=types.SimpleNamespace(flat_p=torch.zeros(4), device="cpu"))
+    model.mark_dirty = lambda full=False: model.dirty.append(full)
+    opt = types.SimpleNamespace(clip_grad_norm_=None, m=torch.zeros(4), v=torch.zeros(4), step_dev=torch.tensor([7]), step_count=7)
+    img = NestedTensor(types.SimpleNamespace(is_cuda=on_device, shape=(2, 3, 8, 8)), None)
+    samples, targets = {"img": img, "sentence": torch.zeros(2, 6)}, [{"boxes": torch.zeros(1, 4)}, {"boxes": torch.zeros(3, 4)}]
+    return E, Cap, model, opt, samples, targets
+
+
+def test_capture_lookup_answers_replay_capture_or_eager_and_flushes_every_other_capture(monkeypatch):
+    """_find_capture(): a hit replays and flushes every capture but the hit; a miss within the budget flushes them all, builds the
+    capture and takes back what its warm-up moved; a miss over the budget and a host-resident batch run eagerly, the former after
+    flushing them all; a batch the previous iteration staged is answered by identity."""
+    E, Cap, model, opt, samples, targets = _lookup_world(monkeypatch)
+    crit = object()
+    plain = lambda **kw: E._find_capture(model, crit, samples, targets, opt, 0.1, kw.get("max_shapes", 4), None, kw.get("accumulate", False))
+    key = (E.CapturedTrainStep.shape_key(samples, targets), id(crit), id(opt), 0.1, True)
+    hit, a, b = Cap(), Cap(), Cap()
+    model._captured_steps.update({key: hit, "a": a, "b": b})
+    assert plain() == ("replay", hit, None, None)
+    assert (hit.flushed, a.flushed, b.flushed) == (0, 1, 1)
+    model._captured_steps.pop(key)                                     # a miss, within the budget of 4
+    how, cap, _, _ = plain()
+    assert how == "capture" and model._captured_steps[key] is cap and (a.flushed, b.flushed) == (2, 2) and cap.flushed == 0
+    # the plain step's warm-up iterations were real updates: weights, moments, both step counters, the seed word and _step go back
+    assert cap.training is True and cap.resets == 1 and model.dirty == [True]
+    assert float(model.store.flat_p.sum()) == 0 and float(opt.m.sum()) == 0 and float(opt.v.sum()) == 0
+    assert int(opt.step_dev) == 7 and opt.step_count == 7 and int(model.seed_dev) == 5 and model._step == 5
+    model._captured_steps.pop(key)                                     # a miss, over a budget of 2
+    assert plain(max_shapes=2) == ("eager", None, None, None)
+    assert (a.flushed, b.flushed) == (3, 3) and set(model._captured_steps) == {"a", "b"}
+    # the accumulating step has a key of its own, and so has the other training mode
+    how, acc, _, _ = plain(accumulate=True)
+    akey, = set(model._captured_steps) - {"a", "b"}
+    assert how == "capture" and acc.accumulate and akey == (key[0], id(crit), id(opt), "accumulate", True) and akey != key
+    assert acc.resets == 0 and model.dirty == [True] and int(model.seed_dev) == 5 and model._step == 5      # seed word and _step only
+    assert (a.flushed, b.flushed) == (4, 4)
+    model.training = False
+    how, ev, _, _ = plain()
+    assert how == "capture" and (key[:4] + (False,)) in model._captured_steps and ev is not acc
+    assert plain(accumulate=True)[0] == "eager" and len(model._captured_steps) == 4       # a fifth key: over the budget
+    # steady state: the capture that holds the staged batch is recognised by identity, nothing is flushed
+    ev.criterion, ev.optimizer, ev.max_norm, ev._staged = crit, opt, 0.1, (samples, targets)
+    E._state(model).staged_cap = ev
+    before = [c.flushed for c in model._captured_steps.values()]
+    assert plain() == ("staged", ev, None, None) and [c.flushed for c in model._captured_steps.values()] == before
+    assert plain(accumulate=True)[0] != "staged"                       # (a micro-batch always takes the lookup)
+
+
+def test_capture_lookup_runs_a_host_batch_eagerly(monkeypatch):
+    E, Cap, model, opt, samples, targets = _lookup_world(monkeypatch, on_device=False)
+    other = model._captured_steps["x"] = Cap()
+    for accumulate in (False, True):
+        assert E._find_capture(model, object(), samples, targets, opt, 0.1, 4, None, accumulate) == ("eager", None, None, None)
+    assert other.flushed == 2 and set(model._captured_steps) == {"x"}          # a pending update still lands before the eager forward
+    samples["img"].tensors.is_cuda = True
+    monkeypatch.setenv("REFTR_TRAIN_GRAPH", "0")                               # switched off: eager as well
+    assert E._find_capture(model, object(), samples, targets, opt, 0.1, 4, None, False)[0] == "eager"
+    monkeypatch.delenv("REFTR_TRAIN_GRAPH")
+    del opt.clip_grad_norm_                                                    # a foreign optimizer: the plain step cannot capture
+    assert E._find_capture(model, object(), samples, targets, opt, 0.1, 4, None, False)[0] == "eager"
+
+
+def test_capture_lookup_keys_a_fitting_batch_by_the_canvas_and_says_once_when_one_does_not_fit(monkeypatch, capsys):
+    import types
+    E, Cap, model, opt, samples, targets = _lookup_world(monkeypatch)
+    crit = object()
+    fits = types.SimpleNamespace(why_not=lambda s, t: None, key=lambda s: ("canvas", 64, 64, 2))
+    how, cap, used, _ = E._find_capture(model, crit, samples, targets, opt, 0.1, 4, fits, False)
+    (key, held), = model._captured_steps.items()
+    assert how == "capture" and used is fits and cap.canvas is fits and held is cap and key[0] == ("canvas", 64, 64, 2)
+    assert E._find_capture(model, crit, samples, targets, opt, 0.1, 4, fits, False)[:3] == ("replay", cap, fits)
+    tight = types.SimpleNamespace(why_not=lambda s, t: "image 8 x 8 exceeds the canvas", key=lambda s: ("canvas", 4, 4, 2))
+    capsys.readouterr()
+    for how_expected in ("capture", "replay"):
+        how, own, used, _ = E._find_capture(model, crit, samples, targets, opt, 0.1, 4, tight, False)
+        assert how == how_expected and used is None and own.canvas is None
+    assert E.CapturedTrainStep.shape_key(samples, targets) in {k[0] for k in model._captured_steps}
+    err = capsys.readouterr().err
+    assert err.count("does not fit") == 1 and "image 8 x 8 exceeds the canvas" in err
+
+
+def _coop_model():
+    """A two-parameter model whose first backward raises the cooperative decoder's failure word."""
+    import types
+
+    class TwoParams(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.a, self.b = torch.nn.Parameter(torch.tensor(1.5)), torch.nn.Parameter(torch.tensor(-0.5))
+            self.word, self.forwards = torch.zeros(1, dtype=torch.int32), 0
+            self.net = types.SimpleNamespace(dec_counters=torch.zeros(2), dec_coop=True, dec_coop_bwd=True, _dec_handoff=None)
+
+        def coop_failure_word(self):
+            return self.word
+
+        def forward(self, samples):
+            self.forwards += 1
+            return self.a * samples["x"] + self.b
+    return TwoParams()
+
+
+@pytest.mark.parametrize("second", ["finite", "nan"])
+def test_train_step_runs_the_eager_body_again_after_a_fallback_and_stops_on_its_non_finite_loss(monkeypatch, second):
+    """train_step on the CPU: a failure word raised in the first backward discards the iteration; the one eager body runs a second
+    time, the optimizer steps once, on the second run's gradients, and the second run's numbers come back.  The second run has the
+    non-finite stop of the first (it had none before the two copies of the body became one): exit status 1, no update."""
+    from reftr_amd import engine_vg as E
+    monkeypatch.setenv("REFTR_DEC_COOP", "1"); monkeypatch.setenv("REFTR_DEC_COOP_BWD", "1")      # (_coop_fallback rewrites them)
+    monkeypatch.setattr(E, "_COOP_LOGGED", True)
+    model = _coop_model()
+    x = torch.tensor([1.0, 2.0, 3.0])
+    runs, steps = [], []
+
+    def criterion(outputs, targets):
+        n = len(runs) + 1                                  # the n-th run's loss is n x the mean square: the two runs differ
+        loss = outputs.pow(2).mean() * (float("nan") if (n == 2 and second == "nan") else n)
+        if n == 1:
+            loss.register_hook(lambda g: (model.word.fill_(1), None)[1])
+        runs.append(loss)
+        return {"loss_sq": loss, "other": outputs.detach().sum()}
+    criterion.weight_dict = {"loss_sq": 2.0}
+    body, bodies = E._eager_iteration, []
+    monkeypatch.setattr(E, "_eager_iteration", lambda *a: (bodies.append(1), body(*a))[1])
+    opt = torch.optim.SGD(model.parameters(), lr=0.5)
+    step = opt.step
+    monkeypatch.setattr(opt, "step", lambda: (steps.append(1), step())[1])
+    if second == "nan":
+        with pytest.raises(SystemExit) as stop:
+            E.train_step(model, criterion, {"x": x}, [], opt)
+        assert stop.value.code == 1 and len(bodies) == 2 and steps == [] and float(model.a.detach()) == 1.5
+        return
+    loss_value, scaled, unscaled, gnorm = E.train_step(model, criterion, {"x": x}, [], opt)
+    assert len(bodies) == 2 and model.forwards == 2 and len(runs) == 2 and steps == [1]
+    assert model.net.dec_coop is False and model.net.dec_counters is None and E._state(model).coop_generation == 1
+    out = 1.5 * x - 0.5
+    second_loss = 2 * float(out.pow(2).mean())
+    assert abs(loss_value - 2.0 * second_loss) < 1e-5 and abs(float(scaled["loss_sq"].detach()) - 2.0 * second_loss) < 1e-5
+    assert abs(float(unscaled["loss_sq_unscaled"].detach()) - second_loss) < 1e-5 and float(unscaled["other_unscaled"]) == float(out.sum())
+    # one SGD step on the SECOND run's gradient alone (zero_grad ran in between): the total is weight 2 x (2 x mean((a x + b)^2)),
+    # d/da = 8 * mean(out * x), d/db = 8 * mean(out)
+    assert abs(float(model.a.detach()) - (1.5 - 0.5 * 8 * float((out * x).mean()))) < 1e-5
+    assert abs(float(model.b.detach()) - (-0.5 - 0.5 * 8 * float(out.mean()))) < 1e-5
+    assert float(gnorm) == 0.0                             # max_norm 0 with a torch optimizer: no clip, the reference's zero
+
+
 def test_data_parallel_boundary_clears_never_written_matrices_before_the_exchange(monkeypatch):
     """ParamStore.finish_overwrite_range: a registered matrix that this step never writes must be cleared
     BEFORE its slice is exchanged at a data-parallel boundary, and the end-of-backward clear must leave it (and the in-flight
