@@ -794,6 +794,59 @@ typedef struct rt_eval_metrics_args {
 int rt_eval_metrics(const rt_eval_metrics_args* a, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Evaluation on the batch canvas: the post-processing and metric tail of one canvas batch with every per-batch fact in DEVICE memory,
+ * so that it can sit inside a captured graph and be replayed without an argument change.
+ * rt_eval_facts — one small launch per batch, outside the graph: gathers the B device int64 arrays the loader delivers --
+ *   size_ptrs[b] -> {img_h, img_w}, orig_ptrs[b] -> {orig_h, orig_w} (orig_ptrs NULL: the size), id_ptrs[b] -> the image id (id_ptrs
+ *   NULL: -1) -- and the HOST int32 pairs tm_hw[2b], tm_hw[2b+1] (target mask height, width; NULL: 0, 0) into
+ *   facts int32 [B, 6] = {img_h, img_w, orig_h, orig_w, mask_h, mask_w} and image_ids int64 [B].  The pointer arrays are HOST arrays
+ *   of B entries that travel by value in the kernel's argument block, as rt_batch_stage's do (B <= RT_BATCH_STAGE_MAX_B, else
+ *   RT_ERR_UNSUPPORTED; RT_ERR_BADARG for a NULL required pointer or entry, B <= 0).
+ * rt_eval_canvas — two launches, replacing rt_box_postprocess + rt_mask_postprocess + rt_eval_metrics + the table copy:
+ *   (a) mask partials (only when pred_masks is given), grid (chunk, image): for every pixel of the image's scored rectangle
+ *       ({img_h, img_w} of `facts`, clamped to the target mask's own extent and to the canvas) the decision of query 0 is taken from the
+ *       logits pred_masks fp32 [B, Q, h, w] by rt_mask_postprocess's own function with the canvas Hc x Wc as the frame, the target byte
+ *       is read from tgt_masks uint8 [B, 1, Hc, Wc] (what rt_batch_stage wrote) at pitch Wc, and the integer {I, U} of the workgroup's
+ *       RT_EVAL_CHUNK pixels go to partials[b][chunk] (int32, B * ceil(Hc * Wc / RT_EVAL_CHUNK) * 2 words).  No uint8 frame exists;
+ *   (b) finish, ONE wave, rt_eval_metrics' finish in its order (image ascending, row ascending; un-fused box arithmetic; int64 counts,
+ *       double sums) with the target boxes of image b = rows tgt_off[b] .. tgt_off[b+1] of tgt_boxes (rt_batch_stage's packed buffer of
+ *       tgt_rows rows) -> iou_det [B, P], iou_seg [B], iu [B, 2], acc (never reset here: the caller zeroes acc once).  It also writes
+ *       slot s = cursor[0] of a results ring: ring_boxes fp32 [slots, B, P, 4] = rt_box_postprocess's output scaled by {orig_w, orig_h}
+ *       (unused rows 0), ring_counts int32 [slots, B] = valid phrases per image, ring_ids int64 [slots, B] = image_ids; then
+ *       cursor[0] = s + 1.  s >= slots: nothing is written to the ring, cursor[1] = 1 (overflow) and cursor[0] stays.
+ *   `cursor` is int32 [2] in device memory, zeroed by the caller with acc.  No atomics; the same bits from run to run.
+ *   `veto` (optional): a device word read by the finish; non-zero -> this batch is NOT kept: acc, ring and cursor stay as they were
+ *   (iou_det / iou_seg / iu are still written).  The evaluation loop hands the cooperative decoder's failure word, so that a batch
+ *   whose forward is run again is counted once.
+ *   RT_ERR_BADARG: a NULL required pointer, a non-positive size; RT_ERR_UNSUPPORTED: B > RT_BATCH_STAGE_MAX_B, Hc * Wc >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+int rt_eval_facts(const int64_t* const* size_ptrs, const int64_t* const* orig_ptrs, const int64_t* const* id_ptrs,
+                  const int32_t* tm_hw, int B, int32_t* facts, int64_t* image_ids, rt_stream_t stream);
+typedef struct rt_eval_canvas_args {
+    const float*   pred_boxes;     /* fp32 [B, P, K, 4] cxcywh */
+    const uint8_t* valid;          /* uint8 [B, P, K] */
+    const float*   tgt_boxes;      /* fp32 [tgt_rows, 4] cxcywh, packed in image order */
+    const int32_t* tgt_off;        /* int32 [B + 1] */
+    const int32_t* facts;          /* int32 [B, 6] */
+    const int64_t* image_ids;      /* int64 [B] */
+    const float*   pred_masks;     /* fp32 [B, Q, h, w] | NULL: the box part only */
+    const uint8_t* tgt_masks;      /* uint8 [B, 1, Hc, Wc] */
+    int32_t* partials;
+    float*   iou_det;
+    float*   iou_seg;
+    int64_t* iu;
+    void*    acc;
+    float*   ring_boxes;
+    int32_t* ring_counts;
+    int64_t* ring_ids;
+    int32_t* cursor;
+    const int32_t* veto;           /* int32 [1] | NULL */
+    int32_t B, P, K, Q, h, w, Hc, Wc, tgt_rows, slots;
+    float   threshold;
+} rt_eval_canvas_args;
+int rt_eval_canvas(const rt_eval_canvas_args* a, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * rt_comm_* — the data-parallel gradient exchange: what the reference gets from
  * torch.nn.parallel.DistributedDataParallel (main_vg.py:290-296) after util/misc.py:392-431 set up one process per GPU.
  * RCCL over xGMI, bound at run time (dlopen: the copy the process already holds -- torch.distributed's -- or the system's);

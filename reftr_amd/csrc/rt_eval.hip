@@ -4,9 +4,11 @@
 //   eval_finish_kernel  ONE wave, image ascending then row ascending: box IoU of every valid phrase against its target box
 //                       (util/box_ops.py's arithmetic, un-fused, in its order -> the bits of diag(box_iou)), the mask partials added
 //                       up per image, and the 16 running accumulators (counts int64, the two IoU sums double) updated in that order
+// rt_eval_canvas / rt_eval_facts (below): the same finish with every per-batch fact in device memory, for a captured evaluation step
+// on a batch canvas; its mask launch lives in rt_post.hip (rt_eval_shared.h says why).
 // No floating-point atomics and nothing to clear beforehand: the same bits from run to run.  Latency-bound (0.4 MB per 640 x 640
 // image, a few hundred box rows): byte loads, one thread per pixel, and a serial walk over the rows for the ordered double sums.
-#include "rt_common.h"
+#include "rt_eval_shared.h"
 
 // The box arithmetic must keep torch's roundings: one per operation.  HIP's __fmul_rn / __fadd_rn / __fsub_rn are plain operators
 // defined in a header, under the compiler's default contraction: inlined here, a product feeding a sum still becomes one fused
@@ -16,11 +18,7 @@
 
 namespace {
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using rt_eval_shared::wave_sum_int;
 __device__ __forceinline__ long long wave_sum_i64(long long v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -53,12 +51,6 @@ __device__ __forceinline__ float box_iou_pair(const xyxy a, const xyxy b) {
     return __fdiv_rn(inter, uni);
 }
 
-// the image's scored rectangle: sizes[b], never past the target's own extent or the frame (equal to sizes[b] for consistent input)
-__device__ __forceinline__ void scored_rect(const rt_eval_metrics_args& a, int b, int th, int tw, int& ih, int& iw) {
-    ih = min(min(a.sizes[b * 2], th), a.max_h);
-    iw = min(min(a.sizes[b * 2 + 1], tw), a.max_w);
-}
-
 __global__ __launch_bounds__(256) void eval_mask_kernel(const rt_eval_metrics_args a, int nchunks) {
     __shared__ int sm[8];
     const int b = blockIdx.y, c = blockIdx.x;
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(256) void eval_mask_kernel(const rt_eval_metrics_ar
     if (tg) {
         const int tw = (int)row[4];
         int ih, iw;
-        scored_rect(a, b, (int)row[3], tw, ih, iw);
+        rt_eval_shared::scored_rect(a.sizes[b * 2], a.sizes[b * 2 + 1], (int)row[3], tw, a.max_h, a.max_w, ih, iw);
         if (ih > 0 && iw > 0) {
             const uint8_t* pm = a.masks + (size_t)b * a.Q * a.max_h * a.max_w;          // query 0
             const long long n = (long long)ih * iw, end = min(n, ((long long)c + 1) * RT_EVAL_CHUNK);
@@ -79,15 +71,7 @@ __global__ __launch_bounds__(256) void eval_mask_kernel(const rt_eval_metrics_ar
             }
         }
     }
-    I = wave_sum_int(I); U = wave_sum_int(U);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) { sm[wid * 2] = I; sm[wid * 2 + 1] = U; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t* o = a.partials + ((size_t)b * nchunks + c) * 2;
-        o[0] = (sm[0] + sm[2]) + (sm[4] + sm[6]);
-        o[1] = (sm[1] + sm[3]) + (sm[5] + sm[7]);
-    }
+    rt_eval_shared::store_block_iu(I, U, sm, a.partials + ((size_t)b * nchunks + c) * 2);
 }
 
 __device__ __forceinline__ void count_sample(float v, long long& n, long long* hit, double& sum) {
@@ -98,62 +82,141 @@ __device__ __forceinline__ void count_sample(float v, long long& n, long long* h
     sum += (double)v;
 }
 
-__global__ __launch_bounds__(64) void eval_finish_kernel(const rt_eval_metrics_args a, int nchunks) {
-    __shared__ float s_iou[64];
-    const int lane = threadIdx.x;
-    long long* acc_i = reinterpret_cast<long long*>(a.acc);
-    double* acc_d = reinterpret_cast<double*>(a.acc);
-    // lane 0 owns the running totals
+// the 16 running accumulators while a finish kernel runs: lane 0 owns them
+struct totals {
     long long det_n = 0, det_hit[5] = {0, 0, 0, 0, 0}, seg_n = 0, seg_hit[5] = {0, 0, 0, 0, 0}, seg_i = 0, seg_u = 0;
     double det_sum = 0.0, seg_sum = 0.0;
-    if (lane == 0 && !a.reset) {
+    __device__ __forceinline__ void load(const void* acc) {
+        const long long* acc_i = reinterpret_cast<const long long*>(acc);
+        const double* acc_d = reinterpret_cast<const double*>(acc);
         det_n = acc_i[RT_EVAL_DET_N]; seg_n = acc_i[RT_EVAL_SEG_N];
         for (int t = 0; t < 5; ++t) { det_hit[t] = acc_i[RT_EVAL_DET_HIT + t]; seg_hit[t] = acc_i[RT_EVAL_SEG_HIT + t]; }
         seg_i = acc_i[RT_EVAL_SEG_I]; seg_u = acc_i[RT_EVAL_SEG_U];
         det_sum = acc_d[RT_EVAL_DET_SUM]; seg_sum = acc_d[RT_EVAL_SEG_SUM];
     }
-    for (int b = 0; b < a.B; ++b) {
-        const int64_t* row = a.table + (size_t)b * 5;
-        const float* tb = reinterpret_cast<const float*>(row[0]);
-        const int nb = tb ? (int)min((long long)a.P, max(0ll, (long long)row[1])) : 0;
-        float* out = a.iou_det + (size_t)b * a.P;
-        int base = 0, rank;
-        for (int j0 = 0; j0 < a.P && base < nb; j0 += 64) {
-            const int ph = j0 + lane, before = base;
-            const bool mine = rt_phrase_rank(a.valid + (size_t)b * a.P * a.K, a.P, a.K, ph, lane, base, rank);
-            if (mine && rank < nb) {
-                const float v = box_iou_pair(to_xyxy(tb + (size_t)rank * 4), to_xyxy(a.pred_boxes + ((size_t)(b * a.P + ph) * a.K) * 4));
-                out[rank] = v;
-                s_iou[rank - before] = v;
-            }
-            __syncthreads();
-            if (lane == 0) {
-                const int m = min(base, nb) - before;
-                for (int i = 0; i < m; ++i) count_sample(s_iou[i], det_n, det_hit, det_sum);
-            }
-            __syncthreads();
-        }
-        for (int r = min(base, nb) + lane; r < a.P; r += 64) out[r] = 0.f;
-        if (!a.masks) continue;
-        long long I = 0, U = 0;
-        const bool scored = row[2] != 0;
-        if (scored) {
-            const int32_t* pp = a.partials + (size_t)b * nchunks * 2;
-            for (int c = lane; c < nchunks; c += 64) { I += pp[c * 2]; U += pp[c * 2 + 1]; }
-            I = wave_sum_i64(I); U = wave_sum_i64(U);              // integers: exact in any order
-        }
-        if (lane == 0) {
-            const float v = scored ? __fdiv_rn((float)I, (float)U) : 0.f;
-            a.iou_seg[b] = v; a.iu[b * 2] = I; a.iu[b * 2 + 1] = U;
-            if (scored) { count_sample(v, seg_n, seg_hit, seg_sum); seg_i += I; seg_u += U; }
-        }
-    }
-    if (lane == 0) {
+    __device__ __forceinline__ void store(void* acc) const {
+        long long* acc_i = reinterpret_cast<long long*>(acc);
+        double* acc_d = reinterpret_cast<double*>(acc);
         acc_i[RT_EVAL_DET_N] = det_n; acc_i[RT_EVAL_SEG_N] = seg_n;
         for (int t = 0; t < 5; ++t) { acc_i[RT_EVAL_DET_HIT + t] = det_hit[t]; acc_i[RT_EVAL_SEG_HIT + t] = seg_hit[t]; }
         acc_i[RT_EVAL_SEG_I] = seg_i; acc_i[RT_EVAL_SEG_U] = seg_u;
         acc_d[RT_EVAL_DET_SUM] = det_sum; acc_d[RT_EVAL_SEG_SUM] = seg_sum;
     }
+};
+
+// One image's box rows, by the whole wave: the r-th valid phrase of pred_b [P, K, 4] / valid_b [P, K] against target row r of tb
+// (nb rows, already clamped to [0, P]) -> out[0 .. P) (unused rows 0), counted by lane 0 in row order.  s_iou: 64 floats of shared memory.
+__device__ __forceinline__ void finish_boxes(const float* tb, int nb, const float* pred_b, const uint8_t* valid_b, int P, int K,
+                                             float* out, float* s_iou, int lane, totals& t) {
+    int base = 0, rank;
+    for (int j0 = 0; j0 < P && base < nb; j0 += 64) {
+        const int ph = j0 + lane, before = base;
+        const bool mine = rt_phrase_rank(valid_b, P, K, ph, lane, base, rank);
+        if (mine && rank < nb) {
+            const float v = box_iou_pair(to_xyxy(tb + (size_t)rank * 4), to_xyxy(pred_b + ((size_t)ph * K) * 4));
+            out[rank] = v;
+            s_iou[rank - before] = v;
+        }
+        __syncthreads();
+        if (lane == 0) {
+            const int m = min(base, nb) - before;
+            for (int i = 0; i < m; ++i) count_sample(s_iou[i], t.det_n, t.det_hit, t.det_sum);
+        }
+        __syncthreads();
+    }
+    for (int r = min(base, nb) + lane; r < P; r += 64) out[r] = 0.f;
+}
+
+// One image's mask partials pp [nchunks][2] added up by the wave -> iou_seg_b, iu_b[2], and lane 0's totals when the image is scored
+__device__ __forceinline__ void finish_mask(const int32_t* pp, int nchunks, bool scored, int lane, float* iou_seg_b, int64_t* iu_b,
+                                            totals& t) {
+    long long I = 0, U = 0;
+    if (scored) {
+        for (int c = lane; c < nchunks; c += 64) { I += pp[c * 2]; U += pp[c * 2 + 1]; }
+        I = wave_sum_i64(I); U = wave_sum_i64(U);              // integers: exact in any order
+    }
+    if (lane == 0) {
+        const float v = scored ? __fdiv_rn((float)I, (float)U) : 0.f;
+        *iou_seg_b = v; iu_b[0] = I; iu_b[1] = U;
+        if (scored) { count_sample(v, t.seg_n, t.seg_hit, t.seg_sum); t.seg_i += I; t.seg_u += U; }
+    }
+}
+
+__global__ __launch_bounds__(64) void eval_finish_kernel(const rt_eval_metrics_args a, int nchunks) {
+    __shared__ float s_iou[64];
+    const int lane = threadIdx.x;
+    totals t;
+    if (lane == 0 && !a.reset) t.load(a.acc);
+    for (int b = 0; b < a.B; ++b) {
+        const int64_t* row = a.table + (size_t)b * 5;
+        const float* tb = reinterpret_cast<const float*>(row[0]);
+        const int nb = tb ? (int)min((long long)a.P, max(0ll, (long long)row[1])) : 0;
+        finish_boxes(tb, nb, a.pred_boxes + (size_t)b * a.P * a.K * 4, a.valid + (size_t)b * a.P * a.K, a.P, a.K,
+                     a.iou_det + (size_t)b * a.P, s_iou, lane, t);
+        if (!a.masks) continue;
+        finish_mask(a.partials + (size_t)b * nchunks * 2, nchunks, row[2] != 0, lane, a.iou_seg + b, a.iu + b * 2, t);
+    }
+    if (lane == 0) t.store(a.acc);
+}
+
+// launch (b) of rt_eval_canvas: eval_finish_kernel's walk with every per-batch fact read from device memory -- the target boxes from
+// rt_batch_stage's packed buffer, the original sizes and image ids from rt_eval_facts' tables -- plus the batch's slot of the results
+// ring (rt_box_postprocess's rows, scaled to the original size) and the cursor, which this kernel advances itself.
+__global__ __launch_bounds__(64) void eval_canvas_finish_kernel(const rt_eval_canvas_args a, int nchunks) {
+    __shared__ float s_iou[64];
+    const int lane = threadIdx.x;
+    totals t;
+    if (lane == 0) t.load(a.acc);
+    const bool keep = !a.veto || a.veto[0] == 0;                             // a vetoed batch leaves totals, ring and cursor alone
+    const int slot = a.cursor[0];
+    const bool room = keep && slot >= 0 && slot < a.slots;
+    for (int b = 0; b < a.B; ++b) {
+        const float* pred_b = a.pred_boxes + (size_t)b * a.P * a.K * 4;
+        const uint8_t* valid_b = a.valid + (size_t)b * a.P * a.K;
+        const int off = a.tgt_off[b];
+        int nb = min(a.P, max(0, a.tgt_off[b + 1] - off));
+        if (off < 0 || off > a.tgt_rows - nb) nb = 0;                        // offsets that leave the staged buffer: no rows read
+        finish_boxes(a.tgt_boxes + (size_t)max(off, 0) * 4, nb, pred_b, valid_b, a.P, a.K, a.iou_det + (size_t)b * a.P, s_iou, lane, t);
+        if (a.pred_masks) finish_mask(a.partials + (size_t)b * nchunks * 2, nchunks, true, lane, a.iou_seg + b, a.iu + b * 2, t);
+        if (!room) continue;
+        const int32_t* f = a.facts + (size_t)b * 6;
+        const float oh = (float)f[2], ow = (float)f[3];
+        float* rows = a.ring_boxes + ((size_t)slot * a.B + b) * a.P * 4;
+        int base = 0, rank;
+        for (int j0 = 0; j0 < a.P; j0 += 64) {
+            const int ph = j0 + lane;
+            if (rt_phrase_rank(valid_b, a.P, a.K, ph, lane, base, rank))
+                rt_eval_shared::select_scale_box(pred_b + ((size_t)ph * a.K) * 4, true, oh, ow, rows + (size_t)rank * 4);
+        }
+        for (int i = base * 4 + lane; i < a.P * 4; i += 64) rows[i] = 0.f;
+        if (lane == 0) {
+            a.ring_counts[(size_t)slot * a.B + b] = base;
+            a.ring_ids[(size_t)slot * a.B + b] = a.image_ids[b];
+        }
+    }
+    if (lane == 0 && keep) {
+        t.store(a.acc);
+        if (room) a.cursor[0] = slot + 1; else a.cursor[1] = 1;
+    }
+}
+
+// rt_eval_facts: thread b gathers image b's int64 facts; the pointers ride in the argument block (2.1 KB of the 4 KB a launch carries)
+struct EvalFactsArgs {
+    const int64_t* size_ptr[RT_BATCH_STAGE_MAX_B]; const int64_t* orig_ptr[RT_BATCH_STAGE_MAX_B]; const int64_t* id_ptr[RT_BATCH_STAGE_MAX_B];
+    int32_t tm_hw[2 * RT_BATCH_STAGE_MAX_B];
+    int32_t* facts; int64_t* image_ids; int B;
+};
+static_assert(sizeof(EvalFactsArgs) <= 4096, "the argument block of a launch");
+
+__global__ __launch_bounds__(RT_BATCH_STAGE_MAX_B) void eval_facts_kernel(const EvalFactsArgs a) {
+    const int b = threadIdx.x;
+    if (b >= a.B) return;
+    const int64_t* sz = a.size_ptr[b];
+    const int64_t* og = a.orig_ptr[b] ? a.orig_ptr[b] : sz;
+    int32_t* f = a.facts + (size_t)b * 6;
+    f[0] = (int32_t)sz[0]; f[1] = (int32_t)sz[1]; f[2] = (int32_t)og[0]; f[3] = (int32_t)og[1];
+    f[4] = a.tm_hw[2 * b]; f[5] = a.tm_hw[2 * b + 1];
+    a.image_ids[b] = a.id_ptr[b] ? a.id_ptr[b][0] : -1;
 }
 
 }  // namespace
@@ -172,6 +235,45 @@ extern "C" int rt_eval_metrics(const rt_eval_metrics_args* a, rt_stream_t stream
         RT_CHECK_LAUNCH();
     }
     hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a, nchunks);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
+
+extern "C" int rt_eval_facts(const int64_t* const* size_ptrs, const int64_t* const* orig_ptrs, const int64_t* const* id_ptrs,
+                             const int32_t* tm_hw, int B, int32_t* facts, int64_t* image_ids, rt_stream_t stream) {
+    if (!size_ptrs || !facts || !image_ids || B <= 0) return RT_ERR_BADARG;
+    if (B > RT_BATCH_STAGE_MAX_B) return RT_ERR_UNSUPPORTED;
+    EvalFactsArgs a{};
+    for (int b = 0; b < B; ++b) {
+        if (!size_ptrs[b] || (orig_ptrs && !orig_ptrs[b]) || (id_ptrs && !id_ptrs[b])) return RT_ERR_BADARG;
+        a.size_ptr[b] = size_ptrs[b];
+        a.orig_ptr[b] = orig_ptrs ? orig_ptrs[b] : nullptr;
+        a.id_ptr[b] = id_ptrs ? id_ptrs[b] : nullptr;
+        a.tm_hw[2 * b] = tm_hw ? tm_hw[2 * b] : 0; a.tm_hw[2 * b + 1] = tm_hw ? tm_hw[2 * b + 1] : 0;
+    }
+    a.facts = facts; a.image_ids = image_ids; a.B = B;
+    hipLaunchKernelGGL(eval_facts_kernel, dim3(1), dim3(RT_BATCH_STAGE_MAX_B), 0, (hipStream_t)stream, a);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
+
+extern "C" int rt_eval_canvas(const rt_eval_canvas_args* a, rt_stream_t stream) {
+    if (!a || !a->pred_boxes || !a->valid || !a->tgt_boxes || !a->tgt_off || !a->facts || !a->image_ids || !a->iou_det || !a->acc)
+        return RT_ERR_BADARG;
+    if (!a->ring_boxes || !a->ring_counts || !a->ring_ids || !a->cursor) return RT_ERR_BADARG;
+    if (a->B <= 0 || a->P <= 0 || a->K <= 0 || a->tgt_rows < 0 || a->slots <= 0) return RT_ERR_BADARG;
+    if (a->B > RT_BATCH_STAGE_MAX_B) return RT_ERR_UNSUPPORTED;
+    int nchunks = 0;
+    if (a->pred_masks) {
+        if (!a->tgt_masks || !a->partials || !a->iou_seg || !a->iu) return RT_ERR_BADARG;
+        if (a->Q <= 0 || a->h <= 0 || a->w <= 0 || a->Hc <= 0 || a->Wc <= 0) return RT_ERR_BADARG;
+        const long long px = (long long)a->Hc * a->Wc;
+        if (px >= 0x7fffffffLL || (long long)a->h * a->w >= 0x7fffffffLL) return RT_ERR_UNSUPPORTED;
+        nchunks = (int)((px + RT_EVAL_CHUNK - 1) / RT_EVAL_CHUNK);
+        const int rc = rt_eval_canvas_launch_mask(*a, nchunks, (hipStream_t)stream);
+        if (rc != RT_OK) return rc;
+    }
+    hipLaunchKernelGGL(eval_canvas_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a, nchunks);
     RT_CHECK_LAUNCH();
     return RT_OK;
 }

@@ -11,34 +11,13 @@
 //                        scaling to the image size.  fp32 operations are issued un-fused in the reference's order
 //                        (x - 0.5*w, then * scale) so the boxes are bit-identical to its CPU result.
 // HBM-bound byte kernels: one thread per output pixel / box, coalesced 1-B stores along the row.
-#include "rt_common.h"
+// Also here: launch (a) of rt_eval_canvas (the mask partials of a canvas evaluation batch, taken from the logits), because it calls
+// mask_decision and must be compiled under this file's contraction setting -- see rt_eval_shared.h.
+#include "rt_eval_shared.h"
 
 namespace {
 
-// torch's index / weight rule for mode='bilinear', align_corners=False (ATen UpSample.h: area_pixel_compute_source_index,
-// guard_index_and_lambda): src = max(scale * (dst + 0.5) - 0.5, 0), i0 = min(int(src), in - 1), lambda1 = clamp(src - i0, 0, 1)
-__device__ __forceinline__ void bilinear_axis(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-    float src = __fsub_rn(__fmul_rn(scale, __fadd_rn((float)dst, 0.5f)), 0.5f);
-    if (src < 0.f) src = 0.f;
-    i0 = min((int)floorf(src), in - 1);
-    l1 = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.f), 1.f);
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l0 = __fsub_rn(1.f, l1);
-}
-
-// decision of frame pixel (y, x): sigmoid(bilinear(logits)) > threshold
-__device__ __forceinline__ bool mask_decision(const float* __restrict__ lg, int h, int w, int y, int x, float sh, float sw, float thr) {
-    int y0, y1, x0, x1; float ly0, ly1, lx0, lx1;
-    bilinear_axis(y, sh, h, y0, y1, ly0, ly1);
-    bilinear_axis(x, sw, w, x0, x1, lx0, lx1);
-    const float a = lg[y0 * w + x0], b = lg[y0 * w + x1], c = lg[y1 * w + x0], d = lg[y1 * w + x1];
-    // ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d), the reference kernel's association
-    const float top = __fadd_rn(__fmul_rn(lx0, a), __fmul_rn(lx1, b));
-    const float bot = __fadd_rn(__fmul_rn(lx0, c), __fmul_rn(lx1, d));
-    const float v = __fadd_rn(__fmul_rn(ly0, top), __fmul_rn(ly1, bot));
-    const float s = 1.f / (1.f + expf(-v));
-    return s > thr;
-}
+using rt_eval_shared::mask_decision;        // with bilinear_axis in rt_eval_shared.h: compiled HERE, under this file's contraction
 
 // torch 'nearest' (legacy) source index: out == in -> dst; out == 2 in -> dst >> 1; else min(int(floorf(dst * (float)in/out)), in - 1)
 __device__ __forceinline__ int nearest_src(int dst, int in, int out) {
@@ -78,21 +57,44 @@ __global__ __launch_bounds__(64) void box_postprocess_kernel(const rt_box_post_d
     for (int j0 = 0; j0 < p.P; j0 += 64) {
         const int ph = j0 + lane;
         if (!rt_phrase_rank(p.valid + (size_t)b * p.P * p.K, p.P, p.K, ph, lane, base, rank)) continue;
-        const float* s = p.boxes + ((size_t)(b * p.P + ph) * p.K) * 4;
-        const float cx = s[0], cy = s[1], w = s[2], h = s[3];
-        float x0 = __fsub_rn(cx, __fmul_rn(0.5f, w)), y0 = __fsub_rn(cy, __fmul_rn(0.5f, h));
-        float x1 = __fadd_rn(cx, __fmul_rn(0.5f, w)), y1 = __fadd_rn(cy, __fmul_rn(0.5f, h));
-        if (p.sizes) {                                  // scale_to_original_shape: boxes * [img_w, img_h, img_w, img_h]
-            const float ih = p.sizes[b * 2], iw = p.sizes[b * 2 + 1];
-            x0 = __fmul_rn(x0, iw); y0 = __fmul_rn(y0, ih); x1 = __fmul_rn(x1, iw); y1 = __fmul_rn(y1, ih);
-        }
-        float* o = p.out + ((size_t)b * p.P + rank) * 4;
-        o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1;
+        const bool scale = p.sizes != nullptr;          // scale_to_original_shape: boxes * [img_w, img_h, img_w, img_h]
+        rt_eval_shared::select_scale_box(p.boxes + ((size_t)(b * p.P + ph) * p.K) * 4, scale, scale ? p.sizes[b * 2] : 1.f,
+                                         scale ? p.sizes[b * 2 + 1] : 1.f, p.out + ((size_t)b * p.P + rank) * 4);
     }
     if (lane == 0) p.counts[b] = base;
 }
 
+// launch (a) of rt_eval_canvas (the rest: rt_eval.hip): integer {I, U} of query 0's decisions against the staged target mask over one
+// run of RT_EVAL_CHUNK pixels of the image's scored rectangle.  The decision is mask_postprocess_kernel's, frame = canvas, taken from
+// the logits (L2-resident, 16x smaller than the frame); it lives in THIS file so that both are compiled under one contraction setting.
+__global__ __launch_bounds__(256) void eval_canvas_mask_kernel(const rt_eval_canvas_args a, int nchunks) {
+    __shared__ int sm[8];
+    const int b = blockIdx.y, c = blockIdx.x;
+    const int32_t* f = a.facts + (size_t)b * 6;
+    int ih, iw;
+    rt_eval_shared::scored_rect(f[0], f[1], f[4], f[5], a.Hc, a.Wc, ih, iw);
+    int I = 0, U = 0;
+    if (ih > 0 && iw > 0) {
+        const float* lg = a.pred_masks + (size_t)b * a.Q * a.h * a.w;                  // query 0
+        const uint8_t* tg = a.tgt_masks + (size_t)b * a.Hc * a.Wc;
+        const float sh = (float)a.h / (float)a.Hc, sw = (float)a.w / (float)a.Wc;
+        const long long n = (long long)ih * iw, end = min(n, ((long long)c + 1) * RT_EVAL_CHUNK);
+        for (long long i = (long long)c * RT_EVAL_CHUNK + threadIdx.x; i < end; i += 256) {
+            const int y = (int)(i / iw), x = (int)(i - (long long)y * iw);
+            const int p = mask_decision(lg, a.h, a.w, y, x, sh, sw, a.threshold) ? 1 : 0, t = tg[(size_t)y * a.Wc + x] != 0;
+            I += p & t; U += p | t;
+        }
+    }
+    rt_eval_shared::store_block_iu(I, U, sm, a.partials + ((size_t)b * nchunks + c) * 2);
+}
+
 }  // namespace
+
+int rt_eval_canvas_launch_mask(const rt_eval_canvas_args& a, int nchunks, hipStream_t stream) {
+    hipLaunchKernelGGL(eval_canvas_mask_kernel, dim3((unsigned)nchunks, (unsigned)a.B), dim3(256), 0, stream, a, nchunks);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
 
 extern "C" int rt_mask_postprocess(const rt_mask_post_desc* d, rt_stream_t stream) {
     if (!d || !d->pred || !d->sizes || !d->masks) return RT_ERR_BADARG;

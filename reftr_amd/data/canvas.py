@@ -31,6 +31,19 @@ class StagedBatch:
 
 
 class BatchCanvas:
+    """One fixed input shape: (height, width) images, `boxes_per_image` box rows per image, target masks when `masks`.
+
+    A canvas EVALUATION batch (engine_vg.evaluate(canvas=...)) is the batch the reference's collate and evaluation loop would
+    produce if the batch held one canvas-sized image:
+      * forward and losses run on pad_on_host(samples, targets): image zero-padded to the canvas, padding mask True outside, target
+        masks zero-padded to the canvas;
+      * the mask post-processor's padded frame IS the canvas: `pred_masks` covers the canvas, so the logits are resized to
+        (height, width) -- in the reference the frame is the largest `size` of the batch, which is the same number there because the
+        batch is padded to its largest image -- and each image is then cropped to its own `size`;
+      * box metrics, the results' boxes (scaled to `orig_size`) and the mask {I, U} are what the existing kernels give on that frame
+        with the un-padded targets.
+    Nothing about a batch that already has the canvas's size changes."""
+
     def __init__(self, height, width, boxes_per_image, masks=False, tokens=None):
         self.height, self.width, self.boxes_per_image, self.masks = int(height), int(width), int(boxes_per_image), bool(masks)
         assert self.height > 0 and self.width > 0 and self.boxes_per_image > 0
@@ -92,6 +105,33 @@ class BatchCanvas:
 
     def fits(self, samples, targets):
         return self.why_not(samples, targets) is None
+
+    def why_not_eval(self, samples, targets, segm=False):
+        """What engine_vg.evaluate(canvas=...) asks of a batch ON TOP of why_not: None, or the reason as a short phrase.  The metric
+        tail of a canvas evaluation reads every per-image fact from device memory (rt_eval_facts gathers them), so every target must
+        carry them in the one form the gather takes: `size` as an int64 pair, `orig_size` likewise when any target has it, `image_id`
+        (one int64) on all targets or on none, and -- with a 'segm' post-processor -- a one-byte [1, h, w] target mask on a masks=True
+        canvas.  Tensor shapes, dtypes and key presence only: nothing is read from the device."""
+        def pair(v, n):
+            return torch.is_tensor(v) and v.dtype == torch.int64 and v.numel() == n
+        if segm and not self.masks:
+            return "a 'segm' post-processor needs a masks=True canvas"
+        any_orig = any("orig_size" in t for t in targets)
+        with_id = sum(1 for t in targets if "image_id" in t)
+        if with_id not in (0, len(targets)):
+            return "image_id on some targets only"
+        for t in targets:
+            if not pair(t.get("size"), 2):
+                return "no int64 [2] size on a target"
+            if any_orig and not pair(t.get("orig_size"), 2):
+                return "no int64 [2] orig_size on a target while another has one"
+            if with_id and not pair(t["image_id"], 1):
+                return "an image_id that is not one int64"
+            if segm:
+                m = t.get("masks")
+                if m is None or m.dim() != 3 or m.shape[0] != 1 or m.element_size() != 1:
+                    return "no one-byte [1, h, w] target mask"
+        return None
 
     # ------------------------------------------------------------------ the definition, in plain torch
     def pad_on_host(self, samples, targets):

@@ -1230,6 +1230,140 @@ class CapturedForward:
         return out
 
 
+def _loss_vector(red, weight_dict, wvec):
+    """One iteration's loss meters as ONE device vector, [unscaled..., scaled..., total] (no .item() per loss).  wvec: the (names,
+    weights on the device) of the previous call or None; returned renewed when the names changed."""
+    names = sorted(red)
+    wn = [k for k in names if k in weight_dict]
+    if wvec is None or wvec[0] != names:
+        wvec = (names, torch.tensor([weight_dict[k] for k in wn], dtype=torch.float32, device=red[names[0]].device))
+    un = torch.stack([red[k].reshape(()).float() for k in names])
+    sc = torch.stack([red[k].reshape(()).float() for k in wn]) * wvec[1]
+    return [_UNSCALED(k) for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]), wvec
+
+
+class CapturedEvalStep:
+    """One evaluation batch on a batch canvas (reftr_amd.data.canvas) as ONE replay of ONE hipGraph: forward -> criterion (reading
+    the staged targets, as CapturedTrainStep's canvas form does) -> the loss vector -> rt_eval_canvas (box selection and scaling,
+    mask decisions from the logits, metrics, running totals, the batch's slot of the results ring).  Owns the StagedBatch, the
+    per-image facts and the graph; the accumulators and the ring (`state`, a hip.EvalCanvasState) are handed in and outlive it.
+    Per batch the host issues rt_batch_stage, rt_eval_facts and the grouped token copy and replays; nothing is copied back.
+
+    The cooperative decoder's fail-safe: the graph's metric launch takes the decoder's failure word as its veto, so the device tests
+    the flag BEFORE the batch's results are kept -- a batch whose hand-off timed out leaves totals, ring and cursor untouched.
+    evaluate() then reads the word as it does on every path (one 4-byte read per batch, only while cooperative launches are in use),
+    drops the captures, and runs the batch again on the launched chain: it is counted once."""
+
+    def __init__(self, model, criterion, postprocessors, canvas, samples, targets, acc, slots, state=None):
+        self.model, self.criterion, self.canvas, self.inner = model, criterion, canvas, _inner(model)
+        self.segm = postprocessors.get("segm")
+        if canvas.tokens is None:
+            canvas.bind(samples)
+        self.key = canvas.key(samples)
+        self.staged = canvas.stage(samples, targets)              # fresh canvas-sized buffers, filled with this batch
+        self.s, self.t = self.staged.samples, [{} for _ in targets]
+        B, dev = len(targets), self.s["img"].tensors.device
+        self.facts = torch.zeros((B, 6), dtype=torch.int32, device=dev)
+        self.image_ids = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._gather_facts(targets)
+        self._wvec = None
+        self._gen = _state(model).coop_generation    # a cooperative fall-back anywhere drops this capture: it contains the launches
+        with self._building():
+            warm = []
+            _warm_up(lambda: warm.append(self._forward_losses()), 1)
+            P = int(warm[0][0]["pred_boxes"].shape[1])
+            from . import hip as H
+            self.state = state if state is not None else H.EvalCanvasState(slots, B, P, dev, acc=acc)
+            assert self.state.B == B and self.state.P == P
+            # read after the warm-up: the hand-off buffer exists by now (None: no cooperative launches in this configuration)
+            self.fail_word = self.inner.coop_failure_word() if hasattr(self.inner, "coop_failure_word") else None
+            del warm
+            self.graph = torch.cuda.CUDAGraph()
+            with _capture(self.graph):
+                outputs, self.names, self.vec = self._forward_losses()
+                self.last = self._tail(outputs)
+            self.outputs = outputs
+
+    @contextlib.contextmanager
+    def _building(self):
+        crit, st = self.criterion, self.staged
+        crit.targets_static, crit.target_masks_static = st.targets_static, st.tgt_masks
+        try:
+            yield
+        finally:
+            crit.targets_static = crit.target_masks_static = None
+
+    def _gather_facts(self, targets):
+        from . import hip as H
+        origs = [t["orig_size"] for t in targets] if "orig_size" in targets[0] else None
+        ids = [t["image_id"] for t in targets] if "image_id" in targets[0] else None
+        hw = [tuple(t["masks"].shape[-2:]) for t in targets] if self.segm is not None else None
+        H.eval_facts([t["size"] for t in targets], self.facts, self.image_ids, origs=origs, ids=ids, mask_hw=hw)
+
+    def _forward_losses(self):
+        outputs = self.model(self.s)
+        names, vec, self._wvec = _loss_vector(utils.reduce_dict(self.criterion(outputs, self.t)), self.criterion.weight_dict, self._wvec)
+        return outputs, names, vec
+
+    def _tail(self, outputs):
+        from . import hip as H
+        boxes = outputs["pred_boxes"]
+        B, P, K, _ = boxes.shape
+        pm = None
+        if self.segm is not None:
+            pm = outputs["pred_masks"]
+            pm = (pm.squeeze(2) if pm.dim() == 5 else pm).to(torch.float32).contiguous()
+        st = self.staged
+        return H.eval_canvas(boxes.to(torch.float32).contiguous(), outputs["phrase_mask"].reshape(B, P, K).to(torch.uint8).contiguous(),
+                             st.targets_static[0], st.targets_static[1], self.facts, self.image_ids, self.state, pred_masks=pm,
+                             tgt_masks=st.tgt_masks if pm is not None else None,
+                             threshold=self.segm.threshold if self.segm is not None else 0.5, veto=self.fail_word)
+
+    @torch.no_grad()
+    def __call__(self, samples, targets):
+        """Stages the batch, replays, and returns the loss meters' (names, device vector) -- a static buffer the next replay rewrites."""
+        inner = self.inner
+        if inner._flush_pending is not None:
+            inner._flush_pending()
+        if inner._operands_dirty:                    # weights changed since the capture: rebuild the bf16 operands eagerly
+            inner.refresh_operands()
+            if inner._lin_refresh_pending:
+                inner.net.refresh(); inner._lin_refresh_pending = False
+        self.canvas.stage(samples, targets, out=self.staged, tokens=False)
+        self._gather_facts(targets)
+        _copy_batch(self.s, [], {k: v for k, v in samples.items() if k != "img"}, [])
+        self.graph.replay()
+        return self.names, self.vec
+
+
+def _eval_canvas_active(model, criterion, postprocessors, device, visualize, canvas):
+    """Whether evaluate() runs its batches through `canvas`.  Refuses what a canvas evaluation cannot do -- before anything is
+    launched -- and says once why it ignores the canvas where the loop it would replace is switched off or not this package's."""
+    if canvas is None:
+        return False
+    if _multi_rank():
+        raise NotImplementedError("evaluate(canvas=) is not available on more than one rank: the box count the criterion normalises by "
+                                  "is averaged over the ranks, and the count a canvas batch stages is this rank's")
+    if visualize:
+        raise NotImplementedError("evaluate(canvas=, visualize=True): the dumps need per-image masks_origin views, which a canvas "
+                                  "evaluation never materialises")
+    why = None
+    if os.environ.get("REFTR_EVAL_GRAPH", "1") != "1":
+        why = "REFTR_EVAL_GRAPH=0"
+    elif os.environ.get("REFTR_EVAL_METRICS", "1") != "1":
+        why = "REFTR_EVAL_METRICS=0"
+    elif torch.device(device).type != "cuda":
+        why = "a CPU device"
+    elif not _metered(postprocessors, device):
+        why = "a post-processor that is not this package's"
+    elif not hasattr(criterion, "targets_static"):
+        why = "a criterion without targets_static"
+    if why is not None:
+        _say_once(model, ("eval-canvas", why), f"[reftr_amd] evaluate: {canvas!r} is ignored ({why}); every batch runs at its own shape")
+        return False
+    return True
+
+
 def _vis_dirs(output_dir, split):
     """output_dir/vis/<split>/{mask,bbox,att,gt} (engine_vg.py:86-94)."""
     from pathlib import Path
@@ -1308,7 +1442,7 @@ def _fill_results(results_dict, targets, results_scaled):
 
 
 @torch.no_grad()
-def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=None, visualize=False):
+def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=None, visualize=False, canvas=None):
     """engine_vg.evaluate (engine_vg.py:82-225): losses, Acc@0.5 / mean IoU of the predicted boxes (:127-140), mask IoU when a
     'segm' post-processor is present (:143-152), boxes scaled to the original image size in the returned results dict (:141,203).
     On a GPU the metrics are scored by metrics.EvalMeter (csrc/rt_eval.hip: one ABI call per batch, the running totals stay on the
@@ -1316,8 +1450,16 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     CPU device) runs the reference's per-image torch loop, without the new keys.
     `visualize` (needs the 'segm' post-processor, `output_dir` and a dataset with `split` / `pull_item`, as in the reference):
     per sample the predicted mask, the ground-truth mask, the image with both boxes and four attention maps under
-    output_dir/vis/<split>/{mask,gt,bbox,att} (:86-96,157-192)."""
+    output_dir/vis/<split>/{mask,gt,bbox,att} (:86-96,157-192).
+    canvas (reftr_amd.data.canvas.BatchCanvas): ragged validation data -- every batch that fits the canvas (why_not and why_not_eval)
+    is staged into canvas buffers and runs as one replay of one captured graph (CapturedEvalStep; one capture per batch size), with no
+    device-to-host copy per batch: totals and result boxes stay on the device and are read back once after the loop.  What such a batch
+    computes is defined in BatchCanvas' docstring.  A batch that does not fit takes the path below at its own shape (said once per
+    reason) and adds to the same totals and results, in loader order.  NotImplementedError on more than one rank and with
+    `visualize`; ignored (said once) with REFTR_EVAL_GRAPH=0, REFTR_EVAL_METRICS=0, a CPU device, a foreign post-processor or a
+    criterion without `targets_static`.  canvas=None: the loop below, unchanged."""
     from .util.box_ops import mask_iou
+    on_canvas = _eval_canvas_active(model, criterion, postprocessors, device, visualize, canvas)
     model.eval()
     criterion.eval()
     board = utils.StatBoard()
@@ -1336,7 +1478,41 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     # shapes, then eager launches); REFTR_EVAL_GRAPH=0: always eager
     fwd = CapturedForward(model) if (os.environ.get("REFTR_EVAL_GRAPH", "1") == "1" and torch.device(device).type == "cuda") else model
     wvec = None
-    for _ in board.log_every(range(len(data_loader)), 50, "Test:"):
+    # canvas: captures by canvas key, their rings (which outlive a capture dropped by the cooperative fall-back), and what went where
+    steps, rings, order = {}, {}, []
+    if on_canvas:
+        meter.begin_external()
+    for batch_no in board.log_every(range(len(data_loader)), 50, "Test:"):
+        if on_canvas:
+            segm = "segm" in postprocessors
+            why = canvas.why_not(samples, targets) or canvas.why_not_eval(samples, targets, segm=segm)
+            if why is not None:
+                _say_once(model, ("eval-canvas", why), f"[reftr_amd] evaluate: a batch does not fit {canvas!r} ({why}): it runs at its "
+                          "own shape")
+            else:
+                key = canvas.key(samples)
+                if any(st._gen != _state(model).coop_generation for st in steps.values()):
+                    steps.clear()
+                for attempt in (0, 1):
+                    step = steps.get(key)
+                    if step is None:
+                        ring = rings.get(key)
+                        step = steps[key] = CapturedEvalStep(model, criterion, postprocessors, canvas, samples, targets, meter.acc,
+                                                             len(data_loader), state=ring[0] if ring else None)
+                        if ring is None:
+                            ring = rings[key] = (step.state, [])
+                    names, vec = step(samples, targets)
+                    if attempt or not _cooperative_failed(model):
+                        break
+                    _coop_fallback(model)        # the device kept nothing of this batch (the failure word vetoed it): run it again
+                    steps.clear()
+                board.add_device(names, vec)
+                meter.note_external(len(targets), segm)
+                ring = rings[key]
+                order.append((key, len(ring[1])))
+                ring[1].append((batch_no, "image_id" in targets[0], [int(t["boxes"].shape[0]) for t in targets]))
+                samples, targets = prefetcher.next()
+                continue
         outputs = fwd(samples)
         if _cooperative_failed(model):           # a hand-off timed out: the batch is run again on the launched chain
             _coop_fallback(model)
@@ -1345,13 +1521,8 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
         weight_dict = criterion.weight_dict
         red = utils.reduce_dict(loss_dict)
         # meters stay on the device (no .item() per loss): [unscaled..., scaled..., total] of this iteration in one vector
-        names = sorted(red)
-        wn = [k for k in names if k in weight_dict]
-        if wvec is None or wvec[0] != names:
-            wvec = (names, torch.tensor([weight_dict[k] for k in wn], dtype=torch.float32, device=red[names[0]].device))
-        un = torch.stack([red[k].reshape(()).float() for k in names])
-        sc = torch.stack([red[k].reshape(()).float() for k in wn]) * wvec[1]
-        board.add_device([_UNSCALED(k) for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]))
+        names, vec, wvec = _loss_vector(red, weight_dict, wvec)
+        board.add_device(names, vec)
         key = "orig_size" if "orig_size" in targets[0] else "size"
         orig_sizes = torch.stack([t[key] for t in targets], dim=0)
         if meter is not None:
@@ -1369,7 +1540,11 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
                                       results_scaled[i]["boxes"][0], outputs["mask_att"][i])
             else:
                 meter.update(outputs, targets)
-            _fill_results(results_dict, targets, results_scaled)
+            if on_canvas:                        # a misfit between canvas batches: merged with the ring's results in loader order
+                order.append({})
+                _fill_results(order[-1], targets, results_scaled)
+            else:
+                _fill_results(results_dict, targets, results_scaled)
             samples, targets = prefetcher.next()
             continue
         results = postprocessors["bbox"](outputs, orig_sizes)
@@ -1393,6 +1568,16 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
                 results_dict[int(tg["image_id"])] = res["boxes"].cpu().numpy().tolist()
         samples, targets = prefetcher.next()
     _check_cooperative(model)
+    if on_canvas:
+        # the ONE read-back of the result boxes: every ring once, then a pure host decode (metrics.decode_ring), merged in loader order
+        from .metrics import decode_ring
+        decoded = {}
+        for key, (state, batches) in rings.items():
+            cursor, overflow = state.cursor.tolist()
+            decoded[key] = decode_ring(state.boxes.cpu().numpy(), state.counts.cpu().numpy(), state.ids.cpu().numpy(), cursor, overflow,
+                                       batches)
+        for entry in order:
+            results_dict.update(entry if isinstance(entry, dict) else decoded[entry[0]][entry[1]])
     board.synchronize_between_processes()
     stats = board.global_avg()
     if meter is not None:

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2, 3
 _c_float_p = POINTER(c_float)
@@ -246,6 +246,15 @@ class EvalMetricsArgs(Structure):
                 ("reset", c_int32)]
 
 
+class EvalCanvasArgs(Structure):
+    _fields_ = [("pred_boxes", c_void_p), ("valid", c_void_p), ("tgt_boxes", c_void_p), ("tgt_off", c_void_p), ("facts", c_void_p),
+                ("image_ids", c_void_p), ("pred_masks", c_void_p), ("tgt_masks", c_void_p), ("partials", c_void_p),
+                ("iou_det", c_void_p), ("iou_seg", c_void_p), ("iu", c_void_p), ("acc", c_void_p), ("ring_boxes", c_void_p),
+                ("ring_counts", c_void_p), ("ring_ids", c_void_p), ("cursor", c_void_p), ("veto", c_void_p),
+                ("B", c_int32), ("P", c_int32), ("K", c_int32), ("Q", c_int32), ("h", c_int32), ("w", c_int32), ("Hc", c_int32),
+                ("Wc", c_int32), ("tgt_rows", c_int32), ("slots", c_int32), ("threshold", c_float)]
+
+
 DEC_MAX_LAYERS = 8
 
 
@@ -344,6 +353,9 @@ _SIGNATURES = {
     "rt_mask_postprocess": (c_int, [POINTER(MaskPostDesc), c_void_p]),
     "rt_box_postprocess": (c_int, [POINTER(BoxPostDesc), c_void_p]),
     "rt_eval_metrics": (c_int, [POINTER(EvalMetricsArgs), c_void_p]),
+    "rt_eval_facts": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32), c_int, c_void_p,
+                              c_void_p, c_void_p]),
+    "rt_eval_canvas": (c_int, [POINTER(EvalCanvasArgs), c_void_p]),
     "rt_small_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rt_pos_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rt_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1243,6 +1255,80 @@ def eval_metrics(pred_boxes, valid_u8, table, acc, masks=None, sizes_i32=None, r
     a = EvalMetricsArgs(_p(pred_boxes), _p(valid_u8), _p(table), _p(masks), _p(sizes_i32), _p(partials), _p(iou_det), _p(iou_seg),
                         _p(iu), _p(acc), B, P, K, Q, max_h, max_w, 1 if reset else 0)
     _check(lib().rt_eval_metrics(ctypes.byref(a), _stream()), "rt_eval_metrics")
+    return iou_det, iou_seg, iu
+
+
+def eval_facts(sizes, facts, image_ids, origs=None, ids=None, mask_hw=None):
+    """rt_eval_facts: the per-image facts of one evaluation batch gathered on the device in one launch.  sizes / origs: B device
+    int64 tensors of two elements ({h, w}; origs None: the sizes), ids: B device int64 tensors of one element (None: -1), mask_hw: B
+    (h, w) pairs of python ints (None: 0, 0) -> facts int32 [B, 6], image_ids int64 [B].  The pointers go by value in the kernel
+    arguments: nothing is copied to the device and nothing synchronises."""
+    B = len(sizes)
+    _req(facts, torch.int32, "facts"); _req(image_ids, torch.int64, "image_ids")
+    assert facts.numel() == 6 * B and image_ids.numel() == B and facts.is_contiguous()
+
+    def ptrs(ts, n):
+        if ts is None:
+            return None
+        assert len(ts) == B
+        for t in ts:
+            assert t.is_cuda and t.dtype == torch.int64 and t.numel() == n and t.is_contiguous(), (t.dtype, tuple(t.shape))
+        return (c_void_p * B)(*[t.data_ptr() for t in ts])
+    hw = None
+    if mask_hw is not None:
+        assert len(mask_hw) == B
+        hw = (ctypes.c_int32 * (2 * B))(*[int(v) for p in mask_hw for v in p])
+    _check(lib().rt_eval_facts(ptrs(sizes, 2), ptrs(origs, 2), ptrs(ids, 1), hw, B, _p(facts), _p(image_ids), _stream()),
+           "rt_eval_facts")
+
+
+class EvalCanvasState:
+    """What rt_eval_canvas keeps in device memory over an evaluation: `acc` (int64 [EVAL_SLOTS], shared with rt_eval_metrics), the
+    results ring of `slots` batches of B images with P phrase rows (boxes fp32 [slots, B, P, 4], counts int32 [slots, B], ids int64
+    [slots, B]) and `cursor` int32 [2] = {next slot, overflow}.  The caller zeroes acc and cursor once, before the first batch."""
+
+    def __init__(self, slots, B, P, device, acc=None):
+        self.slots, self.B, self.P = int(slots), int(B), int(P)
+        self.acc = torch.zeros(EVAL_SLOTS, dtype=torch.int64, device=device) if acc is None else acc
+        self.boxes = torch.zeros((self.slots, B, P, 4), dtype=torch.float32, device=device)
+        self.counts = torch.zeros((self.slots, B), dtype=torch.int32, device=device)
+        self.ids = torch.zeros((self.slots, B), dtype=torch.int64, device=device)
+        self.cursor = torch.zeros(2, dtype=torch.int32, device=device)
+
+
+def eval_canvas(pred_boxes, valid_u8, tgt_boxes, tgt_off, facts, image_ids, state, pred_masks=None, tgt_masks=None, threshold=0.5,
+                out=None, veto=None):
+    """rt_eval_canvas for one canvas batch: pred_boxes fp32 [B, P, K, 4], valid uint8 [B, P, K], tgt_boxes / tgt_off what batch_stage
+    wrote, facts / image_ids what eval_facts wrote, state an EvalCanvasState (accumulators, ring and cursor, updated in place).
+    pred_masks fp32 [B, Q, h, w] + tgt_masks uint8 [B, 1, Hc, Wc] add the mask part (query 0 of every image, frame = canvas).
+    veto: device int32 word; non-zero at run time -> the batch leaves accumulators, ring and cursor untouched.
+    `out` = (iou_det, iou_seg, iu, partials) to write into (a captured graph's static outputs); fresh tensors when None.
+    Returns (iou_det fp32 [B, P], iou_seg fp32 [B] | None, iu int64 [B, 2] | None) of this batch."""
+    B, P, K, _ = pred_boxes.shape
+    _req(pred_boxes, torch.float32, "pred_boxes"); _req(valid_u8, torch.uint8, "valid"); _req(tgt_boxes, torch.float32, "tgt_boxes")
+    _req(tgt_off, torch.int32, "tgt_off"); _req(facts, torch.int32, "facts"); _req(image_ids, torch.int64, "image_ids")
+    _req(pred_masks, torch.float32, "pred_masks"); _req(tgt_masks, torch.uint8, "tgt_masks"); _req(veto, torch.int32, "veto")
+    assert tuple(valid_u8.shape) == (B, P, K) and tgt_off.numel() == B + 1 and facts.numel() == 6 * B and image_ids.numel() == B
+    assert pred_boxes.is_contiguous() and valid_u8.is_contiguous() and tgt_boxes.is_contiguous()
+    assert state.B == B and state.P == P and state.acc.numel() == EVAL_SLOTS
+    Q = h = w = Hc = Wc = 0
+    iou_det, iou_seg, iu, partials = out if out is not None else (None, None, None, None)
+    if iou_det is None:
+        iou_det = _new((B, P), torch.float32, pred_boxes)
+    if pred_masks is not None:
+        assert tgt_masks is not None and pred_masks.dim() == 4 and pred_masks.shape[0] == B and pred_masks.is_contiguous()
+        Q, h, w = (int(v) for v in pred_masks.shape[1:])
+        Hc, Wc = (int(v) for v in tgt_masks.shape[-2:])
+        assert tgt_masks.numel() == B * Hc * Wc and tgt_masks.is_contiguous()
+        if iou_seg is None:
+            partials = _new((B, max(1, -(-(Hc * Wc) // EVAL_CHUNK)), 2), torch.int32, pred_boxes)
+            iou_seg = _new((B,), torch.float32, pred_boxes)
+            iu = _new((B, 2), torch.int64, pred_boxes)
+    a = EvalCanvasArgs(_p(pred_boxes), _p(valid_u8), _p(tgt_boxes), _p(tgt_off), _p(facts), _p(image_ids), _p(pred_masks),
+                       _p(tgt_masks) if pred_masks is not None else None, _p(partials), _p(iou_det), _p(iou_seg), _p(iu), _p(state.acc),
+                       _p(state.boxes), _p(state.counts), _p(state.ids), _p(state.cursor), _p(veto), B, P, K, Q, h, w, Hc, Wc,
+                       int(tgt_boxes.shape[0]), state.slots, float(threshold))
+    _check(lib().rt_eval_canvas(ctypes.byref(a), _stream()), "rt_eval_canvas")
     return iou_det, iou_seg, iu
 
 

@@ -70,6 +70,31 @@ def stats_from_accumulators(slots, seg=False, world=1, local_seg_n=0):
     return stats
 
 
+def decode_ring(boxes, counts, ids, cursor, overflow, batches):
+    """The results ring of rt_eval_canvas, read back once after an evaluation, as one results dict per slot (the caller merges them
+    in loader order).  Pure host work on numpy arrays:
+    boxes float32 [slots, B, P, 4], counts int32 [slots, B], ids int64 [slots, B]; cursor / overflow: the two device words as ints;
+    batches: one (batch number in the loader, has_ids, [target boxes per image as the host knew them from shapes]) per slot, in
+    the order the batches were replayed.
+    dict[int(image_id)] = the image's boxes as nested lists of python floats (float64 holds every fp32 coordinate exactly;
+    the ids stay integers).  An image of a batch without `image_id` is skipped.  The reference's assertion -- as many result boxes
+    as target boxes, engine_vg.py:128 -- is checked here, naming the batch and the image.  A ring that overflowed, or whose cursor
+    is not the number of replayed batches, raises RuntimeError: results would be missing."""
+    if overflow:
+        raise RuntimeError(f"evaluation results ring overflowed ({boxes.shape[0]} slots, {len(batches)} batches replayed)")
+    if int(cursor) != len(batches):
+        raise RuntimeError(f"evaluation results ring holds {int(cursor)} batches, {len(batches)} were replayed")
+    out = []
+    for slot, (number, has_ids, n_boxes) in enumerate(batches):
+        out.append({})
+        for b, n in enumerate(n_boxes):
+            c = int(counts[slot, b])
+            assert c == int(n), f"batch {number}, image {b}: {c} result boxes for {int(n)} target boxes"
+            if has_ids:
+                out[-1][int(ids[slot, b])] = np.asarray(boxes[slot, b, :c], dtype=np.float64).tolist()
+    return out
+
+
 class EvalMeter:
     """Running evaluation metrics on `device`: update() per batch (two kernel launches, one host-to-device copy, no sync),
     compute() once at the end (one all-reduce pair under torch.distributed, one device-to-host copy)."""
@@ -88,6 +113,18 @@ class EvalMeter:
         self.local_seg_n = 0
         self.last = None
         self._keep = None
+
+    def begin_external(self):
+        """For a loop in which another producer (engine_vg.CapturedEvalStep: rt_eval_canvas inside a replayed graph) adds to `acc`
+        beside update(): the accumulators are zeroed NOW and no later update resets them."""
+        self.acc.zero_()
+        self._fresh = False
+
+    def note_external(self, n_images, seg):
+        """Books a batch that the other producer scored: the mask keys and this rank's seg sample count, as update() books them."""
+        if seg:
+            self.seg = True if self._seg is None else self.seg
+            self.local_seg_n += int(n_images)
 
     @torch.no_grad()
     def update(self, outputs, targets, masks=None, sizes=None):
