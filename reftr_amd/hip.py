@@ -15,238 +15,235 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
 ABI_VERSION = 38
 
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2, 3
-_c_float_p = POINTER(c_float)
+# The Python copy of the header's #defines and enumerators (tests/test_abi.py prints each from C and compares) ...
+CONSTANTS = {
+    "RT_ACT_NONE": 0, "RT_ACT_RELU": 1, "RT_ACT_GELU": 2, "RT_ACT_TANH": 3,
+    "RT_ACCUM_FIRST": 0, "RT_ACCUM_ADD": 1, "RT_ACCUM_FINISH": 2, "RT_GRAD_ACCUM_SLOTS": 2048,
+    # gradient-norm accumulator slots (rt_sqnorm_finish)
+    "RT_SQ_SLOTS": 256, "RT_SQ_STRIDE": 32,
+    "RT_MASK_LOSS_PARTIALS": 1024, "RT_STATS_MAX": 40,
+    "RT_BATCH_STAGE_MAX_B": 64,          # what fits the kernel's argument block
+    # rt_eval_metrics: accumulator slots (8 bytes each: int64 but for the two double sums) and the mask kernel's pixels per workgroup
+    "RT_EVAL_DET_N": 0, "RT_EVAL_DET_HIT": 1, "RT_EVAL_SEG_N": 6, "RT_EVAL_SEG_HIT": 7, "RT_EVAL_SEG_I": 12, "RT_EVAL_SEG_U": 13,
+    "RT_EVAL_DET_SUM": 14, "RT_EVAL_SEG_SUM": 15, "RT_EVAL_SLOTS": 16, "RT_EVAL_CHUNK": 16384,
+    "RT_DEC_MAX_LAYERS": 8, "RT_DEC_HANDOFF_BYTES": 256 + 16 * 256 * 36 + 16 * 2048 * 4,
+}
+# ... and its public names: every key without the "RT_" (hip.ACT_RELU, hip.SQ_SLOTS, hip.EVAL_SLOTS, hip.DEC_MAX_LAYERS, ...)
+globals().update({name[3:]: value for name, value in CONSTANTS.items()})
+
+STRUCTS = {}          # C typedef name -> its ctypes class (tests/test_abi.py checks every field's offset and size against the header)
 
 
-class ConvGemmDesc(Structure):
-    _fields_ = [
-        ("src", c_void_p), ("wgt", c_void_p), ("out_bf16", c_void_p), ("out_f32", c_void_p),
-        ("bias", c_void_p), ("res_f32", c_void_p), ("res_bf16", c_void_p), ("gate", c_void_p),
-        ("preact", c_void_p),
-        ("B", c_int32), ("SH", c_int32), ("SW", c_int32), ("SC", c_int32),
-        ("DH", c_int32), ("DW", c_int32), ("N", c_int32),
-        ("KH", c_int32), ("KW", c_int32), ("stride", c_int32), ("pad", c_int32),
-        ("transposed", c_int32), ("act", c_int32),
-        ("gate_scale", c_float), ("drop_p", c_float), ("drop_seed", c_uint32), ("tile_hint", c_int32),
-        ("out_preact", c_void_p), ("dtanh", c_void_p), ("res_first", c_int32), ("seed_dev", c_void_p),
-        ("drop_shift", c_int32), ("acc2_f32", c_void_p), ("dil", c_int32),
-    ]
+class _Abi(Structure):
+    """Base of every bound struct; `c` = its typedef in the header."""
+
+    def __init_subclass__(cls, c):
+        cls.C_NAME = c
+        STRUCTS[c] = cls
 
 
-class ConvWgradDesc(Structure):
-    _fields_ = [
-        ("dy", c_void_p), ("x", c_void_p), ("dw", c_void_p), ("scale", c_void_p),
-        ("B", c_int32), ("SH", c_int32), ("SW", c_int32), ("SC", c_int32),
-        ("DH", c_int32), ("DW", c_int32), ("N", c_int32),
-        ("KH", c_int32), ("KW", c_int32), ("stride", c_int32), ("pad", c_int32),
-        ("msplit", c_int32), ("dbias", c_void_p), ("variant", c_int32),
-        ("workspace", c_void_p), ("workspace_bytes", ctypes.c_int64), ("overwrite", c_int32), ("dil", c_int32),
-        ("sqacc", c_void_p), ("g16", c_void_p),
-    ]
+class ConvGemmDesc(_Abi, c="rt_conv_gemm_desc"):
+    _fields_ = [("src", c_void_p), ("wgt", c_void_p), ("out_bf16", c_void_p), ("out_f32", c_void_p),
+                ("bias", c_void_p), ("res_f32", c_void_p), ("res_bf16", c_void_p), ("gate", c_void_p),
+                ("preact", c_void_p),
+                ("B", c_int32), ("SH", c_int32), ("SW", c_int32), ("SC", c_int32),
+                ("DH", c_int32), ("DW", c_int32), ("N", c_int32),
+                ("KH", c_int32), ("KW", c_int32), ("stride", c_int32), ("pad", c_int32),
+                ("transposed", c_int32), ("act", c_int32),
+                ("gate_scale", c_float), ("drop_p", c_float), ("drop_seed", c_uint32), ("tile_hint", c_int32),
+                ("out_preact", c_void_p), ("dtanh", c_void_p), ("res_first", c_int32), ("seed_dev", c_void_p),
+                ("drop_shift", c_int32), ("acc2_f32", c_void_p), ("dil", c_int32)]
 
 
-class LayerNormDesc(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("y_f32", c_void_p), ("y_bf16", c_void_p),
-        ("pos", c_void_p), ("ypos_bf16", c_void_p), ("mean", c_void_p), ("rstd", c_void_p),
-        ("M", c_int32), ("D", c_int32), ("eps", c_float), ("act", c_int32),
-        ("drop_p", c_float), ("drop_seed", c_uint32),
-        ("grp_rows", c_int32), ("grp_stride", c_int32), ("grp_off", c_int32), ("seed_dev", c_void_p),
-    ]
+class ConvWgradDesc(_Abi, c="rt_conv_wgrad_desc"):
+    _fields_ = [("dy", c_void_p), ("x", c_void_p), ("dw", c_void_p), ("scale", c_void_p),
+                ("B", c_int32), ("SH", c_int32), ("SW", c_int32), ("SC", c_int32),
+                ("DH", c_int32), ("DW", c_int32), ("N", c_int32),
+                ("KH", c_int32), ("KW", c_int32), ("stride", c_int32), ("pad", c_int32),
+                ("msplit", c_int32), ("dbias", c_void_p), ("variant", c_int32),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64), ("overwrite", c_int32), ("dil", c_int32),
+                ("sqacc", c_void_p), ("g16", c_void_p)]
 
 
-class LayerNormBwdDesc(Structure):
-    _fields_ = [
-        ("dy", c_void_p), ("dy2", c_void_p), ("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
-        ("mean", c_void_p), ("rstd", c_void_p), ("dx_f32", c_void_p), ("dx_bf16", c_void_p),
-        ("dgamma", c_void_p), ("dbeta", c_void_p),
-        ("M", c_int32), ("D", c_int32), ("act", c_int32),
-        ("drop_p", c_float), ("drop_seed", c_uint32), ("drop2_p", c_float), ("drop2_seed", c_uint32),
-        ("grp_rows", c_int32), ("grp_stride", c_int32), ("grp_off", c_int32), ("seed_dev", c_void_p),
-        ("partials", c_void_p), ("n_blocks_out", POINTER(c_int32)),
-    ]
+class LayerNormDesc(_Abi, c="rt_layernorm_desc"):
+    _fields_ = [("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("y_f32", c_void_p), ("y_bf16", c_void_p),
+                ("pos", c_void_p), ("ypos_bf16", c_void_p), ("mean", c_void_p), ("rstd", c_void_p),
+                ("M", c_int32), ("D", c_int32), ("eps", c_float), ("act", c_int32),
+                ("drop_p", c_float), ("drop_seed", c_uint32),
+                ("grp_rows", c_int32), ("grp_stride", c_int32), ("grp_off", c_int32), ("seed_dev", c_void_p)]
 
 
-class LnPgJob(Structure):
+class LayerNormBwdDesc(_Abi, c="rt_layernorm_bwd_desc"):
+    _fields_ = [("dy", c_void_p), ("dy2", c_void_p), ("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
+                ("mean", c_void_p), ("rstd", c_void_p), ("dx_f32", c_void_p), ("dx_bf16", c_void_p),
+                ("dgamma", c_void_p), ("dbeta", c_void_p),
+                ("M", c_int32), ("D", c_int32), ("act", c_int32),
+                ("drop_p", c_float), ("drop_seed", c_uint32), ("drop2_p", c_float), ("drop2_seed", c_uint32),
+                ("grp_rows", c_int32), ("grp_stride", c_int32), ("grp_off", c_int32), ("seed_dev", c_void_p),
+                ("partials", c_void_p), ("n_blocks_out", POINTER(c_int32))]
+
+
+class LnPgJob(_Abi, c="rt_ln_pg_job"):
     _fields_ = [("partials", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p), ("n_blocks", c_int32), ("D", c_int32)]
 
 
-class GroupNormDesc(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("stats", c_void_p),
-        ("y_f32", c_void_p), ("y_bf16", c_void_p), ("pos", c_void_p), ("ypos_bf16", c_void_p),
-        ("B", c_int32), ("HW", c_int32), ("C", c_int32), ("G", c_int32), ("eps", c_float),
-        ("out_rows_per_img", c_int32), ("out_row_off", c_int32), ("partials", c_void_p), ("chunks", c_int32),
-    ]
+class GroupNormDesc(_Abi, c="rt_groupnorm_desc"):
+    _fields_ = [("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("stats", c_void_p),
+                ("y_f32", c_void_p), ("y_bf16", c_void_p), ("pos", c_void_p), ("ypos_bf16", c_void_p),
+                ("B", c_int32), ("HW", c_int32), ("C", c_int32), ("G", c_int32), ("eps", c_float),
+                ("out_rows_per_img", c_int32), ("out_row_off", c_int32), ("partials", c_void_p), ("chunks", c_int32)]
 
 
-class GroupNormBwdDesc(Structure):
-    _fields_ = [
-        ("dy", c_void_p), ("dy2", c_void_p), ("x", c_void_p), ("gamma", c_void_p), ("stats", c_void_p),
-        ("bstats", c_void_p), ("dx_f32", c_void_p), ("dx_bf16", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p),
-        ("B", c_int32), ("HW", c_int32), ("C", c_int32), ("G", c_int32), ("eps", c_float),
-        ("out_rows_per_img", c_int32), ("out_row_off", c_int32),
-    ]
+class GroupNormBwdDesc(_Abi, c="rt_groupnorm_bwd_desc"):
+    _fields_ = [("dy", c_void_p), ("dy2", c_void_p), ("x", c_void_p), ("gamma", c_void_p), ("stats", c_void_p),
+                ("bstats", c_void_p), ("dx_f32", c_void_p), ("dx_bf16", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p),
+                ("B", c_int32), ("HW", c_int32), ("C", c_int32), ("G", c_int32), ("eps", c_float),
+                ("out_rows_per_img", c_int32), ("out_row_off", c_int32)]
 
 
-class AttnDesc(Structure):
-    _fields_ = [
-        ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("out", c_void_p), ("lse", c_void_p), ("kpm", c_void_p),
-        ("B", c_int32), ("H", c_int32), ("Sq", c_int32), ("Sk", c_int32), ("dh", c_int32),
-        ("ldq", c_int32), ("ldk", c_int32), ("ldv", c_int32), ("ldo", c_int32),
-        ("scale", c_float), ("drop_p", c_float), ("drop_seed", c_uint32), ("seed_dev", c_void_p),
-    ]
+class AttnDesc(_Abi, c="rt_attn_desc"):
+    _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("out", c_void_p), ("lse", c_void_p), ("kpm", c_void_p),
+                ("B", c_int32), ("H", c_int32), ("Sq", c_int32), ("Sk", c_int32), ("dh", c_int32),
+                ("ldq", c_int32), ("ldk", c_int32), ("ldv", c_int32), ("ldo", c_int32),
+                ("scale", c_float), ("drop_p", c_float), ("drop_seed", c_uint32), ("seed_dev", c_void_p)]
 
 
-class AttnBwdDesc(Structure):
-    _fields_ = [
-        ("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("out", c_void_p), ("dout", c_void_p),
-        ("lse", c_void_p), ("delta", c_void_p), ("kpm", c_void_p), ("dq", c_void_p), ("dk", c_void_p), ("dv", c_void_p),
-        ("B", c_int32), ("H", c_int32), ("Sq", c_int32), ("Sk", c_int32), ("dh", c_int32),
-        ("ldq", c_int32), ("ldk", c_int32), ("ldv", c_int32), ("ldo", c_int32),
-        ("lddq", c_int32), ("lddk", c_int32), ("lddv", c_int32),
-        ("scale", c_float), ("drop_p", c_float), ("drop_seed", c_uint32), ("seed_dev", c_void_p),
-    ]
+class AttnBwdDesc(_Abi, c="rt_attn_bwd_desc"):
+    _fields_ = [("q", c_void_p), ("k", c_void_p), ("v", c_void_p), ("out", c_void_p), ("dout", c_void_p),
+                ("lse", c_void_p), ("delta", c_void_p), ("kpm", c_void_p), ("dq", c_void_p), ("dk", c_void_p), ("dv", c_void_p),
+                ("B", c_int32), ("H", c_int32), ("Sq", c_int32), ("Sk", c_int32), ("dh", c_int32),
+                ("ldq", c_int32), ("ldk", c_int32), ("ldv", c_int32), ("ldo", c_int32),
+                ("lddq", c_int32), ("lddk", c_int32), ("lddv", c_int32),
+                ("scale", c_float), ("drop_p", c_float), ("drop_seed", c_uint32), ("seed_dev", c_void_p)]
 
 
-class MaskPosencDesc(Structure):
-    _fields_ = [
-        ("mask", c_void_p), ("kpm_out", c_void_p), ("pos_out", c_void_p), ("add_vec", c_void_p),
-        ("B", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32), ("C", c_int32),
-        ("kpm_stride", c_int32), ("kpm_off", c_int32), ("pos_rows_per_img", c_int32), ("pos_row_off", c_int32),
-    ]
+class MaskPosencDesc(_Abi, c="rt_mask_posenc_desc"):
+    _fields_ = [("mask", c_void_p), ("kpm_out", c_void_p), ("pos_out", c_void_p), ("add_vec", c_void_p),
+                ("B", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32), ("C", c_int32),
+                ("kpm_stride", c_int32), ("kpm_off", c_int32), ("pos_rows_per_img", c_int32), ("pos_row_off", c_int32)]
 
 
-class BottleneckDesc(Structure):
-    _fields_ = [
-        ("x", c_void_p), ("w1", c_void_p), ("w2", c_void_p), ("w3", c_void_p), ("wd", c_void_p),
-        ("b1", c_void_p), ("b2", c_void_p), ("b3", c_void_p), ("bd", c_void_p), ("out", c_void_p),
-        ("B", c_int32), ("H", c_int32), ("W", c_int32), ("cin", c_int32), ("planes", c_int32), ("form", c_int32),
-    ]
+class BottleneckDesc(_Abi, c="rt_bottleneck_desc"):
+    _fields_ = [("x", c_void_p), ("w1", c_void_p), ("w2", c_void_p), ("w3", c_void_p), ("wd", c_void_p),
+                ("b1", c_void_p), ("b2", c_void_p), ("b3", c_void_p), ("bd", c_void_p), ("out", c_void_p),
+                ("B", c_int32), ("H", c_int32), ("W", c_int32), ("cin", c_int32), ("planes", c_int32), ("form", c_int32)]
 
 
-class RowsAddDesc(Structure):
-    _fields_ = [
-        ("a_f32", c_void_p), ("a_bf16", c_void_p), ("b_f32", c_void_p), ("out_f32", c_void_p), ("out_bf16", c_void_p),
-        ("rows", c_int32), ("D", c_int32), ("alpha", c_float), ("accumulate", c_int32),
-        ("a_grp_rows", c_int32), ("a_grp_stride", c_int32), ("a_grp_off", c_int32),
-        ("b_grp_rows", c_int32), ("b_grp_stride", c_int32), ("b_grp_off", c_int32),
-        ("o_grp_rows", c_int32), ("o_grp_stride", c_int32), ("o_grp_off", c_int32),
-    ]
+class RowsAddDesc(_Abi, c="rt_rows_add_desc"):
+    _fields_ = [("a_f32", c_void_p), ("a_bf16", c_void_p), ("b_f32", c_void_p), ("out_f32", c_void_p), ("out_bf16", c_void_p),
+                ("rows", c_int32), ("D", c_int32), ("alpha", c_float), ("accumulate", c_int32),
+                ("a_grp_rows", c_int32), ("a_grp_stride", c_int32), ("a_grp_off", c_int32),
+                ("b_grp_rows", c_int32), ("b_grp_stride", c_int32), ("b_grp_off", c_int32),
+                ("o_grp_rows", c_int32), ("o_grp_stride", c_int32), ("o_grp_off", c_int32)]
 
 
-class BoxLossDesc(Structure):
-    _fields_ = [
-        ("logits", c_void_p), ("valid", c_void_p), ("targets", c_void_p), ("tgt_off", c_void_p),
-        ("num_boxes", c_void_p), ("losses", c_void_p), ("total", c_void_p), ("dlogits", c_void_p),
-        ("NL", c_int32), ("B", c_int32), ("P", c_int32), ("K", c_int32), ("w_bbox", c_float), ("w_giou", c_float),
-        ("weights", c_void_p),
-    ]
+class BoxLossDesc(_Abi, c="rt_box_loss_desc"):
+    _fields_ = [("logits", c_void_p), ("valid", c_void_p), ("targets", c_void_p), ("tgt_off", c_void_p),
+                ("num_boxes", c_void_p), ("losses", c_void_p), ("total", c_void_p), ("dlogits", c_void_p),
+                ("NL", c_int32), ("B", c_int32), ("P", c_int32), ("K", c_int32), ("w_bbox", c_float), ("w_giou", c_float),
+                ("weights", c_void_p)]
 
 
-class MaskPostDesc(Structure):
-    _fields_ = [
-        ("pred", c_void_p), ("sizes", c_void_p), ("orig", c_void_p), ("origin_off", c_void_p),
-        ("masks", c_void_p), ("masks_origin", c_void_p),
-        ("B", c_int32), ("Q", c_int32), ("h", c_int32), ("w", c_int32), ("max_h", c_int32), ("max_w", c_int32),
-        ("max_origin", c_int64), ("threshold", c_float),
-    ]
+class MaskPostDesc(_Abi, c="rt_mask_post_desc"):
+    _fields_ = [("pred", c_void_p), ("sizes", c_void_p), ("orig", c_void_p), ("origin_off", c_void_p),
+                ("masks", c_void_p), ("masks_origin", c_void_p),
+                ("B", c_int32), ("Q", c_int32), ("h", c_int32), ("w", c_int32), ("max_h", c_int32), ("max_w", c_int32),
+                ("max_origin", c_int64), ("threshold", c_float)]
 
 
-class BoxPostDesc(Structure):
-    _fields_ = [
-        ("boxes", c_void_p), ("valid", c_void_p), ("sizes", c_void_p), ("out", c_void_p), ("counts", c_void_p),
-        ("B", c_int32), ("P", c_int32), ("K", c_int32),
-    ]
+class BoxPostDesc(_Abi, c="rt_box_post_desc"):
+    _fields_ = [("boxes", c_void_p), ("valid", c_void_p), ("sizes", c_void_p), ("out", c_void_p), ("counts", c_void_p),
+                ("B", c_int32), ("P", c_int32), ("K", c_int32)]
 
 
-class CemDesc(Structure):
+class CemDesc(_Abi, c="rt_cem_desc"):
     _fields_ = [("hs", c_void_p), ("w3", c_void_p), ("b3", c_void_p), ("res", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
                 ("u", c_void_p), ("energy", c_void_p), ("stats", c_void_p), ("loss", c_void_p), ("g", c_void_p),
                 ("dres", c_void_p), ("dhs", c_void_p), ("dw3", c_void_p), ("db3", c_void_p), ("dw2", c_void_p),
                 ("B", c_int32), ("HW", c_int32), ("ld", c_int32), ("lddr", c_int32), ("E", c_int32), ("reserved", c_int32)]
 
 
-class AdamWDesc(Structure):
-    _fields_ = [
-        ("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64),
-        ("gnorm_sq", c_void_p), ("gnorm_out", c_void_p),
-        ("grad_scale", c_float), ("max_norm", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float),
-        ("step", c_int32), ("n_ranges", c_int32),
-        ("range_begin", c_int64 * 8), ("range_end", c_int64 * 8), ("range_lr", c_float * 8), ("range_wd", c_float * 8),
-        ("step_dev", c_void_p), ("active", c_void_p), ("lr_dev", c_void_p), ("span_begin", c_int64), ("span_end", c_int64),
-        ("g16", c_void_p),
-    ]
+class AdamWDesc(_Abi, c="rt_adamw_desc"):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64),
+                ("gnorm_sq", c_void_p), ("gnorm_out", c_void_p),
+                ("grad_scale", c_float), ("max_norm", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float),
+                ("step", c_int32), ("n_ranges", c_int32),
+                ("range_begin", c_int64 * 8), ("range_end", c_int64 * 8), ("range_lr", c_float * 8), ("range_wd", c_float * 8),
+                ("step_dev", c_void_p), ("active", c_void_p), ("lr_dev", c_void_p), ("span_begin", c_int64), ("span_end", c_int64),
+                ("g16", c_void_p)]
 
 
-# name -> (restype, argtypes); every symbol include/reftr_hip.h declares must be listed here
-# (tests/test_abi.py cross-checks this table against the header).
-class SmallWgradJob(Structure):
+class FinishDesc(_Abi, c="rt_finish_desc"):
+    _fields_ = [("step", c_void_p), ("active", c_void_p), ("cond", c_void_p), ("loss", c_void_p),
+                ("sq", c_void_p), ("norm_scale", c_float), ("grad_norm", c_void_p),
+                ("src", c_void_p * STATS_MAX), ("n_src", c_int), ("cond_in_stats", c_int), ("stats", c_void_p)]
+
+
+class SmallWgradJob(_Abi, c="rt_small_wgrad_job"):
     _fields_ = [("dy", c_void_p), ("x", c_void_p), ("dw", c_void_p), ("dbias", c_void_p),
                 ("M", c_int32), ("N", c_int32), ("K", c_int32), ("overwrite", c_int32), ("sqacc", c_void_p), ("g16", c_void_p)]
 
 
-class GnNhwcDesc(Structure):
+class GnNhwcDesc(_Abi, c="rt_gn_nhwc_desc"):
     _fields_ = [("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("stats", c_void_p), ("y_bf16", c_void_p),
                 ("B", c_int32), ("HW", c_int32), ("C", c_int32), ("G", c_int32), ("ldx", c_int32), ("ldy", c_int32),
                 ("act", c_int32), ("eps", c_float), ("partials", c_void_p), ("partial_blocks", c_int32)]
 
 
-class GnNhwcBwdDesc(Structure):
+class GnNhwcBwdDesc(_Abi, c="rt_gn_nhwc_bwd_desc"):
     _fields_ = [("dy", c_void_p), ("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("stats", c_void_p),
                 ("bstats", c_void_p), ("dx_bf16", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p),
                 ("B", c_int32), ("HW", c_int32), ("C", c_int32), ("G", c_int32), ("ldx", c_int32), ("lddy", c_int32),
                 ("lddx", c_int32), ("act", c_int32), ("eps", c_float)]
 
 
-class UpsampleAddDesc(Structure):
+class UpsampleAddDesc(_Abi, c="rt_upsample_add_desc"):
     _fields_ = [("fpn", c_void_p), ("a_bf16", c_void_p), ("out_bf16", c_void_p),
                 ("B", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32), ("C", c_int32),
                 ("ldf", c_int32), ("lda", c_int32), ("ldo", c_int32)]
 
 
-class UpsampleAddBwdDesc(Structure):
+class UpsampleAddBwdDesc(_Abi, c="rt_upsample_add_bwd_desc"):
     _fields_ = [("dy", c_void_p), ("da", c_void_p), ("dy_bf16", c_void_p),
                 ("B", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32), ("C", c_int32),
                 ("lddy", c_int32), ("ldda", c_int32), ("lddyb", c_int32)]
 
 
-class AttnMapDesc(Structure):
+class AttnMapDesc(_Abi, c="rt_attn_map_desc"):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("mask", c_void_p), ("P", c_void_p), ("concat_bf16", c_void_p),
                 ("B", c_int32), ("HW", c_int32), ("E", c_int32), ("nh", c_int32), ("ldk", c_int32),
                 ("k_rows_per_img", c_int32), ("k_row_off", c_int32), ("ld_concat", c_int32), ("concat_col", c_int32),
                 ("norm", c_float)]
 
 
-class AttnMapBwdDesc(Structure):
+class AttnMapBwdDesc(_Abi, c="rt_attn_map_bwd_desc"):
     _fields_ = [("q", c_void_p), ("k", c_void_p), ("P", c_void_p), ("dconcat", c_void_p), ("dq", c_void_p), ("dk", c_void_p),
                 ("B", c_int32), ("HW", c_int32), ("E", c_int32), ("nh", c_int32), ("ldk", c_int32),
                 ("k_rows_per_img", c_int32), ("k_row_off", c_int32), ("ld_dconcat", c_int32), ("concat_col", c_int32),
                 ("norm", c_float)]
 
 
-class SegConcatDesc(Structure):
+class SegConcatDesc(_Abi, c="rt_seg_concat_desc"):
     _fields_ = [("src", c_void_p), ("mem", c_void_p), ("out_bf16", c_void_p),
                 ("B", c_int32), ("HW", c_int32), ("E", c_int32), ("nh", c_int32), ("ldo", c_int32),
                 ("mem_rows_per_img", c_int32), ("mem_row_off", c_int32), ("src_rows_per_img", c_int32), ("src_row_off", c_int32)]
 
 
-class MaskLossDesc(Structure):
+class MaskLossDesc(_Abi, c="rt_mask_loss_desc"):
     _fields_ = [("pred", c_void_p), ("target", c_void_p), ("sums", c_void_p), ("losses", c_void_p),
                 ("dpred", c_void_p), ("g_focal", c_void_p), ("g_dice", c_void_p),
                 ("B", c_int32), ("h", c_int32), ("w", c_int32), ("Ht", c_int32), ("Wt", c_int32), ("ldp", c_int32),
                 ("lddp", c_int32), ("inv_norm", c_float), ("gbuf", c_void_p)]
 
 
-class EvalMetricsArgs(Structure):
+class EvalMetricsArgs(_Abi, c="rt_eval_metrics_args"):
     _fields_ = [("pred_boxes", c_void_p), ("valid", c_void_p), ("table", c_void_p), ("masks", c_void_p), ("sizes", c_void_p),
                 ("partials", c_void_p), ("iou_det", c_void_p), ("iou_seg", c_void_p), ("iu", c_void_p), ("acc", c_void_p),
                 ("B", c_int32), ("P", c_int32), ("K", c_int32), ("Q", c_int32), ("max_h", c_int32), ("max_w", c_int32),
                 ("reset", c_int32)]
 
 
-class EvalCanvasArgs(Structure):
+class EvalCanvasArgs(_Abi, c="rt_eval_canvas_args"):
     _fields_ = [("pred_boxes", c_void_p), ("valid", c_void_p), ("tgt_boxes", c_void_p), ("tgt_off", c_void_p), ("facts", c_void_p),
                 ("image_ids", c_void_p), ("pred_masks", c_void_p), ("tgt_masks", c_void_p), ("partials", c_void_p),
                 ("iou_det", c_void_p), ("iou_seg", c_void_p), ("iu", c_void_p), ("acc", c_void_p), ("ring_boxes", c_void_p),
@@ -255,10 +252,7 @@ class EvalCanvasArgs(Structure):
                 ("Wc", c_int32), ("tgt_rows", c_int32), ("slots", c_int32), ("threshold", c_float)]
 
 
-DEC_MAX_LAYERS = 8
-
-
-class DecoderLayerFwd(Structure):
+class DecoderLayerFwd(_Abi, c="rt_decoder_layer_fwd"):
     _PTRS = ("Wv", "Wo", "Wq", "Wo2", "W1", "W2", "bv", "bo", "bq", "bo2", "b1", "b2", "g1", "be1", "g2", "be2", "g3", "be3",
              "k2", "v2", "o", "t1q16", "q2", "o2", "t2_16", "hdn", "t3_16", "u", "u2", "u3",
              "mean1", "rstd1", "mean2", "rstd2", "mean3", "rstd3", "lse2", "t3_f32")
@@ -266,7 +260,7 @@ class DecoderLayerFwd(Structure):
     _fields_ = [(n, c_void_p) for n in _PTRS] + [(n, c_uint32) for n in _SEEDS]
 
 
-class DecoderLayerBwd(Structure):
+class DecoderLayerBwd(_Abi, c="rt_decoder_layer_bwd"):
     _PTRS = ("WT2", "WT1", "WTo2", "WTq", "WTo", "WTv", "g1", "g2", "g3", "u", "u2", "u3",
              "mean1", "rstd1", "mean2", "rstd2", "mean3", "rstd3", "hdn", "q2", "k2", "v2", "o2", "lse2", "dnorm",
              "du3b", "dhdn", "du2b", "dq2", "dub", "dv", "dk2", "dv2", "dk2p", "dv2p", "part1", "part2", "part3")
@@ -274,14 +268,14 @@ class DecoderLayerBwd(Structure):
     _fields_ = [(n, c_void_p) for n in _PTRS] + [(n, c_uint32) for n in _SEEDS]
 
 
-class DecoderBwdDesc(Structure):
+class DecoderBwdDesc(_Abi, c="rt_decoder_bwd_desc"):
     _fields_ = [("layer", DecoderLayerBwd * DEC_MAX_LAYERS),
                 ("dta", c_void_p), ("dqpos", c_void_p), ("kpm", c_void_p), ("handoff", c_void_p), ("seed_dev", c_void_p),
                 ("n_layers", c_int32), ("M", c_int32), ("H", c_int32), ("S", c_int32), ("F", c_int32), ("ldkv", c_int32),
                 ("drop_p", c_float), ("scale", c_float), ("gate_scale", c_float), ("ldkvp", c_int32)]
 
 
-class DecoderFwdDesc(Structure):
+class DecoderFwdDesc(_Abi, c="rt_decoder_fwd_desc"):
     _fields_ = [("layer", DecoderLayerFwd * DEC_MAX_LAYERS),
                 ("t32", c_void_p), ("t16", c_void_p), ("qpos", c_void_p), ("kpm", c_void_p), ("handoff", c_void_p),
                 ("seed_dev", c_void_p),
@@ -289,7 +283,7 @@ class DecoderFwdDesc(Structure):
                 ("drop_p", c_float), ("eps", c_float), ("scale", c_float)]
 
 
-class QencFwdDesc(Structure):
+class QencFwdDesc(_Abi, c="rt_qenc_fwd_desc"):
     _PTRS = ("mem16", "mem32", "ctx", "W1", "W2", "W3", "Wc", "Wf0", "Wf4", "b1", "b2", "b3", "bc", "bf0", "bf4",
              "gc", "betc", "g1", "bet1", "g5", "bet5", "qembed", "seed_dev",
              "cls16", "lang16", "kq", "qs", "vs", "qw", "c16", "co", "cmean", "crstd", "cat16",
@@ -299,7 +293,7 @@ class QencFwdDesc(Structure):
                                                  ("reserved", c_int32)]
 
 
-class HeadLossDesc(Structure):
+class HeadLossDesc(_Abi, c="rt_head_loss_desc"):
     _PTRS = ("t3", "gn", "betn", "W0", "W1", "W2", "W0T", "W1T", "b0", "b1", "b2", "w2_f32",
              "valid", "targets", "tgt_off", "num_boxes", "weights",
              "hs16", "y1", "y2", "hmean", "hrstd", "logits", "losses", "dlogits", "dl16", "dy2", "dy1", "dhs", "dnorm", "db2_part", "part_n", "total", "ticket")
@@ -307,7 +301,7 @@ class HeadLossDesc(Structure):
                                                  ("eps", c_float), ("invert_valid", c_int32), ("reserved", c_int32)]
 
 
-class QencBwdDesc(Structure):
+class QencBwdDesc(_Abi, c="rt_qenc_bwd_desc"):
     _PTRS = ("ga", "gb", "dqpos", "t2", "m2", "r2", "g5", "bet5", "t1", "m1", "r1", "g1", "bet1", "co", "cmean", "crstd", "gc", "betc",
              "kq", "qs", "vs", "qw", "Wf4T", "Wf0T", "WcT", "W1T", "W2T", "W3T", "seed_dev",
              "dt2b", "dt1b", "dcob", "dk16", "dqs16", "dvs16", "da", "dcat", "dc", "dmem", "dqembed", "part5", "part1", "partc")
@@ -315,6 +309,8 @@ class QencBwdDesc(Structure):
                                                  ("drop_p", c_float), ("drop_seed", c_uint32), ("reserved", c_int32)]
 
 
+# name -> (restype, argtypes); every symbol include/reftr_hip.h declares must be listed here (tests/test_abi.py checks the names, the
+# number of parameters and the kind of each one against the header).
 _SIGNATURES = {
     "rt_abi_version": (c_int, []),
     "rt_device_arch": (c_int, [c_int, c_char_p, c_int]),
@@ -353,7 +349,7 @@ _SIGNATURES = {
     "rt_mask_postprocess": (c_int, [POINTER(MaskPostDesc), c_void_p]),
     "rt_box_postprocess": (c_int, [POINTER(BoxPostDesc), c_void_p]),
     "rt_eval_metrics": (c_int, [POINTER(EvalMetricsArgs), c_void_p]),
-    "rt_eval_facts": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(ctypes.c_int32), c_int, c_void_p,
+    "rt_eval_facts": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_void_p,
                               c_void_p, c_void_p]),
     "rt_eval_canvas": (c_int, [POINTER(EvalCanvasArgs), c_void_p]),
     "rt_small_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -368,12 +364,12 @@ _SIGNATURES = {
     "rt_zero_chunks": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "rt_counter_add": (c_int, [c_void_p, c_int32, c_void_p]),
     "rt_ln_param_grad_grouped": (c_int, [POINTER(LnPgJob), c_int, c_void_p]),
-    "rt_conv_wgrad_grouped": (c_int, [POINTER(ConvWgradDesc), c_int, c_void_p, ctypes.c_int64, c_void_p]),
+    "rt_conv_wgrad_grouped": (c_int, [POINTER(ConvWgradDesc), c_int, c_void_p, c_int64, c_void_p]),
     "rt_small_wgrad_grouped": (c_int, [POINTER(SmallWgradJob), c_int, c_void_p]),
     "rt_resample_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "rt_img_collate_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), c_void_p]),
     "rt_batch_stage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, POINTER(c_void_p),
-                               POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(ctypes.c_int32),
+                               POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int32),
                                c_void_p, c_void_p]),
     "rt_gn_nhwc_fwd": (c_int, [POINTER(GnNhwcDesc), c_void_p]),
     "rt_gn_nhwc_bwd": (c_int, [POINTER(GnNhwcBwdDesc), c_void_p]),
@@ -385,7 +381,7 @@ _SIGNATURES = {
     "rt_mask_loss": (c_int, [POINTER(MaskLossDesc), c_void_p]),
     "rt_comm_unique_id": (c_int, [c_void_p]),
     "rt_comm_init": (c_int, [c_void_p, c_int, c_int, POINTER(c_void_p)]),
-    "rt_comm_allreduce": (c_int, [c_void_p, POINTER(c_void_p), POINTER(ctypes.c_int64), c_int, c_int, c_void_p]),
+    "rt_comm_allreduce": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_int64), c_int, c_int, c_void_p]),
     "rt_comm_destroy": (c_int, [c_void_p]),
     "rt_decoder_fwd": (c_int, [POINTER(DecoderFwdDesc), c_void_p]),
     "rt_decoder_bwd": (c_int, [POINTER(DecoderBwdDesc), c_void_p]),
@@ -457,18 +453,58 @@ def exported_symbols():
     return sorted(_SIGNATURES)
 
 
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed with code {rc} "
-                           f"({'RT_ERR' if rc < 0 else 'hipError'})")
-
-
 def _p(t):
     return None if t is None else t.data_ptr()
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+# what a field or an argument takes as it is: most of them, and every launch looks at each of its own
+_PLAIN = frozenset({int, float, bool, type(None), POINTER(c_int32)})
+
+
+def _val(v):
+    """What a field or an argument holds: a tensor gives its address, a Python sequence its converted elements."""
+    if isinstance(v, torch.Tensor):
+        return v.data_ptr()
+    return tuple(_val(e) for e in v) if isinstance(v, (list, tuple)) else v
+
+
+def _fill(d, fields, Tensor=torch.Tensor, plain=_PLAIN):
+    for k, v in fields.items():          # (per field and per launch: locals, and no call for a plain value)
+        if v.__class__ is Tensor:
+            fields[k] = v.data_ptr()
+        elif v.__class__ not in plain:
+            fields[k] = _val(v)
+    d.__init__(**fields)          # one ctypes call sets them all; a name the struct does not have it keeps as a plain attribute
+    if d.__dict__:
+        raise TypeError(f"{type(d).__name__} ({d.C_NAME}): no field {sorted(d.__dict__)}")
+    return d
+
+
+def _set(d, **fields):
+    """Fills fields of the bound struct `d` BY NAME: a tensor gives its address, None gives NULL, a sequence given to an array field
+    fills its leading elements; fields not named keep what they hold.  A name the struct does not have is an error."""
+    return _fill(d, fields)
+
+
+def _desc(cls, **fields):
+    """A new `cls` filled by `_set`: fields not named are zero / NULL."""
+    return _fill(cls(), fields)
+
+
+def _call(name, *args, stream=True, Tensor=torch.Tensor, plain=_PLAIN, byref=ctypes.byref):
+    """The library's entry point `name`: bound structs go by reference, tensors by address, and the current stream goes last (entry
+    points without one: stream=False).  A non-zero return code is an error."""
+    args = [a if a.__class__ in plain else a.data_ptr() if a.__class__ is Tensor
+            else byref(a) if isinstance(a, Structure) else _val(a) for a in args]
+    if stream:
+        args.append(_stream())
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed with code {rc} ({'RT_ERR' if rc < 0 else 'hipError'})")
 
 
 _TIMER = None
@@ -483,7 +519,6 @@ def set_seed_dev(t):
 
 def _seedp(drop_p):
     return _p(_SEED_DEV) if (drop_p > 0 and _SEED_DEV is not None) else None
-
 
 
 def set_launch_timer(records):
@@ -539,25 +574,16 @@ def _req(t, dtype, name):
 _GEOM = ("B", "SH", "SW", "SC", "DH", "DW", "N", "KH", "KW", "stride", "pad")
 
 
-def _geom_desc(cls, geom, fields):
-    """A `cls` descriptor: the geometry tuple and every other field BY NAME (a tensor gives its address; fields not named stay
-    zero / NULL).  A name the struct does not have is an error."""
-    d = cls(**dict(zip(_GEOM, geom, strict=True)))
-    known = {name for name, _ in cls._fields_}
-    for k, v in fields.items():
-        if k not in known:
-            raise TypeError(f"{cls.__name__}: no field {k!r}")
-        setattr(d, k, _p(v) if torch.is_tensor(v) else v)
-    return d
-
-
 def _gemm_desc(src, wgt, geom, **fields):
-    return _geom_desc(ConvGemmDesc, geom, dict(fields, src=src, wgt=wgt))
+    """A product's descriptor: the geometry tuple and every other field by name (`_set`)."""
+    fields.update(src=src, wgt=wgt)
+    return _fill(ConvGemmDesc(**dict(zip(_GEOM, geom, strict=True))), fields)
 
 
 def _wgrad_desc(dy, x, dw, geom, **fields):
     """... of a weight gradient into `dw`, with the norm accumulator and the bf16 twin `dw` is registered for."""
-    return _geom_desc(ConvWgradDesc, geom, dict(fields, dy=dy, x=x, dw=dw, sqacc=_sqacc(dw), g16=_g16(dw)))
+    fields.update(dy=dy, x=x, dw=dw, sqacc=_sqacc(dw), g16=_g16(dw))
+    return _fill(ConvWgradDesc(**dict(zip(_GEOM, geom, strict=True))), fields)
 
 
 def _out_buffer(o, dtype, name, M, N, dev):
@@ -600,7 +626,7 @@ def conv_gemm(src, wgt, *, geom, bias=None, res_f32=None, res_bf16=None, gate=No
     op = None
     if out_preact:
         op = torch.empty((M, N), dtype=torch.bfloat16, device=src.device)
-        d.out_preact = _p(op)
+        _set(d, out_preact=op)
     if transposed:     # algorithmic FLOPs of backward-data = those of the forward conv it differentiates
         flops = 2.0 * B * SH * SW * SC * N * KH * KW
     else:
@@ -614,8 +640,7 @@ def conv_gemm(src, wgt, *, geom, bias=None, res_f32=None, res_bf16=None, gate=No
     if group is not None:      # queued: GemmGroup.run() launches every queued product at once
         group.add(d, flops, ("T" if transposed else "F",) + tuple(geom), (src, wgt, ob, of, op, bias, res_f32, res_bf16, gate, preact, dtanh), epi)
     else:
-        _timed("conv_gemm", flops, lambda: _check(lib().rt_conv_gemm(ctypes.byref(d), _stream()), "rt_conv_gemm"),
-               tag=("T" if transposed else "F",) + tuple(geom), epi_bytes=epi)
+        _timed("conv_gemm", flops, lambda: _call("rt_conv_gemm", d), tag=("T" if transposed else "F",) + tuple(geom), epi_bytes=epi)
     if out_preact:
         return ob, of, op
     return ob, of
@@ -639,8 +664,7 @@ class GemmGroup:
             chunk = self.descs[i:i + 12]
             arr = (ConvGemmDesc * len(chunk))(*chunk)
             share = len(chunk) / n
-            _timed("conv_gemm", self.flops * share,
-                   lambda arr=arr, m=len(chunk): _check(lib().rt_conv_gemm_grouped(arr, m, _stream()), "rt_conv_gemm_grouped"),
+            _timed("conv_gemm", self.flops * share, lambda arr=arr, m=len(chunk): _call("rt_conv_gemm_grouped", arr, m),
                    nbytes=self.nbytes * share, epi_bytes=self.epi * share)
         self.descs, self.keep, self.flops, self.nbytes, self.epi = [], [], 0.0, 0.0, 0.0
 
@@ -669,7 +693,6 @@ def _wgrad_workspace(dev):
 # Gradient-norm accumulators: {data_ptr of a registered weight-gradient matrix: its model's slot buffer} (ParamStore registers its
 # overwritable matrices here).  Every weight-gradient launch into such a matrix hands the slots to the library (`sqacc`), which adds
 # |dw after|^2 - |dw before|^2 -- the clip norm then needs no pass over the gradient buffer (rt_sqnorm_finish).
-SQ_SLOTS, SQ_STRIDE = 256, 32
 _SQACC_MAP = {}
 
 
@@ -703,14 +726,14 @@ def round_chunks(base, twin, table, n):
     """twin[i] = bf16(base[i]) over n chunks {offset, count} of a static device table (rt_round_chunks)."""
     _req(base, torch.float32, "base"); _req(twin, torch.bfloat16, "twin"); _req(table, torch.int64, "table")
     if n > 0:
-        _check(lib().rt_round_chunks(_p(base), _p(twin), _p(table), int(n), _stream()), "rt_round_chunks")
+        _call("rt_round_chunks", base, twin, table, int(n))
 
 
 def sqnorm_finish(flat_g, table, nchunks, slots, out, extra=None):
     """out[0] = sum of the accumulator slots + |the chunks of flat_g listed in `table`|^2 (+ extra[0])."""
     _req(flat_g, torch.float32, "flat_g"); _req(slots, torch.float32, "slots"); _req(out, torch.float32, "out")
     assert slots.numel() == SQ_SLOTS * SQ_STRIDE
-    _check(lib().rt_sqnorm_finish(_p(flat_g), _p(table), int(nchunks), _p(slots), _p(extra), _p(out), _stream()), "rt_sqnorm_finish")
+    _call("rt_sqnorm_finish", flat_g, table, int(nchunks), slots, extra, out)
 
 
 def conv_wgrad(dy, x, dw, *, geom, scale=None, msplit=0, dbias=None, variant=0, workspace=True, overwrite=False, dil=1):
@@ -723,8 +746,7 @@ def conv_wgrad(dy, x, dw, *, geom, scale=None, msplit=0, dbias=None, variant=0, 
     ws = _wgrad_workspace(dy.device) if workspace else None
     d = _wgrad_desc(dy, x, dw, geom, scale=scale, msplit=msplit, dbias=dbias, variant=variant, workspace=ws,
                     workspace_bytes=WGRAD_WS_BYTES if ws is not None else 0, overwrite=int(bool(overwrite)), dil=int(dil))
-    _timed("conv_wgrad", 2.0 * B * DH * DW * N * KH * KW * SC,
-           lambda: _check(lib().rt_conv_wgrad(ctypes.byref(d), _stream()), "rt_conv_wgrad"), tag=("W",) + tuple(geom))
+    _timed("conv_wgrad", 2.0 * B * DH * DW * N * KH * KW * SC, lambda: _call("rt_conv_wgrad", d), tag=("W",) + tuple(geom))
     return dw
 
 
@@ -747,8 +769,7 @@ def gconv(src, wgt, *, geom, groups, bias=None, gate=None, gate_scale=1.0, act=A
                    gate_scale=gate_scale, dil=int(dil), **unsupported)      # (forwarded so that the library refuses them: no silent drop)
     spatial = B * (SH * SW if transposed else DH * DW)
     flops = 2.0 * spatial * SC * KH * KW * cg
-    _timed("gconv", flops, lambda: _check(lib().rt_gconv(ctypes.byref(d), int(groups), _stream()), "rt_gconv"),
-           nbytes=2.0 * (B * SH * SW * SC + M * N) + 2.0 * wgt.numel())
+    _timed("gconv", flops, lambda: _call("rt_gconv", d, int(groups)), nbytes=2.0 * (B * SH * SW * SC + M * N) + 2.0 * wgt.numel())
     return ob, of
 
 
@@ -763,8 +784,7 @@ def gconv_wgrad(dy, x, dw, *, geom, groups, scale=None, msplit=0, overwrite=Fals
     ws = _wgrad_workspace(dy.device)
     d = _wgrad_desc(dy, x, dw, geom, scale=scale, msplit=msplit, dbias=dbias, variant=variant, workspace=ws,
                     workspace_bytes=WGRAD_WS_BYTES, overwrite=int(bool(overwrite)), dil=int(dil))
-    _timed("gconv_wgrad", 2.0 * B * DH * DW * N * KH * KW * cg,
-           lambda: _check(lib().rt_gconv_wgrad(ctypes.byref(d), int(groups), _stream()), "rt_gconv_wgrad"),
+    _timed("gconv_wgrad", 2.0 * B * DH * DW * N * KH * KW * cg, lambda: _call("rt_gconv_wgrad", d, int(groups)),
            nbytes=2.0 * (B * DH * DW * N + B * SH * SW * SC) + 4.0 * dw.numel())
     return dw
 
@@ -798,9 +818,11 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5, *, act=ACT_NONE, drop_p=0.0, drop_se
         ypos_bf16 = _new((M, D), torch.bfloat16, x)
     mean = _new((M,), torch.float32, x) if save_stats else None
     rstd = _new((M,), torch.float32, x) if save_stats else None
-    d = LayerNormDesc(_p(x), _p(gamma), _p(beta), _p(y_f32), _p(y_bf16), _p(pos), _p(ypos_bf16), _p(mean), _p(rstd),
-                      M, D, eps, act, drop_p, drop_seed & 0xFFFFFFFF, *rowmap, _seedp(drop_p))
-    _check(lib().rt_layernorm_fwd(ctypes.byref(d), _stream()), "rt_layernorm_fwd")
+    grp_rows, grp_stride, grp_off = rowmap
+    _call("rt_layernorm_fwd", _desc(
+        LayerNormDesc, x=x, gamma=gamma, beta=beta, y_f32=y_f32, y_bf16=y_bf16, pos=pos, ypos_bf16=ypos_bf16, mean=mean, rstd=rstd,
+        M=M, D=D, eps=eps, act=act, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF, grp_rows=grp_rows, grp_stride=grp_stride,
+        grp_off=grp_off, seed_dev=_seedp(drop_p)))
     return y_f32, y_bf16, ypos_bf16, mean, rstd
 
 
@@ -814,7 +836,7 @@ class LnGradBatch:
         if not self.jobs:
             return
         arr = (LnPgJob * len(self.jobs))(*self.jobs)
-        _check(lib().rt_ln_param_grad_grouped(arr, len(self.jobs), _stream()), "rt_ln_param_grad_grouped")
+        _call("rt_ln_param_grad_grouped", arr, len(self.jobs))
         self.jobs, self.keep = [], []
 
 
@@ -829,12 +851,14 @@ def layernorm_bwd(dy, x, gamma, beta, mean, rstd, dgamma, dbeta, *, dy2=None, ac
     part, nb = None, c_int32(0)
     if pg_batch is not None and (dgamma is not None or dbeta is not None):
         part = _new((min((M + 3) // 4, 1024), 2, D), torch.float32, x)
-    d = LayerNormBwdDesc(_p(dy), _p(dy2), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx_f32), _p(dx_bf16),
-                         _p(dgamma), _p(dbeta), M, D, act, drop_p, drop_seed & 0xFFFFFFFF, drop2_p,
-                         drop2_seed & 0xFFFFFFFF, *rowmap, _seedp(max(drop_p, drop2_p)), _p(part), ctypes.pointer(nb))
-    _check(lib().rt_layernorm_bwd(ctypes.byref(d), _stream()), "rt_layernorm_bwd")
+    grp_rows, grp_stride, grp_off = rowmap
+    _call("rt_layernorm_bwd", _desc(
+        LayerNormBwdDesc, dy=dy, dy2=dy2, x=x, gamma=gamma, beta=beta, mean=mean, rstd=rstd, dx_f32=dx_f32, dx_bf16=dx_bf16,
+        dgamma=dgamma, dbeta=dbeta, M=M, D=D, act=act, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF, drop2_p=drop2_p,
+        drop2_seed=drop2_seed & 0xFFFFFFFF, grp_rows=grp_rows, grp_stride=grp_stride, grp_off=grp_off,
+        seed_dev=_seedp(max(drop_p, drop2_p)), partials=part, n_blocks_out=ctypes.pointer(nb)))
     if part is not None:
-        pg_batch.jobs.append(LnPgJob(_p(part), _p(dgamma), _p(dbeta), nb.value, D))
+        pg_batch.jobs.append(_desc(LnPgJob, partials=part, dgamma=dgamma, dbeta=dbeta, n_blocks=nb.value, D=D))
         pg_batch.keep.append(part)
     return dx_f32, dx_bf16
 
@@ -848,9 +872,9 @@ def groupnorm_fwd(x, gamma, beta, G, eps, *, y_f32=None, y_bf16=None, pos=None, 
     stats = _new((B, G, 2), torch.float32, x)
     chunks = min(64, (HW + 7) // 8)
     partials = _new((B, chunks, G, 2), torch.float32, x)
-    d = GroupNormDesc(_p(x), _p(gamma), _p(beta), _p(stats), _p(y_f32), _p(y_bf16), _p(pos), _p(ypos_bf16),
-                      B, HW, C, G, eps, rows_per_img, row_off, _p(partials), chunks)
-    _check(lib().rt_groupnorm_fwd(ctypes.byref(d), _stream()), "rt_groupnorm_fwd")
+    _call("rt_groupnorm_fwd", _desc(
+        GroupNormDesc, x=x, gamma=gamma, beta=beta, stats=stats, y_f32=y_f32, y_bf16=y_bf16, pos=pos, ypos_bf16=ypos_bf16,
+        B=B, HW=HW, C=C, G=G, eps=eps, out_rows_per_img=rows_per_img, out_row_off=row_off, partials=partials, chunks=chunks))
     return stats
 
 
@@ -861,9 +885,9 @@ def groupnorm_bwd(dy, x, gamma, stats, dgamma, dbeta, G, eps, *, dy2=None, rows_
     bstats = _new((B, G, 2), torch.float32, x)
     dx_f32 = _new((B, HW, C), torch.float32, x) if want_f32 else None
     dx_bf16 = _new((B, HW, C), torch.bfloat16, x) if want_bf16 else None
-    d = GroupNormBwdDesc(_p(dy), _p(dy2), _p(x), _p(gamma), _p(stats), _p(bstats), _p(dx_f32), _p(dx_bf16),
-                         _p(dgamma), _p(dbeta), B, HW, C, G, eps, rows_per_img, row_off)
-    _check(lib().rt_groupnorm_bwd(ctypes.byref(d), _stream()), "rt_groupnorm_bwd")
+    _call("rt_groupnorm_bwd", _desc(
+        GroupNormBwdDesc, dy=dy, dy2=dy2, x=x, gamma=gamma, stats=stats, bstats=bstats, dx_f32=dx_f32, dx_bf16=dx_bf16,
+        dgamma=dgamma, dbeta=dbeta, B=B, HW=HW, C=C, G=G, eps=eps, out_rows_per_img=rows_per_img, out_row_off=row_off))
     return dx_f32, dx_bf16
 
 
@@ -881,9 +905,9 @@ def attn_fwd(q, k, v, kpm, *, B, H, Sq, Sk, dh, scale, drop_p=0.0, drop_seed=0, 
     if out is None:
         out = _new((B * Sq, H * dh), torch.bfloat16, q)
     lse = _new((B, H, Sq), torch.float32, q)
-    d = AttnDesc(_p(q), _p(k), _p(v), _p(out), _p(lse), _p(kpm), B, H, Sq, Sk, dh, _ld(q), _ld(k), _ld(v), _ld(out),
-                 scale, drop_p, drop_seed & 0xFFFFFFFF, _seedp(drop_p))
-    _check(lib().rt_attn_fwd(ctypes.byref(d), _stream()), "rt_attn_fwd")
+    _call("rt_attn_fwd", _desc(
+        AttnDesc, q=q, k=k, v=v, out=out, lse=lse, kpm=kpm, B=B, H=H, Sq=Sq, Sk=Sk, dh=dh, ldq=_ld(q), ldk=_ld(k), ldv=_ld(v),
+        ldo=_ld(out), scale=scale, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF, seed_dev=_seedp(drop_p)))
     return out, lse
 
 
@@ -897,15 +921,12 @@ def attn_bwd(q, k, v, out, dout, lse, kpm, *, B, H, Sq, Sk, dh, scale, drop_p=0.
     if dv is None:
         dv = _new((B * Sk, H * dh), torch.bfloat16, q)
     delta = _new((B, H, Sq), torch.float32, q)
-    d = AttnBwdDesc(_p(q), _p(k), _p(v), _p(out), _p(dout), _p(lse), _p(delta), _p(kpm), _p(dq), _p(dk), _p(dv),
-                    B, H, Sq, Sk, dh, _ld(q), _ld(k), _ld(v), _ld(out), _ld(dq), _ld(dk), _ld(dv),
-                    scale, drop_p, drop_seed & 0xFFFFFFFF, _seedp(drop_p))
+    d = _desc(AttnBwdDesc, q=q, k=k, v=v, out=out, dout=dout, lse=lse, delta=delta, kpm=kpm, dq=dq, dk=dk, dv=dv,
+              B=B, H=H, Sq=Sq, Sk=Sk, dh=dh, ldq=_ld(q), ldk=_ld(k), ldv=_ld(v), ldo=_ld(out), lddq=_ld(dq), lddk=_ld(dk), lddv=_ld(dv),
+              scale=scale, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF, seed_dev=_seedp(drop_p))
     assert _ld(dout) == _ld(out)
-    _check(lib().rt_attn_bwd(ctypes.byref(d), _stream()), "rt_attn_bwd")
+    _call("rt_attn_bwd", d)
     return dq, dk, dv
-
-
-DEC_HANDOFF_BYTES = 256 + 16 * 256 * 36 + 16 * 2048 * 4
 
 
 def decoder_handoff(dev):
@@ -919,19 +940,12 @@ def decoder_fwd(layers, t32, t16, qpos, kpm, *, H, S, F, drop_p, scale, handoff,
     layer, keys = DecoderLayerFwd._PTRS (tensors) + DecoderLayerFwd._SEEDS (ints); every output tensor is allocated by the
     caller (they are the launched chain's saved tensors).  Returns the hand-off buffer's header [epoch, failure flag]."""
     M = t32.shape[0]
-    d = DecoderFwdDesc()
     assert 1 <= len(layers) <= DEC_MAX_LAYERS
+    d = _desc(DecoderFwdDesc, t32=t32, t16=t16, qpos=qpos, kpm=kpm, handoff=handoff, seed_dev=_seedp(drop_p), n_layers=len(layers),
+              M=M, H=H, S=S, F=F, ldkv=_ld(layers[0]["k2"]), drop_p=drop_p, eps=eps, scale=scale)
     for i, lay in enumerate(layers):
-        L = d.layer[i]
-        for n in DecoderLayerFwd._PTRS:
-            setattr(L, n, _p(lay[n]))
-        for n in DecoderLayerFwd._SEEDS:
-            setattr(L, n, lay[n] & 0xFFFFFFFF)
-    d.t32, d.t16, d.qpos, d.kpm, d.handoff = _p(t32), _p(t16), _p(qpos), _p(kpm), _p(handoff)
-    d.seed_dev = _seedp(drop_p)
-    d.n_layers, d.M, d.H, d.S, d.F, d.ldkv = len(layers), M, H, S, F, _ld(layers[0]["k2"])
-    d.drop_p, d.eps, d.scale = drop_p, eps, scale
-    _check(lib().rt_decoder_fwd(ctypes.byref(d), _stream()), "rt_decoder_fwd")
+        _set(d.layer[i], **{n: lay[n] for n in DecoderLayerFwd._PTRS}, **{n: lay[n] & 0xFFFFFFFF for n in DecoderLayerFwd._SEEDS})
+    _call("rt_decoder_fwd", d)
     return handoff[:2]
 
 
@@ -939,25 +953,20 @@ def decoder_bwd(layers, dta, dqpos, kpm, *, H, S, F, drop_p, scale, gate_scale, 
     """Backward of the cooperative decoder stack (rt_decoder_bwd).  `layers`: one dict per layer (first to last), keys =
     DecoderLayerBwd._PTRS (tensors, all allocated by the caller) + the dropout seeds of the forward."""
     M = dta.shape[0]
-    d = DecoderBwdDesc()
     assert 1 <= len(layers) <= DEC_MAX_LAYERS
+    d = _desc(DecoderBwdDesc, dta=dta, dqpos=dqpos, kpm=kpm, handoff=handoff, seed_dev=_seedp(drop_p), n_layers=len(layers),
+              M=M, H=H, S=S, F=F, ldkv=_ld(layers[0]["k2"]), drop_p=drop_p, scale=scale, gate_scale=gate_scale, ldkvp=ldkvp)
     for i, lay in enumerate(layers):
-        L = d.layer[i]
-        for n in DecoderLayerBwd._PTRS:
-            setattr(L, n, _p(lay.get(n)))
-        for n in DecoderLayerBwd._SEEDS[:-1]:
-            setattr(L, n, lay[n] & 0xFFFFFFFF)
-    d.dta, d.dqpos, d.kpm, d.handoff, d.seed_dev = _p(dta), _p(dqpos), _p(kpm), _p(handoff), _seedp(drop_p)
-    d.n_layers, d.M, d.H, d.S, d.F, d.ldkv = len(layers), M, H, S, F, _ld(layers[0]["k2"])
-    d.drop_p, d.scale, d.gate_scale, d.ldkvp = drop_p, scale, gate_scale, ldkvp
-    _check(lib().rt_decoder_bwd(ctypes.byref(d), _stream()), "rt_decoder_bwd")
+        _set(d.layer[i], **{n: lay.get(n) for n in DecoderLayerBwd._PTRS},
+             **{n: lay[n] & 0xFFFFFFFF for n in DecoderLayerBwd._SEEDS[:-1]})
+    _call("rt_decoder_bwd", d)
     return handoff[:2]
 
 
 def decoder_trace(readback=True):
     """REFTR_DEC_TRACE=1: (workgroup 0 stamps, last workgroup stamps) of the last rt_decoder_fwd launch, 100 MHz ticks."""
     buf = (c_uint32 * 1024)()
-    _check(lib().rt_decoder_trace(ctypes.cast(buf, c_void_p) if readback else None), "rt_decoder_trace")
+    _call("rt_decoder_trace", ctypes.cast(buf, c_void_p) if readback else None, stream=False)
     if not readback:
         return None
     a = list(buf)
@@ -981,14 +990,14 @@ def img_pack(img):
     _req(img, torch.float32, "img")
     _, _, Hp, Wp = stem_geometry(H, W)
     out = _new((B, Hp, Wp, 4), torch.bfloat16, img)
-    _check(lib().rt_img_pack(_p(img), _p(out), B, H, W, Hp, Wp, _stream()), "rt_img_pack")
+    _call("rt_img_pack", img, out, B, H, W, Hp, Wp)
     return out
 
 
 def stem_conv(xp, w, bias, Ho, Wo):
     B, Hp, Wp, _ = xp.shape
     out = _new((B, Ho, Wo, 64), torch.bfloat16, xp)
-    _check(lib().rt_stem_conv(_p(xp), _p(w), _p(bias), _p(out), B, Hp, Wp, Ho, Wo, _stream()), "rt_stem_conv")
+    _call("rt_stem_conv", xp, w, bias, out, B, Hp, Wp, Ho, Wo)
     return out
 
 
@@ -996,7 +1005,7 @@ def maxpool3x3s2(x):
     B, H, W, C = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = _new((B, Ho, Wo, C), torch.bfloat16, x)
-    _check(lib().rt_maxpool3x3s2(_p(x), _p(y), B, H, W, C, Ho, Wo, _stream()), "rt_maxpool3x3s2")
+    _call("rt_maxpool3x3s2", x, y, B, H, W, C, Ho, Wo)
     return y
 
 
@@ -1004,7 +1013,7 @@ def stem_pool(xp, w, bias, Ho, Wo):
     """conv1 7x7/2 + FrozenBN + ReLU + MaxPool2d(3, 2, 1) in one launch: the stem output is never written."""
     B, Hp, Wp, _ = xp.shape
     out = _new((B, (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1, 64), torch.bfloat16, xp)
-    _check(lib().rt_stem_pool(_p(xp), _p(w), _p(bias), _p(out), B, Hp, Wp, Ho, Wo, _stream()), "rt_stem_pool")
+    _call("rt_stem_pool", xp, w, bias, out, B, Hp, Wp, Ho, Wo)
     return out
 
 
@@ -1014,37 +1023,38 @@ def bottleneck_fwd(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, out=None, form=0
     B, Hh, Ww, cin = x.shape
     if out is None:
         out = _new((B, Hh, Ww, 256), torch.bfloat16, x)
-    d = BottleneckDesc(_p(x), _p(w1), _p(w2), _p(w3), _p(wd), _p(b1), _p(b2), _p(b3), _p(bd), _p(out), B, Hh, Ww, cin, w1.shape[0], form)
+    d = _desc(BottleneckDesc, x=x, w1=w1, w2=w2, w3=w3, wd=wd, b1=b1, b2=b2, b3=b3, bd=bd, out=out, B=B, H=Hh, W=Ww, cin=cin,
+              planes=w1.shape[0], form=form)
     # a member of the GEMM family of bench.py's roofline: the algorithmic FLOPs of the convolutions it replaces (the conv1 halo
     # recomputation is not counted), compulsory bytes = block input + output + weights once
     M = B * Hh * Ww
     macs = cin * 64 + 576 * 64 + 64 * 256 + (cin * 256 if wd is not None else 0)
     nbytes = 2.0 * (M * (cin + 256) + macs)
-    _timed("bottleneck_fwd", 2.0 * M * macs, lambda: _check(lib().rt_bottleneck_fwd(ctypes.byref(d), _stream()), "rt_bottleneck_fwd"),
-           tag=("BNK", B, Hh, Ww, cin, Hh, Ww, 256, 3, 3, 1, 1), nbytes=nbytes)
+    _timed("bottleneck_fwd", 2.0 * M * macs, lambda: _call("rt_bottleneck_fwd", d), tag=("BNK", B, Hh, Ww, cin, Hh, Ww, 256, 3, 3, 1, 1),
+           nbytes=nbytes)
     return out
 
 
 def weight_prep(src, N, T, C, *, scale=None, dst=None, dst_t=None):
     """fp32 [N][T][C] master -> bf16 dst [N][T][C] and/or dst_t [C][T][N] (both * scale[n])."""
     _req(src, torch.float32, "src")
-    _check(lib().rt_weight_prep(_p(src), _p(scale), _p(dst), _p(dst_t), N, T, C, _stream()), "rt_weight_prep")
+    _call("rt_weight_prep", src, scale, dst, dst_t, N, T, C)
 
 
 def stem_weight_prep(src, scale, dst):
-    _check(lib().rt_stem_weight_prep(_p(src), _p(scale), _p(dst), _stream()), "rt_stem_weight_prep")
+    _call("rt_stem_weight_prep", src, scale, dst)
 
 
 def bn_fold(w, b, rm, rv, eps, scale, shift):
-    _check(lib().rt_bn_fold(_p(w), _p(b), _p(rm), _p(rv), eps, _p(scale), _p(shift), w.numel(), _stream()), "rt_bn_fold")
+    _call("rt_bn_fold", w, b, rm, rv, eps, scale, shift, w.numel())
 
 
 def mask_posenc(mask_u8, h, w, C, add_vec, kpm_out, kpm_off, pos_out, rows_per_img, row_off):
     """mask uint8 [B,H,W]; writes kpm_out[b, kpm_off + pix] and pos_out[b*rows_per_img + row_off + pix, :]."""
     B, H, W = mask_u8.shape
-    d = MaskPosencDesc(_p(mask_u8), _p(kpm_out), _p(pos_out), _p(add_vec), B, H, W, h, w, C,
-                       kpm_out.shape[1], kpm_off, rows_per_img, row_off)
-    _check(lib().rt_mask_posenc(ctypes.byref(d), _stream()), "rt_mask_posenc")
+    _call("rt_mask_posenc", _desc(
+        MaskPosencDesc, mask=mask_u8, kpm_out=kpm_out, pos_out=pos_out, add_vec=add_vec, B=B, H=H, W=W, h=h, w=w, C=C,
+        kpm_stride=kpm_out.shape[1], kpm_off=kpm_off, pos_rows_per_img=rows_per_img, pos_row_off=row_off))
 
 
 # --------------------------------------------------------------------------------------------
@@ -1053,20 +1063,22 @@ def mask_posenc(mask_u8, h, w, C, add_vec, kpm_out, kpm_off, pos_out, rows_per_i
 def colsum(dy, db):
     """db[n] += sum_m dy[m, n] (dy bf16 or fp32, 2-D contiguous)."""
     M, N = dy.shape
-    _check(lib().rt_colsum(_p(dy), 1 if dy.dtype == torch.bfloat16 else 0, _p(db), M, N, _stream()), "rt_colsum")
+    _call("rt_colsum", dy, 1 if dy.dtype == torch.bfloat16 else 0, db, M, N)
 
 
 def rows_add(rows, D, *, a_f32=None, a_bf16=None, b_f32=None, out_f32=None, out_bf16=None, alpha=1.0,
              accumulate=False, a_map=(0, 0, 0), b_map=(0, 0, 0), o_map=(0, 0, 0)):
-    d = RowsAddDesc(_p(a_f32), _p(a_bf16), _p(b_f32), _p(out_f32), _p(out_bf16), rows, D, alpha,
-                    int(accumulate), *a_map, *b_map, *o_map)
-    _check(lib().rt_rows_add(ctypes.byref(d), _stream()), "rt_rows_add")
+    (a_rows, a_stride, a_off), (b_rows, b_stride, b_off), (o_rows, o_stride, o_off) = a_map, b_map, o_map
+    _call("rt_rows_add", _desc(
+        RowsAddDesc, a_f32=a_f32, a_bf16=a_bf16, b_f32=b_f32, out_f32=out_f32, out_bf16=out_bf16, rows=rows, D=D, alpha=alpha,
+        accumulate=int(accumulate), a_grp_rows=a_rows, a_grp_stride=a_stride, a_grp_off=a_off, b_grp_rows=b_rows, b_grp_stride=b_stride,
+        b_grp_off=b_off, o_grp_rows=o_rows, o_grp_stride=o_stride, o_grp_off=o_off))
 
 
 def roberta_pos_ids(ids, pad_idx):
     B, L = ids.shape
     out = torch.empty((B, L), dtype=torch.int32, device=ids.device)
-    _check(lib().rt_roberta_pos_ids(_p(ids), _p(out), B, L, pad_idx, _stream()), "rt_roberta_pos_ids")
+    _call("rt_roberta_pos_ids", ids, out, B, L, pad_idx)
     return out
 
 
@@ -1074,15 +1086,13 @@ def bert_embed_fwd(ids, word, pos, type_emb, L, pos_ids=None):
     rows = ids.numel()
     D = word.shape[1]
     out = _new((rows, D), torch.float32, word)
-    _check(lib().rt_bert_embed_fwd(_p(ids), _p(word), _p(pos), _p(type_emb), _p(out), rows, L, D, _p(pos_ids), _stream()),
-           "rt_bert_embed_fwd")
+    _call("rt_bert_embed_fwd", ids, word, pos, type_emb, out, rows, L, D, pos_ids)
     return out
 
 
 def bert_embed_bwd(ids, de, dword, dpos, dtype_emb, L, pos_ids=None):
     rows, D = de.shape
-    _check(lib().rt_bert_embed_bwd(_p(ids), _p(de), _p(dword), _p(dpos), _p(dtype_emb), rows, L, D, _p(pos_ids), _stream()),
-           "rt_bert_embed_bwd")
+    _call("rt_bert_embed_bwd", ids, de, dword, dpos, dtype_emb, rows, L, D, pos_ids)
 
 
 def context_mask(smask_u8, phrase_mask_u8=None, pos_l=None, pos_r=None):
@@ -1094,8 +1104,7 @@ def context_mask(smask_u8, phrase_mask_u8=None, pos_l=None, pos_r=None):
         _, P, Lp = phrase_mask_u8.shape
     ctx = _new((B, P, L), torch.uint8, smask_u8)
     qmask = _new((B, P), torch.uint8, smask_u8)
-    _check(lib().rt_context_mask(_p(smask_u8), _p(phrase_mask_u8), _p(pos_l), _p(pos_r), _p(ctx), _p(qmask),
-                                 B, L, P, Lp, _stream()), "rt_context_mask")
+    _call("rt_context_mask", smask_u8, phrase_mask_u8, pos_l, pos_r, ctx, qmask, B, L, P, Lp)
     return ctx, qmask
 
 
@@ -1105,7 +1114,7 @@ def qenc_attn_fwd(k, qs, vs, ctx):
     P = ctx.shape[1]
     w = _new((B, P, L), torch.float32, qs)
     c = _new((B, P, E), torch.float32, qs)
-    _check(lib().rt_qenc_attn_fwd(_p(k), _p(qs), _p(vs), _p(ctx), _p(w), _p(c), B, P, L, E, _stream()), "rt_qenc_attn_fwd")
+    _call("rt_qenc_attn_fwd", k, qs, vs, ctx, w, c, B, P, L, E)
     return w, c
 
 
@@ -1114,48 +1123,31 @@ def qenc_attn_bwd(k, qs, vs, w, dc):
     P = w.shape[1]
     zz = torch.zeros(B * E + 2 * B * L * E, dtype=torch.float32, device=qs.device)       # one clear for the three outputs
     dk, dqs, dvs = zz[:B * E].view(B, E), zz[B * E:B * E + B * L * E].view(B, L, E), zz[B * E + B * L * E:].view(B, L, E)
-    _check(lib().rt_qenc_attn_bwd(_p(k), _p(qs), _p(vs), _p(w), _p(dc), _p(dk), _p(dqs), _p(dvs), B, P, L, E, _stream()),
-           "rt_qenc_attn_bwd")
+    _call("rt_qenc_attn_bwd", k, qs, vs, w, dc, dk, dqs, dvs, B, P, L, E)
     return dk, dqs, dvs
-
-
-def _fill(desc_cls, ptrs, **scalars):
-    """A descriptor whose pointer fields are named tensors (None -> NULL); unknown names are an error."""
-    d = desc_cls()
-    names = set(desc_cls._PTRS)
-    for k, v in ptrs.items():
-        if k not in names:
-            raise KeyError(f"{desc_cls.__name__}: no pointer field {k!r}")
-        setattr(d, k, _p(v))
-    for k, v in scalars.items():
-        setattr(d, k, v)
-    return d
 
 
 def qenc_fwd(*, B, S, L, P, nq, E, eps=1e-5, drop_p=0.0, drop_seed=0, **t):
     """QueryEncoder forward + query / query_pos split as ONE launch (rt_qenc_fwd).  `t`: the named tensors of rt_qenc_fwd_desc."""
-    d = _fill(QencFwdDesc, dict(t, seed_dev=_SEED_DEV if drop_p > 0 else None), B=B, S=S, L=L, P=P, nq=nq, E=E, eps=eps,
-              drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF, reserved=0)
-    _check(lib().rt_qenc_fwd(ctypes.byref(d), _stream()), "rt_qenc_fwd")
+    _call("rt_qenc_fwd", _desc(QencFwdDesc, **dict(t, seed_dev=_SEED_DEV if drop_p > 0 else None), B=B, S=S, L=L, P=P, nq=nq, E=E,
+                               eps=eps, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF))
 
 
 def head_loss(*, NL, B, P, K, E, eps=1e-5, invert_valid=False, **t):
     """decoder.norm + bbox MLP + box losses + d total / d logits + their backward-data as ONE launch (rt_head_loss)."""
-    d = _fill(HeadLossDesc, t, NL=NL, B=B, P=P, K=K, E=E, eps=eps, invert_valid=int(bool(invert_valid)), reserved=0)
-    _check(lib().rt_head_loss(ctypes.byref(d), _stream()), "rt_head_loss")
+    _call("rt_head_loss", _desc(HeadLossDesc, **t, NL=NL, B=B, P=P, K=K, E=E, eps=eps, invert_valid=int(bool(invert_valid))))
 
 
 def qenc_bwd(*, B, S, L, P, E, drop_p=0.0, drop_seed=0, **t):
     """Backward-data of rt_qenc_fwd as ONE launch (rt_qenc_bwd)."""
-    d = _fill(QencBwdDesc, dict(t, seed_dev=_SEED_DEV if drop_p > 0 else None), B=B, S=S, L=L, P=P, E=E, drop_p=drop_p,
-              drop_seed=drop_seed & 0xFFFFFFFF, reserved=0)
-    _check(lib().rt_qenc_bwd(ctypes.byref(d), _stream()), "rt_qenc_bwd")
+    _call("rt_qenc_bwd", _desc(QencBwdDesc, **dict(t, seed_dev=_SEED_DEV if drop_p > 0 else None), B=B, S=S, L=L, P=P, E=E,
+                               drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF))
 
 
 def qregion_trace():
     """Stage stamps [3][24] (10 ns units) of workgroup 0 of the last rt_qenc_fwd / rt_head_loss / rt_qenc_bwd launches."""
     buf = (ctypes.c_uint64 * 72)()
-    _check(lib().rt_qregion_trace(ctypes.cast(buf, c_void_p)), "rt_qregion_trace")
+    _call("rt_qregion_trace", ctypes.cast(buf, c_void_p), stream=False)
     return [list(buf[i * 24:(i + 1) * 24]) for i in range(3)]
 
 
@@ -1166,9 +1158,8 @@ def box_loss(logits, valid_u8, targets, tgt_off, num_boxes, w_bbox=1.0, w_giou=1
     buf = _new((NL * 2 + 1,), torch.float32, logits)        # [NL][2] losses | total: one clear inside rt_box_loss
     losses, total = buf[:NL * 2].view(NL, 2), buf[NL * 2:]
     dl = _new(tuple(logits.shape), torch.float32, logits) if want_grad else None
-    d = BoxLossDesc(_p(logits), _p(valid_u8), _p(targets), _p(tgt_off), _p(num_boxes), _p(losses), _p(total), _p(dl),
-                    NL, B, P, K, w_bbox, w_giou, _p(weights))
-    _check(lib().rt_box_loss(ctypes.byref(d), _stream()), "rt_box_loss")
+    _call("rt_box_loss", _desc(BoxLossDesc, logits=logits, valid=valid_u8, targets=targets, tgt_off=tgt_off, num_boxes=num_boxes,
+                               losses=losses, total=total, dlogits=dl, NL=NL, B=B, P=P, K=K, w_bbox=w_bbox, w_giou=w_giou, weights=weights))
     return losses, total, dl
 
 
@@ -1180,9 +1171,8 @@ def cem_fwd(hs16, w3, b3, res16, w2, b2, B, HW):
     E = hs16.shape[-1]
     u = _new((B, 16), torch.float32, w3); energy = _new((B,), torch.float32, w3); stats = _new((B, 2), torch.float32, w3)
     loss = _new((1,), torch.float32, w3)
-    d = CemDesc(_p(hs16), _p(w3), _p(b3), _p(res16), _p(w2), _p(b2), _p(u), _p(energy), _p(stats), _p(loss), None,
-                None, None, None, None, None, B, HW, res16.shape[-1], 0, E, 0)
-    _check(lib().rt_cem_fwd(ctypes.byref(d), _stream()), "rt_cem_fwd")
+    _call("rt_cem_fwd", _desc(CemDesc, hs=hs16, w3=w3, b3=b3, res=res16, w2=w2, b2=b2, u=u, energy=energy, stats=stats, loss=loss,
+                              B=B, HW=HW, ld=res16.shape[-1], E=E))
     return loss, (u, energy, stats)
 
 
@@ -1194,9 +1184,8 @@ def cem_bwd(hs16, w3, b3, res16, w2, b2, saved, g, dres, dw3, db3, dw2, B, HW):
     u, energy, stats = saved
     E = hs16.shape[-1]
     dhs = _new((B, E), torch.float32, w3)
-    d = CemDesc(_p(hs16), _p(w3), _p(b3), _p(res16), _p(w2), _p(b2), _p(u), _p(energy), _p(stats), None, _p(g),
-                _p(dres), _p(dhs), _p(dw3), _p(db3), _p(dw2), B, HW, res16.shape[-1], dres.shape[-1], E, 0)
-    _check(lib().rt_cem_bwd(ctypes.byref(d), _stream()), "rt_cem_bwd")
+    _call("rt_cem_bwd", _desc(CemDesc, hs=hs16, w3=w3, b3=b3, res=res16, w2=w2, b2=b2, u=u, energy=energy, stats=stats, g=g, dres=dres,
+                              dhs=dhs, dw3=dw3, db3=db3, dw2=dw2, B=B, HW=HW, ld=res16.shape[-1], lddr=dres.shape[-1], E=E))
     return dhs
 
 
@@ -1209,9 +1198,9 @@ def mask_postprocess(pred, sizes_i32, max_hw, threshold=0.5, orig_i32=None, orig
     max_h, max_w = int(max_hw[0]), int(max_hw[1])
     masks = _new((B, Q, max_h, max_w), torch.uint8, pred)
     mo = _new((int(origin_total),), torch.uint8, pred) if orig_i32 is not None else None
-    d = MaskPostDesc(_p(pred), _p(sizes_i32), _p(orig_i32), _p(origin_off), _p(masks), _p(mo), B, Q, h, w, max_h, max_w,
-                     int(max_origin), float(threshold))
-    _check(lib().rt_mask_postprocess(ctypes.byref(d), _stream()), "rt_mask_postprocess")
+    _call("rt_mask_postprocess", _desc(
+        MaskPostDesc, pred=pred, sizes=sizes_i32, orig=orig_i32, origin_off=origin_off, masks=masks, masks_origin=mo, B=B, Q=Q, h=h, w=w,
+        max_h=max_h, max_w=max_w, max_origin=int(max_origin), threshold=float(threshold)))
     return masks, mo
 
 
@@ -1222,15 +1211,8 @@ def box_postprocess(boxes, valid_u8, sizes_f32=None):
     _req(boxes, torch.float32, "boxes"); _req(valid_u8, torch.uint8, "valid"); _req(sizes_f32, torch.float32, "sizes")
     out = torch.zeros(B, P, 4, dtype=torch.float32, device=boxes.device)
     counts = _new((B,), torch.int32, boxes)
-    d = BoxPostDesc(_p(boxes), _p(valid_u8), _p(sizes_f32), _p(out), _p(counts), B, P, K)
-    _check(lib().rt_box_postprocess(ctypes.byref(d), _stream()), "rt_box_postprocess")
+    _call("rt_box_postprocess", _desc(BoxPostDesc, boxes=boxes, valid=valid_u8, sizes=sizes_f32, out=out, counts=counts, B=B, P=P, K=K))
     return out, counts
-
-
-# rt_eval_metrics: accumulator slots (8 bytes each: int64 but for the two double sums) and the mask kernel's pixels per workgroup
-(EVAL_DET_N, EVAL_DET_HIT, EVAL_SEG_N, EVAL_SEG_HIT, EVAL_SEG_I, EVAL_SEG_U, EVAL_DET_SUM, EVAL_SEG_SUM, EVAL_SLOTS) = (
-    0, 1, 6, 7, 12, 13, 14, 15, 16)
-EVAL_CHUNK = 16384
 
 
 def eval_metrics(pred_boxes, valid_u8, table, acc, masks=None, sizes_i32=None, reset=False):
@@ -1252,9 +1234,9 @@ def eval_metrics(pred_boxes, valid_u8, table, acc, masks=None, sizes_i32=None, r
         partials = _new((B, max(1, -(-(max_h * max_w) // EVAL_CHUNK)), 2), torch.int32, pred_boxes)
         iou_seg = _new((B,), torch.float32, pred_boxes)
         iu = _new((B, 2), torch.int64, pred_boxes)
-    a = EvalMetricsArgs(_p(pred_boxes), _p(valid_u8), _p(table), _p(masks), _p(sizes_i32), _p(partials), _p(iou_det), _p(iou_seg),
-                        _p(iu), _p(acc), B, P, K, Q, max_h, max_w, 1 if reset else 0)
-    _check(lib().rt_eval_metrics(ctypes.byref(a), _stream()), "rt_eval_metrics")
+    _call("rt_eval_metrics", _desc(
+        EvalMetricsArgs, pred_boxes=pred_boxes, valid=valid_u8, table=table, masks=masks, sizes=sizes_i32, partials=partials,
+        iou_det=iou_det, iou_seg=iou_seg, iu=iu, acc=acc, B=B, P=P, K=K, Q=Q, max_h=max_h, max_w=max_w, reset=1 if reset else 0))
     return iou_det, iou_seg, iu
 
 
@@ -1277,9 +1259,8 @@ def eval_facts(sizes, facts, image_ids, origs=None, ids=None, mask_hw=None):
     hw = None
     if mask_hw is not None:
         assert len(mask_hw) == B
-        hw = (ctypes.c_int32 * (2 * B))(*[int(v) for p in mask_hw for v in p])
-    _check(lib().rt_eval_facts(ptrs(sizes, 2), ptrs(origs, 2), ptrs(ids, 1), hw, B, _p(facts), _p(image_ids), _stream()),
-           "rt_eval_facts")
+        hw = (c_int32 * (2 * B))(*[int(v) for p in mask_hw for v in p])
+    _call("rt_eval_facts", ptrs(sizes, 2), ptrs(origs, 2), ptrs(ids, 1), hw, B, facts, image_ids)
 
 
 class EvalCanvasState:
@@ -1324,29 +1305,26 @@ def eval_canvas(pred_boxes, valid_u8, tgt_boxes, tgt_off, facts, image_ids, stat
             partials = _new((B, max(1, -(-(Hc * Wc) // EVAL_CHUNK)), 2), torch.int32, pred_boxes)
             iou_seg = _new((B,), torch.float32, pred_boxes)
             iu = _new((B, 2), torch.int64, pred_boxes)
-    a = EvalCanvasArgs(_p(pred_boxes), _p(valid_u8), _p(tgt_boxes), _p(tgt_off), _p(facts), _p(image_ids), _p(pred_masks),
-                       _p(tgt_masks) if pred_masks is not None else None, _p(partials), _p(iou_det), _p(iou_seg), _p(iu), _p(state.acc),
-                       _p(state.boxes), _p(state.counts), _p(state.ids), _p(state.cursor), _p(veto), B, P, K, Q, h, w, Hc, Wc,
-                       int(tgt_boxes.shape[0]), state.slots, float(threshold))
-    _check(lib().rt_eval_canvas(ctypes.byref(a), _stream()), "rt_eval_canvas")
+    _call("rt_eval_canvas", _desc(
+        EvalCanvasArgs, pred_boxes=pred_boxes, valid=valid_u8, tgt_boxes=tgt_boxes, tgt_off=tgt_off, facts=facts, image_ids=image_ids,
+        pred_masks=pred_masks, tgt_masks=tgt_masks if pred_masks is not None else None, partials=partials, iou_det=iou_det,
+        iou_seg=iou_seg, iu=iu, acc=state.acc, ring_boxes=state.boxes, ring_counts=state.counts, ring_ids=state.ids, cursor=state.cursor,
+        veto=veto, B=B, P=P, K=K, Q=Q, h=h, w=w, Hc=Hc, Wc=Wc, tgt_rows=int(tgt_boxes.shape[0]), slots=state.slots,
+        threshold=float(threshold)))
     return iou_det, iou_seg, iu
 
 
 def zero_chunks(base, table, n):
     """Clears n chunks {element offset, count} (static device int64 table) of the fp32 buffer `base` in one launch."""
     _req(base, torch.float32, "base"); _req(table, torch.int64, "table")
-    _check(lib().rt_zero_chunks(_p(base), _p(table), int(n), _stream()), "rt_zero_chunks")
+    _call("rt_zero_chunks", base, table, int(n))
 
 
 def sqnorm(g, out):
     if g.dtype == torch.bfloat16:
-        _check(lib().rt_sqnorm_bf16(_p(g), g.numel(), _p(out), _stream()), "rt_sqnorm_bf16")
+        _call("rt_sqnorm_bf16", g, g.numel(), out)
     else:
-        _check(lib().rt_sqnorm(_p(g), g.numel(), _p(out), _stream()), "rt_sqnorm")
-
-
-ACCUM_FIRST, ACCUM_ADD, ACCUM_FINISH = 0, 1, 2
-GRAD_ACCUM_SLOTS = 2048
+        _call("rt_sqnorm", g, g.numel(), out)
 
 
 def grad_accum(mode, g, acc, scale=1.0, scale_dev=None, partials=None, out_sq=None):
@@ -1357,8 +1335,7 @@ def grad_accum(mode, g, acc, scale=1.0, scale_dev=None, partials=None, out_sq=No
     _req(scale_dev, torch.float32, "scale_dev"); _req(partials, torch.float32, "partials"); _req(out_sq, torch.float32, "out_sq")
     assert g.is_contiguous() and acc.is_contiguous() and g.numel() == acc.numel()
     assert partials is None or partials.numel() >= GRAD_ACCUM_SLOTS
-    _check(lib().rt_grad_accum(int(mode), _p(g), _p(acc), g.numel(), float(scale), _p(scale_dev), _p(partials), _p(out_sq), _stream()),
-           "rt_grad_accum")
+    _call("rt_grad_accum", int(mode), g, acc, g.numel(), float(scale), scale_dev, partials, out_sq)
 
 
 def adamw_flat(p, g, m, v, *, step, ranges, gnorm_sq=None, gnorm_out=None, grad_scale=1.0, max_norm=0.0,
@@ -1369,26 +1346,22 @@ def adamw_flat(p, g, m, v, *, step, ranges, gnorm_sq=None, gnorm_out=None, grad_
     (m = momentum buffer, beta1 = momentum, v unused).  mat = (device job table, njobs, total tiles) and / or chunks = (device
     chunk table, nchunks): the matrix-aware form (rt_adamw_mat + rt_adamw_chunks) that also emits the bf16 operands; the
     tables say what is updated and `span` is ignored."""
-    d = AdamWDesc()
-    d.p, d.g, d.m, d.v, d.n = _p(p), _p(g), _p(m), _p(v), p.numel()
-    d.gnorm_sq, d.gnorm_out = _p(gnorm_sq), _p(gnorm_out)
-    d.grad_scale, d.max_norm, d.beta1, d.beta2, d.eps = grad_scale, max_norm, beta1, beta2, eps
-    d.step, d.n_ranges = step, len(ranges)
-    d.step_dev, d.active, d.lr_dev = _p(step_dev), _p(active), _p(lr_dev)
-    d.span_begin, d.span_end = (0, 0) if span is None else span
-    d.g16 = _p(g16)
-    for i, (b, e, lr, wd) in enumerate(ranges):
-        d.range_begin[i], d.range_end[i], d.range_lr[i], d.range_wd[i] = b, e, lr, wd
+    span_begin, span_end = (0, 0) if span is None else span
+    begins, ends, lrs, wds = zip(*ranges) if ranges else ((), (), (), ())
+    d = _desc(AdamWDesc, p=p, g=g, m=m, v=v, n=p.numel(), gnorm_sq=gnorm_sq, gnorm_out=gnorm_out, grad_scale=grad_scale,
+              max_norm=max_norm, beta1=beta1, beta2=beta2, eps=eps, step=step, n_ranges=len(ranges), range_begin=begins, range_end=ends,
+              range_lr=lrs, range_wd=wds, step_dev=step_dev, active=active, lr_dev=lr_dev, span_begin=span_begin, span_end=span_end,
+              g16=g16)
     if mat is not None or chunks is not None:
         assert not sgd
         if mat is not None and mat[1] > 0:
-            _check(lib().rt_adamw_mat(ctypes.byref(d), _p(mat[0]), mat[1], mat[2], _stream()), "rt_adamw_mat")
+            _call("rt_adamw_mat", d, mat[0], mat[1], mat[2])
         if chunks is not None and chunks[1] > 0:
-            _check(lib().rt_adamw_chunks(ctypes.byref(d), _p(chunks[0]), chunks[1], _stream()), "rt_adamw_chunks")
+            _call("rt_adamw_chunks", d, chunks[0], chunks[1])
     elif sgd:
-        _check(lib().rt_sgd_flat(ctypes.byref(d), _stream()), "rt_sgd_flat")
+        _call("rt_sgd_flat", d)
     else:
-        _check(lib().rt_adamw_flat(ctypes.byref(d), _stream()), "rt_adamw_flat")
+        _call("rt_adamw_flat", d)
 
 
 def small_dgrad(dy_f32, w_f32, gate=None):
@@ -1396,60 +1369,46 @@ def small_dgrad(dy_f32, w_f32, gate=None):
     M, N = dy_f32.shape
     K = w_f32.shape[1]
     dx = _new((M, K), torch.bfloat16, dy_f32)
-    _check(lib().rt_small_dgrad(_p(dy_f32), _p(w_f32), _p(gate), _p(dx), M, N, K, _stream()), "rt_small_dgrad")
+    _call("rt_small_dgrad", dy_f32, w_f32, gate, dx, M, N, K)
     return dx
 
 
 def pos_grad(dpos, d_lang_pos, d_type, d_level, B, S, L):
     E = dpos.shape[1]
-    _check(lib().rt_pos_grad(_p(dpos), _p(d_lang_pos), _p(d_type), _p(d_level), B, S, L, E, _stream()), "rt_pos_grad")
+    _call("rt_pos_grad", dpos, d_lang_pos, d_type, d_level, B, S, L, E)
 
 
 def counter_add(ctr, inc=1, unless=None, reset_else=False):
     """*ctr += inc on the device; `unless` (a device word): only while it is 0, else *ctr is left alone or -- reset_else --
     cleared (rt_counter_add_if_zero)."""
     if unless is not None:
-        _check(lib().rt_counter_add_if_zero(_p(ctr), inc, _p(unless), int(bool(reset_else)), _stream()), "rt_counter_add_if_zero")
+        _call("rt_counter_add_if_zero", ctr, inc, unless, int(bool(reset_else)))
     else:
-        _check(lib().rt_counter_add(_p(ctr), inc, _stream()), "rt_counter_add")
+        _call("rt_counter_add", ctr, inc)
 
 
 def finish_step(step_dev, active, veto=None, loss=None):
     """*step_dev += 1, *active += 1 unless the veto word is set or the loss is not finite; else *active = 0 (rt_finish_step)."""
     _req(loss, torch.float32, "loss")
-    _check(lib().rt_finish_step(_p(step_dev), _p(active), _p(veto), _p(loss), _stream()), "rt_finish_step")
-
-
-RT_STATS_MAX = 40
-
-
-class FinishDesc(Structure):
-    _fields_ = [("step", c_void_p), ("active", c_void_p), ("cond", c_void_p), ("loss", c_void_p),
-                ("sq", c_void_p), ("norm_scale", c_float), ("grad_norm", c_void_p),
-                ("src", c_void_p * RT_STATS_MAX), ("n_src", c_int), ("cond_in_stats", c_int), ("stats", c_void_p)]
+    _call("rt_finish_step", step_dev, active, veto, loss)
 
 
 def finish_stats(step_dev, active, veto, loss, sq, norm_scale, grad_norm, srcs=(), cond_in_stats=False, stats=None):
     """rt_finish_stats: the iteration's counters (as finish_step), grad_norm = sqrt(sq) * norm_scale and the stats vector
     [*srcs | float(veto word) | grad_norm] in one launch.  `srcs`: fp32 device scalars (tensors of one element)."""
-    assert len(srcs) <= RT_STATS_MAX
+    assert len(srcs) <= STATS_MAX
     for t in list(srcs) + [loss, sq, grad_norm, stats]:
         _req(t, torch.float32, "finish_stats operand")
-    d = FinishDesc()
-    d.step, d.active, d.cond, d.loss = _p(step_dev), _p(active), _p(veto), _p(loss)
-    d.sq, d.norm_scale, d.grad_norm = _p(sq), float(norm_scale), _p(grad_norm)
-    for i, t in enumerate(srcs):
-        d.src[i] = _p(t)
-    d.n_src, d.cond_in_stats, d.stats = len(srcs), int(bool(cond_in_stats)), _p(stats)
     if stats is not None:
         assert stats.numel() == len(srcs) + int(bool(cond_in_stats)) + 1
-    _check(lib().rt_finish_stats(ctypes.byref(d), _stream()), "rt_finish_stats")
+    _call("rt_finish_stats", _desc(FinishDesc, step=step_dev, active=active, cond=veto, loss=loss, sq=sq, norm_scale=float(norm_scale),
+                                   grad_norm=grad_norm, src=list(srcs), n_src=len(srcs), cond_in_stats=int(bool(cond_in_stats)), stats=stats))
 
 
 def stamp(buf, idx):
     """buf[idx] (int64 device tensor) = the device's 100 MHz wall clock when the current stream gets here (rt_stamp)."""
     assert buf.dtype == torch.int64 and 0 <= idx < buf.numel()
-    _check(lib().rt_stamp(_p(buf), idx, _stream()), "rt_stamp")
+    _call("rt_stamp", buf, idx)
 
 
 # Measurement aid (tools/concurrent_timeline.py): wall-clock stamps at named points of a step, on whatever stream reaches them.
@@ -1487,7 +1446,7 @@ def decoder_supported(F=2048):
 
 
 def decoder_set_spin(spin):
-    _check(lib().rt_decoder_set_spin(int(spin)), "rt_decoder_set_spin")
+    _call("rt_decoder_set_spin", int(spin), stream=False)
 
 
 class WgradBatch:
@@ -1531,12 +1490,11 @@ class WgradBatch:
             ws = WgradBatch._WS[key] = torch.empty(self.ws_bytes // 4, dtype=torch.float32, device=dev)
         single = _wgrad_workspace(dev)          # for the descriptors that are forwarded to rt_conv_wgrad (this stream's)
         for d in self.descs:
-            d.workspace, d.workspace_bytes = _p(single), WGRAD_WS_BYTES
+            _set(d, workspace=single, workspace_bytes=WGRAD_WS_BYTES)
         arr = (ConvWgradDesc * len(self.descs))(*self.descs)
         n = len(self.descs)
         _timed("conv_wgrad_grouped", self.flops,
-               lambda: _check(lib().rt_conv_wgrad_grouped(arr, n, _p(ws), self.ws_bytes, _stream()), "rt_conv_wgrad_grouped"),
-               nbytes=self.nbytes)
+               lambda: _call("rt_conv_wgrad_grouped", arr, n, ws, self.ws_bytes), nbytes=self.nbytes)
         self.descs, self.keep = [], []
         self.flops = self.nbytes = 0.0
 
@@ -1554,7 +1512,8 @@ class SmallWgradBatch:
         M, N = dy.shape
         K = x.shape[1]
         assert M <= 16 and x.shape[0] == M and dw.numel() == N * K and K % 4 == 0
-        self.jobs.append(SmallWgradJob(_p(dy), _p(x), _p(dw), _p(dbias), M, N, K, int(bool(overwrite)), _sqacc(dw), _g16(dw)))
+        self.jobs.append(_desc(SmallWgradJob, dy=dy, x=x, dw=dw, dbias=dbias, M=M, N=N, K=K, overwrite=int(bool(overwrite)),
+                               sqacc=_sqacc(dw), g16=_g16(dw)))
         self.keep.append((dy, x))
         self.flops += 2.0 * M * N * K; self.nbytes += 2.0 * M * (N + K) + 4.0 * N * K
 
@@ -1563,8 +1522,7 @@ class SmallWgradBatch:
             return
         arr = (SmallWgradJob * len(self.jobs))(*self.jobs)
         n = len(self.jobs)
-        _timed("small_wgrad_grouped", self.flops,
-               lambda: _check(lib().rt_small_wgrad_grouped(arr, n, _stream()), "rt_small_wgrad_grouped"), nbytes=self.nbytes)
+        _timed("small_wgrad_grouped", self.flops, lambda: _call("rt_small_wgrad_grouped", arr, n), nbytes=self.nbytes)
         self.jobs, self.keep = [], []
         self.flops = self.nbytes = 0.0
 
@@ -1588,7 +1546,7 @@ class WeightPrepBatch:
             return
         if self.table is None:
             self.table = torch.tensor(self.jobs, dtype=torch.int64).to(self.device)
-        _check(lib().rt_weight_prep_batched(_p(self.table), len(self.jobs), self.tiles, _stream()), "rt_weight_prep_batched")
+        _call("rt_weight_prep_batched", self.table, len(self.jobs), self.tiles)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1605,8 +1563,8 @@ def gn_nhwc_fwd(x, gamma, beta, B, HW, C, G=8, ldy=None, act=ACT_RELU, eps=1e-5)
     ppb = max(1, (4096 + C - 1) // C)          # rt_gn_nhwc_fwd cuts the pixels the same way
     nblk = (HW + ppb - 1) // ppb
     partials = torch.empty((B, nblk, G, 2), dtype=torch.float32, device=x.device)
-    d = GnNhwcDesc(_p(x), _p(gamma), _p(beta), _p(stats), _p(y), B, HW, C, G, ldx, ldy, act, eps, _p(partials), nblk)
-    _check(lib().rt_gn_nhwc_fwd(ctypes.byref(d), _stream()), "rt_gn_nhwc_fwd")
+    _call("rt_gn_nhwc_fwd", _desc(GnNhwcDesc, x=x, gamma=gamma, beta=beta, stats=stats, y_bf16=y, B=B, HW=HW, C=C, G=G, ldx=ldx, ldy=ldy,
+                                  act=act, eps=eps, partials=partials, partial_blocks=nblk))
     return y, stats
 
 
@@ -1617,9 +1575,8 @@ def gn_nhwc_bwd(dy, x, gamma, beta, stats, dgamma, dbeta, B, HW, C, G=8, lddx=No
     lddx = lddx or ldx
     dx = torch.empty((B * HW, lddx), dtype=torch.bfloat16, device=x.device)
     bst = torch.empty((B, G, 2), dtype=torch.float32, device=x.device)
-    d = GnNhwcBwdDesc(_p(dy), _p(x), _p(gamma), _p(beta), _p(stats), _p(bst), _p(dx), _p(dgamma), _p(dbeta),
-                      B, HW, C, G, ldx, lddy, lddx, act, eps)
-    _check(lib().rt_gn_nhwc_bwd(ctypes.byref(d), _stream()), "rt_gn_nhwc_bwd")
+    _call("rt_gn_nhwc_bwd", _desc(GnNhwcBwdDesc, dy=dy, x=x, gamma=gamma, beta=beta, stats=stats, bstats=bst, dx_bf16=dx, dgamma=dgamma,
+                                  dbeta=dbeta, B=B, HW=HW, C=C, G=G, ldx=ldx, lddy=lddy, lddx=lddx, act=act, eps=eps))
     return dx
 
 
@@ -1629,8 +1586,7 @@ def upsample_add(fpn, a, B, H, W, h, w, C, ldo=None):
     ldf, lda = fpn.shape[-1], a.shape[-1]
     ldo = ldo or ldf
     out = torch.empty((B * H * W, ldo), dtype=torch.bfloat16, device=fpn.device)
-    d = UpsampleAddDesc(_p(fpn), _p(a), _p(out), B, H, W, h, w, C, ldf, lda, ldo)
-    _check(lib().rt_upsample_add(ctypes.byref(d), _stream()), "rt_upsample_add")
+    _call("rt_upsample_add", _desc(UpsampleAddDesc, fpn=fpn, a_bf16=a, out_bf16=out, B=B, H=H, W=W, h=h, w=w, C=C, ldf=ldf, lda=lda, ldo=ldo))
     return out
 
 
@@ -1642,17 +1598,17 @@ def upsample_add_bwd(dy, B, H, W, h, w, C, ldda=None, lddyb=None):
     da = torch.zeros((B * h * w, ldda), dtype=torch.float32, device=dy.device) if ldda > C else \
         torch.empty((B * h * w, ldda), dtype=torch.float32, device=dy.device)
     dyb = torch.empty((B * H * W, lddyb), dtype=torch.bfloat16, device=dy.device)
-    d = UpsampleAddBwdDesc(_p(dy), _p(da), _p(dyb), B, H, W, h, w, C, lddy, ldda, lddyb)
-    _check(lib().rt_upsample_add_bwd(ctypes.byref(d), _stream()), "rt_upsample_add_bwd")
+    _call("rt_upsample_add_bwd", _desc(UpsampleAddBwdDesc, dy=dy, da=da, dy_bf16=dyb, B=B, H=H, W=W, h=h, w=w, C=C, lddy=lddy, ldda=ldda,
+                                       lddyb=lddyb))
     return da, dyb
 
 
 def attn_map_fwd(q, k, mask_u8, B, HW, E, nh, k_rows_per_img, k_row_off, concat=None, concat_col=0):
     _req(q, torch.float32, "q"); _req(k, torch.float32, "k"); _req(mask_u8, torch.uint8, "mask")
     P = torch.empty((B, nh, HW), dtype=torch.float32, device=q.device)
-    d = AttnMapDesc(_p(q), _p(k), _p(mask_u8), _p(P), _p(concat), B, HW, E, nh, k.shape[-1], k_rows_per_img, k_row_off,
-                    concat.shape[-1] if concat is not None else 0, concat_col, float(E / nh) ** -0.5)
-    _check(lib().rt_attn_map_fwd(ctypes.byref(d), _stream()), "rt_attn_map_fwd")
+    _call("rt_attn_map_fwd", _desc(
+        AttnMapDesc, q=q, k=k, mask=mask_u8, P=P, concat_bf16=concat, B=B, HW=HW, E=E, nh=nh, ldk=k.shape[-1], k_rows_per_img=k_rows_per_img,
+        k_row_off=k_row_off, ld_concat=concat.shape[-1] if concat is not None else 0, concat_col=concat_col, norm=float(E / nh) ** -0.5))
     return P
 
 
@@ -1661,40 +1617,36 @@ def attn_map_bwd(q, k, P, dconcat, B, HW, E, nh, k_rows_per_img, k_row_off, conc
     _req(dconcat, torch.float32, "dconcat")
     dq = torch.empty((B, E), dtype=torch.float32, device=q.device)
     dk = torch.zeros_like(k)
-    d = AttnMapBwdDesc(_p(q), _p(k), _p(P), _p(dconcat), _p(dq), _p(dk), B, HW, E, nh, k.shape[-1], k_rows_per_img,
-                       k_row_off, dconcat.shape[-1], concat_col, float(E / nh) ** -0.5)
-    _check(lib().rt_attn_map_bwd(ctypes.byref(d), _stream()), "rt_attn_map_bwd")
+    _call("rt_attn_map_bwd", _desc(
+        AttnMapBwdDesc, q=q, k=k, P=P, dconcat=dconcat, dq=dq, dk=dk, B=B, HW=HW, E=E, nh=nh, ldk=k.shape[-1], k_rows_per_img=k_rows_per_img,
+        k_row_off=k_row_off, ld_dconcat=dconcat.shape[-1], concat_col=concat_col, norm=float(E / nh) ** -0.5))
     return dq, dk
 
 
 def seg_concat(src, mem, out, B, HW, E, nh, rows_per_img, row_off, src_dense=False):
     """src / mem rows of image b, pixel p: (b * rows_per_img + row_off + p); src_dense: src is a dense [B*HW, E]."""
     _req(src, torch.float32, "src"); _req(mem, torch.float32, "mem"); _req(out, torch.bfloat16, "out")
-    d = SegConcatDesc(_p(src), _p(mem), _p(out), B, HW, E, nh, out.shape[-1], rows_per_img, row_off,
-                      HW if src_dense else rows_per_img, 0 if src_dense else row_off)
-    _check(lib().rt_seg_concat(ctypes.byref(d), _stream()), "rt_seg_concat")
+    _call("rt_seg_concat", _desc(
+        SegConcatDesc, src=src, mem=mem, out_bf16=out, B=B, HW=HW, E=E, nh=nh, ldo=out.shape[-1], mem_rows_per_img=rows_per_img,
+        mem_row_off=row_off, src_rows_per_img=HW if src_dense else rows_per_img, src_row_off=0 if src_dense else row_off))
     return out
-
-
-MASK_LOSS_PARTIALS = 1024
 
 
 def mask_loss(pred, target_u8, B, h, w, Ht, Wt, ldp, norm, sums=None, dpred=None, g_focal=None, g_dice=None):
     """Forward (dpred None): returns (losses[2] = {focal, dice}, sums [B,4]).  Backward: accumulates into dpred."""
     _req(pred, torch.float32, "pred"); _req(target_u8, torch.uint8, "target")
     assert target_u8.numel() == B * Ht * Wt
+    common = dict(pred=pred, target=target_u8, B=B, h=h, w=w, Ht=Ht, Wt=Wt, ldp=ldp, inv_norm=1.0 / norm)
     if dpred is None:
         sums = torch.empty((B, 4), dtype=torch.float32, device=pred.device)
         losses = torch.empty(2, dtype=torch.float32, device=pred.device)
         partials = torch.empty((B, MASK_LOSS_PARTIALS), dtype=torch.float32, device=pred.device)      # fixed-order sums: no atomics
-        d = MaskLossDesc(_p(pred), _p(target_u8), _p(sums), _p(losses), None, None, None, B, h, w, Ht, Wt, ldp, 0, 1.0 / norm, _p(partials))
-        _check(lib().rt_mask_loss(ctypes.byref(d), _stream()), "rt_mask_loss")
+        _call("rt_mask_loss", _desc(MaskLossDesc, sums=sums, losses=losses, gbuf=partials, **common))
         return losses, sums
     _req(dpred, torch.float32, "dpred"); _req(g_focal, torch.float32, "g_focal"); _req(g_dice, torch.float32, "g_dice")
     gbuf = torch.empty(B * Ht * Wt, dtype=torch.float32, device=pred.device)
-    d = MaskLossDesc(_p(pred), _p(target_u8), _p(sums), None, _p(dpred), _p(g_focal), _p(g_dice), B, h, w, Ht, Wt, ldp,
-                     dpred.shape[-1], 1.0 / norm, _p(gbuf))
-    _check(lib().rt_mask_loss(ctypes.byref(d), _stream()), "rt_mask_loss")
+    _call("rt_mask_loss", _desc(MaskLossDesc, sums=sums, dpred=dpred, g_focal=g_focal, g_dice=g_dice, lddp=dpred.shape[-1], gbuf=gbuf,
+                                **common))
     return dpred
 
 
@@ -1707,8 +1659,7 @@ def resample_u8(src, bounds, coeffs, out_len, axis):
     n0, n1, C = src.shape
     shape = (out_len, n1, C) if axis == 0 else (n0, out_len, C)
     dst = torch.empty(shape, dtype=torch.uint8, device=src.device)
-    _check(lib().rt_resample_u8(_p(src), _p(dst), _p(bounds), _p(coeffs), n0, n1, C, out_len, coeffs.shape[1], axis, _stream()),
-           "rt_resample_u8")
+    _call("rt_resample_u8", src, dst, bounds, coeffs, n0, n1, C, out_len, coeffs.shape[1], axis)
     return dst
 
 
@@ -1723,11 +1674,8 @@ def img_collate_norm(images, H, W, mean, std):
     out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
     mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     m = (c_float * 3)(*[float(v) for v in mean]); s_ = (c_float * 3)(*[float(v) for v in std])
-    _check(lib().rt_img_collate_norm(_p(tab), _p(out), _p(mask), B, H, W, m, s_, _stream()), "rt_img_collate_norm")
+    _call("rt_img_collate_norm", tab, out, mask, B, H, W, m, s_)
     return out, mask
-
-
-BATCH_STAGE_MAX_B = 64          # RT_BATCH_STAGE_MAX_B: what fits the kernel's argument block
 
 
 def batch_stage(src_img, src_mask, img, mask, box_list, boxes_per_image, boxes, tgt_off, num_boxes, mask_list=None, tgt_masks=None):
@@ -1747,17 +1695,16 @@ def batch_stage(src_img, src_mask, img, mask, box_list, boxes_per_image, boxes, 
     for t in box_list:
         assert t.numel() == 0 or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4)
     bp = (c_void_p * B)(*[t.data_ptr() if t.numel() else None for t in box_list])
-    bn = (ctypes.c_int32 * B)(*[t.shape[0] for t in box_list])
+    bn = (c_int32 * B)(*[t.shape[0] for t in box_list])
     tp = thw = None
     if mask_list is not None:
         assert len(mask_list) == B and tgt_masks is not None and tgt_masks.numel() == B * Hc * Wc and tgt_masks.element_size() == 1
         for t in mask_list:
             assert t.is_cuda and t.element_size() == 1 and t.is_contiguous() and t.numel() == t.shape[-2] * t.shape[-1]
         tp = (c_void_p * B)(*[t.data_ptr() for t in mask_list])
-        thw = (ctypes.c_int32 * (2 * B))(*[v for t in mask_list for v in t.shape[-2:]])
-    _check(lib().rt_batch_stage(_p(src_img), _p(src_mask), B, hs, ws, _p(img), _p(mask), Hc, Wc, bp, bn, int(boxes_per_image), _p(boxes),
-                                _p(tgt_off), _p(num_boxes), tp, thw, _p(tgt_masks) if mask_list is not None else None, _stream()),
-           "rt_batch_stage")
+        thw = (c_int32 * (2 * B))(*[v for t in mask_list for v in t.shape[-2:]])
+    _call("rt_batch_stage", src_img, src_mask, B, hs, ws, img, mask, Hc, Wc, bp, bn, int(boxes_per_image), boxes, tgt_off, num_boxes, tp, thw,
+          tgt_masks if mask_list is not None else None)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1770,13 +1717,13 @@ class Comm:
     @staticmethod
     def unique_id():
         buf = ctypes.create_string_buffer(128)
-        _check(lib().rt_comm_unique_id(buf), "rt_comm_unique_id")
+        _call("rt_comm_unique_id", buf, stream=False)
         return bytes(buf.raw)
 
     def __init__(self, uid, rank, world):
         assert len(uid) == 128
         h = c_void_p()
-        _check(lib().rt_comm_init(ctypes.create_string_buffer(uid, 128), int(rank), int(world), ctypes.byref(h)), "rt_comm_init")
+        _call("rt_comm_init", ctypes.create_string_buffer(uid, 128), int(rank), int(world), ctypes.byref(h), stream=False)
         self.handle, self.rank, self.world = h, rank, world
 
     def allreduce(self, tensors, stream=None):
@@ -1789,13 +1736,13 @@ class Comm:
         assert dt in (torch.float32, torch.bfloat16) and all(t.dtype == dt and t.is_cuda and t.is_contiguous() for t in tensors)
         n = len(tensors)
         ptrs = (c_void_p * n)(*[t.data_ptr() for t in tensors])
-        cnts = (ctypes.c_int64 * n)(*[t.numel() for t in tensors])
+        cnts = (c_int64 * n)(*[t.numel() for t in tensors])
         s = stream.cuda_stream if stream is not None else _stream()
-        _check(lib().rt_comm_allreduce(self.handle, ptrs, cnts, n, 0 if dt == torch.float32 else 1, s), "rt_comm_allreduce")
+        _call("rt_comm_allreduce", self.handle, ptrs, cnts, n, 0 if dt == torch.float32 else 1, s, stream=False)
 
     def destroy(self):
         if self.handle:
-            _check(lib().rt_comm_destroy(self.handle), "rt_comm_destroy")
+            _call("rt_comm_destroy", self.handle, stream=False)
             self.handle = None
 
 

@@ -591,8 +591,8 @@ class Net:
             self._wgrad_only(p + "self_attn.out_proj.", d16[3], r["o"])
             self._wgrad_only(p + "self_attn.v", d16[4], r["t16"])
             for j, nm in ((2, "norm3."), (1, "norm2."), (0, "norm1.")):
-                self.ln_batch.jobs.append(H.LnPgJob(parts[j].data_ptr(), self.G(p + nm + "weight").data_ptr(),
-                                                    self.G(p + nm + "bias").data_ptr(), nb, E))
+                self.ln_batch.jobs.append(H._desc(H.LnPgJob, partials=parts[j], dgamma=self.G(p + nm + "weight"),
+                                                  dbeta=self.G(p + nm + "bias"), n_blocks=nb, D=E))
                 self.ln_batch.keep.append(parts[j])
         if pack:
             # d memory += [dV_0 | dV_1 | ...] [Wv_0^T | Wv_1^T | ...]^T (and K with memory + pos): one launch, K = layers x 256, instead

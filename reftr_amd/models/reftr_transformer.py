@@ -697,7 +697,8 @@ class RefTR(nn.Module):
         net._wgrad_only(qe + "linear2.", o["dqs16"], sv["lang16"])
         net._wgrad_only(qe + "linear3.", o["dvs16"], sv["lang16"])
         for i, pfx in enumerate(("fuse_encoder_query.5.", "fuse_encoder_query.1.", "context_out.1.")):
-            net.ln_batch.jobs.append(H.LnPgJob(H._p(parts[i]), H._p(st.G[qe + pfx + "weight"]), H._p(st.G[qe + pfx + "bias"]), B, E))
+            net.ln_batch.jobs.append(H._desc(H.LnPgJob, partials=parts[i], dgamma=st.G[qe + pfx + "weight"], dbeta=st.G[qe + pfx + "bias"],
+                                             n_blocks=B, D=E))
         net.ln_batch.keep.append(parts)
         return o["dcat"]
 
@@ -802,11 +803,11 @@ class RefTR(nn.Module):
             net.big_wg.add(head["dl16"], sv["y2"], l2.gw, None, overwrite=st.claim(l2.gw))
             net._wgrad_only("bbox_embed.layers.1.", head["dy2"], sv["y1"])
             net._wgrad_only("bbox_embed.layers.0.", head["dy1"], sv["hs16"])
-            net.ln_batch.jobs.append(H.LnPgJob(H._p(head["part_n"]), H._p(st.G[vt + "decoder.norm.weight"]),
-                                               H._p(st.G[vt + "decoder.norm.bias"]), NL, E))
+            net.ln_batch.jobs.append(H._desc(H.LnPgJob, partials=head["part_n"], dgamma=st.G[vt + "decoder.norm.weight"],
+                                             dbeta=st.G[vt + "decoder.norm.bias"], n_blocks=NL, D=E))
             # the last Linear's bias gradient: the launch ran BEFORE the gradient clear (it sits in the forward), so it left per-layer
             # partial sums and the grouped reduction adds them to the bias gradient like a LayerNorm's d gamma
-            net.ln_batch.jobs.append(H.LnPgJob(H._p(head["db2_part"]), H._p(l2.gb), None, NL, 4))
+            net.ln_batch.jobs.append(H._desc(H.LnPgJob, partials=head["db2_part"], dgamma=l2.gb, n_blocks=NL, D=4))
             net.ln_batch.keep.append((head["part_n"], head["db2_part"]))
             dhs = None
         else:

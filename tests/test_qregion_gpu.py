@@ -254,8 +254,9 @@ def test_head_loss_one_launch_equals_the_launched_head(hip, B, Pn):
     h = model._head_loss_fused((crit, prepared), t3, hs16f, valid, NL, B, Pn, nq, N)
     net._wgrad_only("bbox_embed.layers.1.", h["dy2"], h["y1"])
     net._wgrad_only("bbox_embed.layers.0.", h["dy1"], hs16f)
-    net.ln_batch.jobs.append(hip.LnPgJob(hip._p(h["part_n"]), hip._p(st.G[vt + "decoder.norm.weight"]), hip._p(st.G[vt + "decoder.norm.bias"]), NL, E))
-    net.ln_batch.jobs.append(hip.LnPgJob(hip._p(h["db2_part"]), hip._p(net.lins["bbox_embed.layers.2."].gb), None, NL, 4))
+    net.ln_batch.jobs.append(hip._desc(hip.LnPgJob, partials=h["part_n"], dgamma=st.G[vt + "decoder.norm.weight"],
+                                       dbeta=st.G[vt + "decoder.norm.bias"], n_blocks=NL, D=E))
+    net.ln_batch.jobs.append(hip._desc(hip.LnPgJob, partials=h["db2_part"], dgamma=net.lins["bbox_embed.layers.2."].gb, n_blocks=NL, D=4))
     net.flush_wgrads()
     torch.cuda.synchronize()
     gf = {n: st.G[n].clone() for n in gref}
