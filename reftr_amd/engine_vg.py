@@ -13,8 +13,10 @@ import sys
 
 import torch
 
+from . import hip as H
+from .metrics import EvalMeter, decode_ring
 from .util import misc as utils
-from .util.box_ops import box_cxcywh_to_xyxy, box_iou
+from .util.box_ops import box_cxcywh_to_xyxy, box_iou, mask_iou
 
 
 def _to_device(samples, targets, device, non_blocking=True):
@@ -178,6 +180,19 @@ def _coop_fallback(model):
               "is discarded and run again; the decoder uses the launched chain (REFTR_DEC_COOP=0) from here on.", file=sys.stderr)
 
 
+def _run_again_on_chain(model, run, drop=None):
+    """run(); when a cooperative decoder hand-off timed out in it, what it produced is void: the launches are switched off
+    (_coop_fallback), the caller drops what it must (`drop`: captures that contain the launches, an advanced dropout seed) and run()
+    is called once more, on the launched chain -- at most once, its result is not asked again.  Returns the result that stands."""
+    out = run()
+    if _cooperative_failed(model):
+        _coop_fallback(model)
+        if drop is not None:
+            drop()
+        out = run()
+    return out
+
+
 def _require_accumulation(optimizer):
     """accum_steps > 1 needs the fused optimizer's accumulator, on a single-process fp32 gradient buffer."""
     if not hasattr(optimizer, "finish_accumulation"):
@@ -284,14 +299,11 @@ def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None,
         _require_accumulation(optimizer)
     if hasattr(optimizer, "veto") and hasattr(_inner(model), "coop_failure_word"):
         optimizer.veto = _inner(model).coop_failure_word()
-    res = _eager_iteration(model, criterion, samples, targets, optimizer)
-    if _cooperative_failed(model):
-        # a stage hand-off of the cooperative decoder launches timed out: this iteration's activations / gradients are void.
-        # The reference stops BEFORE the update when an iteration is bad (engine_vg.py:55-58); here the launches are switched
-        # off for the process and the iteration is run again on the launched chain (same dropout seeds), then updated as usual
-        _coop_fallback(model)
-        _restore_seed(model, _seed_state(model))
-        res = _eager_iteration(model, criterion, samples, targets, optimizer)
+    # a stage hand-off of the cooperative decoder launches that timed out voids this iteration's activations / gradients.  The
+    # reference stops BEFORE the update when an iteration is bad (engine_vg.py:55-58); here the launches are switched off for the
+    # process and the iteration is run again on the launched chain (same dropout seeds), then updated as usual
+    res = _run_again_on_chain(model, lambda: _eager_iteration(model, criterion, samples, targets, optimizer),
+                              drop=lambda: _restore_seed(model, _seed_state(model)))
     last = _window_last(optimizer, accum_steps, window_end) if accum_steps > 1 else None
     return (*res, _update(model, optimizer, lr_scheduler, max_norm, last))
 
@@ -1218,28 +1230,37 @@ class CapturedForward:
                 out = self.model(s)
             ent = self.graphs[key] = (g, s, out)
         g, s, out = ent
-        inner = _inner(self.model)
-        if inner._flush_pending is not None:
-            inner._flush_pending()
-        if inner._operands_dirty:                    # weights changed since the capture: rebuild the bf16 operands eagerly
-            inner.refresh_operands()
-            if inner._lin_refresh_pending:
-                inner.net.refresh(); inner._lin_refresh_pending = False
+        _before_forward_replay(_inner(self.model))
         _copy_batch(s, [], samples, [])
         g.replay()
         return out
 
 
-def _loss_vector(red, weight_dict, wvec):
-    """One iteration's loss meters as ONE device vector, [unscaled..., scaled..., total] (no .item() per loss).  wvec: the (names,
-    weights on the device) of the previous call or None; returned renewed when the names changed."""
-    names = sorted(red)
-    wn = [k for k in names if k in weight_dict]
-    if wvec is None or wvec[0] != names:
-        wvec = (names, torch.tensor([weight_dict[k] for k in wn], dtype=torch.float32, device=red[names[0]].device))
-    un = torch.stack([red[k].reshape(()).float() for k in names])
-    sc = torch.stack([red[k].reshape(()).float() for k in wn]) * wvec[1]
-    return [_UNSCALED(k) for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]), wvec
+def _before_forward_replay(inner):
+    """Before a captured forward is replayed: a pending deferred update is applied and dirty operands are rebuilt (the graph has no refresh)."""
+    if inner._flush_pending is not None:
+        inner._flush_pending()
+    if inner._operands_dirty:
+        inner.refresh_now()
+
+
+class _ForwardLosses:
+    """fwd(samples) -> criterion -> utils.reduce_dict -> one iteration's loss meters as ONE device vector, [unscaled..., scaled...,
+    total] (no .item() per loss): (outputs, names, vector).  Keeps the weights on the device, renewed when the loss names change."""
+
+    def __init__(self, fwd, criterion):
+        self.fwd, self.criterion, self._wvec = fwd, criterion, None
+
+    def __call__(self, samples, targets):
+        outputs = self.fwd(samples)
+        red, weight_dict = utils.reduce_dict(self.criterion(outputs, targets)), self.criterion.weight_dict
+        names = sorted(red)
+        wn = [k for k in names if k in weight_dict]
+        if self._wvec is None or self._wvec[0] != names:
+            self._wvec = (names, torch.tensor([weight_dict[k] for k in wn], dtype=torch.float32, device=red[names[0]].device))
+        un = torch.stack([red[k].reshape(()).float() for k in names])
+        sc = torch.stack([red[k].reshape(()).float() for k in wn]) * self._wvec[1]
+        return outputs, [_UNSCALED(k) for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)])
 
 
 class CapturedEvalStep:
@@ -1250,9 +1271,8 @@ class CapturedEvalStep:
     Per batch the host issues rt_batch_stage, rt_eval_facts and the grouped token copy and replays; nothing is copied back.
 
     The cooperative decoder's fail-safe: the graph's metric launch takes the decoder's failure word as its veto, so the device tests
-    the flag BEFORE the batch's results are kept -- a batch whose hand-off timed out leaves totals, ring and cursor untouched.
-    evaluate() then reads the word as it does on every path (one 4-byte read per batch, only while cooperative launches are in use),
-    drops the captures, and runs the batch again on the launched chain: it is counted once."""
+    the flag BEFORE the batch's results are kept -- a batch whose hand-off timed out leaves totals, ring and cursor untouched; the
+    host reads the word as on every path (one 4-byte read per batch, only while cooperative launches are in use: _CanvasEval)."""
 
     def __init__(self, model, criterion, postprocessors, canvas, samples, targets, acc, slots, state=None):
         self.model, self.criterion, self.canvas, self.inner = model, criterion, canvas, _inner(model)
@@ -1266,13 +1286,12 @@ class CapturedEvalStep:
         self.facts = torch.zeros((B, 6), dtype=torch.int32, device=dev)
         self.image_ids = torch.zeros(B, dtype=torch.int64, device=dev)
         self._gather_facts(targets)
-        self._wvec = None
+        self.losses = _ForwardLosses(model, criterion)       # held with the graph: the replay reads the weight vector it keeps
         self._gen = _state(model).coop_generation    # a cooperative fall-back anywhere drops this capture: it contains the launches
         with self._building():
             warm = []
-            _warm_up(lambda: warm.append(self._forward_losses()), 1)
+            _warm_up(lambda: warm.append(self.losses(self.s, self.t)), 1)
             P = int(warm[0][0]["pred_boxes"].shape[1])
-            from . import hip as H
             self.state = state if state is not None else H.EvalCanvasState(slots, B, P, dev, acc=acc)
             assert self.state.B == B and self.state.P == P
             # read after the warm-up: the hand-off buffer exists by now (None: no cooperative launches in this configuration)
@@ -1280,7 +1299,7 @@ class CapturedEvalStep:
             del warm
             self.graph = torch.cuda.CUDAGraph()
             with _capture(self.graph):
-                outputs, self.names, self.vec = self._forward_losses()
+                outputs, self.names, self.vec = self.losses(self.s, self.t)
                 self.last = self._tail(outputs)
             self.outputs = outputs
 
@@ -1294,19 +1313,12 @@ class CapturedEvalStep:
             crit.targets_static = crit.target_masks_static = None
 
     def _gather_facts(self, targets):
-        from . import hip as H
         origs = [t["orig_size"] for t in targets] if "orig_size" in targets[0] else None
         ids = [t["image_id"] for t in targets] if "image_id" in targets[0] else None
         hw = [tuple(t["masks"].shape[-2:]) for t in targets] if self.segm is not None else None
         H.eval_facts([t["size"] for t in targets], self.facts, self.image_ids, origs=origs, ids=ids, mask_hw=hw)
 
-    def _forward_losses(self):
-        outputs = self.model(self.s)
-        names, vec, self._wvec = _loss_vector(utils.reduce_dict(self.criterion(outputs, self.t)), self.criterion.weight_dict, self._wvec)
-        return outputs, names, vec
-
     def _tail(self, outputs):
-        from . import hip as H
         boxes = outputs["pred_boxes"]
         B, P, K, _ = boxes.shape
         pm = None
@@ -1322,13 +1334,7 @@ class CapturedEvalStep:
     @torch.no_grad()
     def __call__(self, samples, targets):
         """Stages the batch, replays, and returns the loss meters' (names, device vector) -- a static buffer the next replay rewrites."""
-        inner = self.inner
-        if inner._flush_pending is not None:
-            inner._flush_pending()
-        if inner._operands_dirty:                    # weights changed since the capture: rebuild the bf16 operands eagerly
-            inner.refresh_operands()
-            if inner._lin_refresh_pending:
-                inner.net.refresh(); inner._lin_refresh_pending = False
+        _before_forward_replay(self.inner)
         self.canvas.stage(samples, targets, out=self.staged, tokens=False)
         self._gather_facts(targets)
         _copy_batch(self.s, [], {k: v for k, v in samples.items() if k != "img"}, [])
@@ -1336,32 +1342,34 @@ class CapturedEvalStep:
         return self.names, self.vec
 
 
-def _eval_canvas_active(model, criterion, postprocessors, device, visualize, canvas):
-    """Whether evaluate() runs its batches through `canvas`.  Refuses what a canvas evaluation cannot do -- before anything is
-    launched -- and says once why it ignores the canvas where the loop it would replace is switched off or not this package's."""
-    if canvas is None:
-        return False
-    if _multi_rank():
-        raise NotImplementedError("evaluate(canvas=) is not available on more than one rank: the box count the criterion normalises by "
-                                  "is averaged over the ranks, and the count a canvas batch stages is this rank's")
-    if visualize:
-        raise NotImplementedError("evaluate(canvas=, visualize=True): the dumps need per-image masks_origin views, which a canvas "
-                                  "evaluation never materialises")
-    why = None
-    if os.environ.get("REFTR_EVAL_GRAPH", "1") != "1":
-        why = "REFTR_EVAL_GRAPH=0"
-    elif os.environ.get("REFTR_EVAL_METRICS", "1") != "1":
-        why = "REFTR_EVAL_METRICS=0"
-    elif torch.device(device).type != "cuda":
-        why = "a CPU device"
-    elif not _metered(postprocessors, device):
-        why = "a post-processor that is not this package's"
-    elif not hasattr(criterion, "targets_static"):
-        why = "a criterion without targets_static"
-    if why is not None:
-        _say_once(model, ("eval-canvas", why), f"[reftr_amd] evaluate: {canvas!r} is ignored ({why}); every batch runs at its own shape")
-        return False
-    return True
+class _EvalPlan:
+    """What decides how evaluate() runs its batches, read ONCE: the two environment switches, the device type, whether the
+    post-processors are this package's (the meter reads PostProcessSegm's frame) and whether the criterion reads staged targets.
+    replayed: the forward from a hipGraph per input shape; metered: scored on the device; on_canvas: through `canvas` -- refused before
+    anything is launched where that cannot be done, ignored (said once) where the loop it would replace is off or not this package's."""
+
+    def __init__(self, model, criterion, postprocessors, device, visualize, canvas):
+        from .models.post_process import PostProcessSegm, PostProcessVGMultiPhrase
+        graph, metrics = (os.environ.get(k, "1") == "1" for k in ("REFTR_EVAL_GRAPH", "REFTR_EVAL_METRICS"))
+        cuda = torch.device(device).type == "cuda"
+        own_post = (isinstance(postprocessors["bbox"], PostProcessVGMultiPhrase)
+                    and isinstance(postprocessors.get("segm", PostProcessSegm()), PostProcessSegm))
+        self.replayed, self.metered, self.on_canvas = graph and cuda, metrics and cuda and own_post, False
+        if canvas is None:
+            return
+        if _multi_rank():
+            raise NotImplementedError("evaluate(canvas=) is not available on more than one rank: the box count the criterion normalises "
+                                      "by is averaged over the ranks, and the count a canvas batch stages is this rank's")
+        if visualize:
+            raise NotImplementedError("evaluate(canvas=, visualize=True): the dumps need per-image masks_origin views, which a canvas "
+                                      "evaluation never materialises")
+        reasons = (("REFTR_EVAL_GRAPH=0", not graph), ("REFTR_EVAL_METRICS=0", not metrics), ("a CPU device", not cuda),
+                   ("a post-processor that is not this package's", not own_post),
+                   ("a criterion without targets_static", not hasattr(criterion, "targets_static")))
+        why = next((text for text, holds in reasons if holds), None)               # the first that holds, in this order
+        if why is not None:
+            _say_once(model, ("eval-canvas", why), f"[reftr_amd] evaluate: {canvas!r} is ignored ({why}); every batch runs at its own shape")
+        self.on_canvas = why is None
 
 
 def _vis_dirs(output_dir, split):
@@ -1410,15 +1418,6 @@ def _dump_visuals(root, dataset, dataset_id, mask_origin, pred_box, mask_att):
             plt.imsave(root / "att" / f"{tag}_{head}.jpg", att[head, :h // 2, :w // 2], cmap="viridis")
 
 
-def _metered(postprocessors, device):
-    """evaluate() scores on the device (metrics.EvalMeter: two launches per batch, totals read back once) unless REFTR_EVAL_METRICS=0,
-    the device is a CPU, or a post-processor is not this package's (the meter reads PostProcessSegm's frame)."""
-    from .models.post_process import PostProcessSegm, PostProcessVGMultiPhrase
-    return (os.environ.get("REFTR_EVAL_METRICS", "1") == "1" and torch.device(device).type == "cuda"
-            and isinstance(postprocessors["bbox"], PostProcessVGMultiPhrase)
-            and isinstance(postprocessors.get("segm", PostProcessSegm()), PostProcessSegm))
-
-
 def _fill_results(results_dict, targets, results_scaled):
     """results_dict[image_id] = the image's scaled boxes as nested lists, from ONE device-to-host copy per batch for boxes and
     image ids together (float64 holds an fp32 box coordinate and an image id below 2^53 exactly)."""
@@ -1441,157 +1440,184 @@ def _fill_results(results_dict, targets, results_scaled):
         o += 4 * n
 
 
-@torch.no_grad()
-def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=None, visualize=False, canvas=None):
-    """engine_vg.evaluate (engine_vg.py:82-225): losses, Acc@0.5 / mean IoU of the predicted boxes (:127-140), mask IoU when a
-    'segm' post-processor is present (:143-152), boxes scaled to the original image size in the returned results dict (:141,203).
-    On a GPU the metrics are scored by metrics.EvalMeter (csrc/rt_eval.hip: one ABI call per batch, the running totals stay on the
-    device and are read back once), which adds 'seg_oiou' and 'seg_prec@0.5' ... '@0.9' for a RES model; REFTR_EVAL_METRICS=0 (or a
-    CPU device) runs the reference's per-image torch loop, without the new keys.
-    `visualize` (needs the 'segm' post-processor, `output_dir` and a dataset with `split` / `pull_item`, as in the reference):
-    per sample the predicted mask, the ground-truth mask, the image with both boxes and four attention maps under
-    output_dir/vis/<split>/{mask,gt,bbox,att} (:86-96,157-192).
-    canvas (reftr_amd.data.canvas.BatchCanvas): ragged validation data -- every batch that fits the canvas (why_not and why_not_eval)
-    is staged into canvas buffers and runs as one replay of one captured graph (CapturedEvalStep; one capture per batch size), with no
-    device-to-host copy per batch: totals and result boxes stay on the device and are read back once after the loop.  What such a batch
-    computes is defined in BatchCanvas' docstring.  A batch that does not fit takes the path below at its own shape (said once per
-    reason) and adds to the same totals and results, in loader order.  NotImplementedError on more than one rank and with
-    `visualize`; ignored (said once) with REFTR_EVAL_GRAPH=0, REFTR_EVAL_METRICS=0, a CPU device, a foreign post-processor or a
-    criterion without `targets_static`.  canvas=None: the loop below, unchanged."""
-    from .util.box_ops import mask_iou
-    on_canvas = _eval_canvas_active(model, criterion, postprocessors, device, visualize, canvas)
-    model.eval()
-    criterion.eval()
-    board = utils.StatBoard()
-    meter = None
-    if _metered(postprocessors, device):
-        from .metrics import EvalMeter
-        meter = EvalMeter(device, seg="segm" in postprocessors)
-    else:
-        sum_accu = torch.zeros((), device=device); sum_iou = torch.zeros((), device=device); cnt = torch.zeros((), device=device)
-        seg_iou = torch.zeros((), device=device); cnt_seg = 0.0
-    results_dict = {}
-    vis_dir = _vis_dirs(output_dir, data_loader.dataset.split) if visualize else None
-    prefetcher = data_prefetcher(data_loader, device, prefetch=True)
-    samples, targets = prefetcher.next()
-    # the forward is replayed from a hipGraph per input shape (fixed-size evaluation sets; bit-identical outputs; up to four
-    # shapes, then eager launches); REFTR_EVAL_GRAPH=0: always eager
-    fwd = CapturedForward(model) if (os.environ.get("REFTR_EVAL_GRAPH", "1") == "1" and torch.device(device).type == "cuda") else model
-    wvec = None
-    # canvas: captures by canvas key, their rings (which outlive a capture dropped by the cooperative fall-back), and what went where
-    steps, rings, order = {}, {}, []
-    if on_canvas:
-        meter.begin_external()
-    for batch_no in board.log_every(range(len(data_loader)), 50, "Test:"):
-        if on_canvas:
-            segm = "segm" in postprocessors
-            why = canvas.why_not(samples, targets) or canvas.why_not_eval(samples, targets, segm=segm)
-            if why is not None:
-                _say_once(model, ("eval-canvas", why), f"[reftr_amd] evaluate: a batch does not fit {canvas!r} ({why}): it runs at its "
-                          "own shape")
-            else:
-                key = canvas.key(samples)
-                if any(st._gen != _state(model).coop_generation for st in steps.values()):
-                    steps.clear()
-                for attempt in (0, 1):
-                    step = steps.get(key)
-                    if step is None:
-                        ring = rings.get(key)
-                        step = steps[key] = CapturedEvalStep(model, criterion, postprocessors, canvas, samples, targets, meter.acc,
-                                                             len(data_loader), state=ring[0] if ring else None)
-                        if ring is None:
-                            ring = rings[key] = (step.state, [])
-                    names, vec = step(samples, targets)
-                    if attempt or not _cooperative_failed(model):
-                        break
-                    _coop_fallback(model)        # the device kept nothing of this batch (the failure word vetoed it): run it again
-                    steps.clear()
-                board.add_device(names, vec)
-                meter.note_external(len(targets), segm)
-                ring = rings[key]
-                order.append((key, len(ring[1])))
-                ring[1].append((batch_no, "image_id" in targets[0], [int(t["boxes"].shape[0]) for t in targets]))
-                samples, targets = prefetcher.next()
-                continue
-        outputs = fwd(samples)
-        if _cooperative_failed(model):           # a hand-off timed out: the batch is run again on the launched chain
-            _coop_fallback(model)
-            outputs = fwd(samples)
-        loss_dict = criterion(outputs, targets)
-        weight_dict = criterion.weight_dict
-        red = utils.reduce_dict(loss_dict)
-        # meters stay on the device (no .item() per loss): [unscaled..., scaled..., total] of this iteration in one vector
-        names, vec, wvec = _loss_vector(red, weight_dict, wvec)
-        board.add_device(names, vec)
-        key = "orig_size" if "orig_size" in targets[0] else "size"
-        orig_sizes = torch.stack([t[key] for t in targets], dim=0)
-        if meter is not None:
-            results_scaled = postprocessors["bbox"](outputs, orig_sizes, scale_to_original_shape=True)
-            for res, tg in zip(results_scaled, targets):         # the reference's check, on the post-processor's host counts
-                assert tg["boxes"].size(0) == res["boxes"].size(0), (res, tg["boxes"])
-            if "segm" in postprocessors:
-                target_sizes = torch.stack([t["size"] for t in targets], dim=0)
-                frame = postprocessors["segm"].frame(outputs, orig_sizes, target_sizes)
-                meter.update(outputs, targets, masks=frame[0], sizes=frame[2])
-                if vis_dir is not None:                          # the dumps alone need per-image views
-                    results = postprocessors["segm"].views([{} for _ in targets], frame)
-                    for i, (res, tg) in enumerate(zip(results, targets)):
-                        _dump_visuals(vis_dir, data_loader.dataset, int(tg["dataset_id"]), res["masks_origin"][0, 0],
-                                      results_scaled[i]["boxes"][0], outputs["mask_att"][i])
-            else:
-                meter.update(outputs, targets)
-            if on_canvas:                        # a misfit between canvas batches: merged with the ring's results in loader order
-                order.append({})
-                _fill_results(order[-1], targets, results_scaled)
-            else:
-                _fill_results(results_dict, targets, results_scaled)
-            samples, targets = prefetcher.next()
-            continue
-        results = postprocessors["bbox"](outputs, orig_sizes)
+def _stacked_sizes(targets, original=False):
+    """[B, 2] (h, w) of the batch's images as the model saw them, or (`original`) before resizing where the targets say."""
+    key = "orig_size" if original and "orig_size" in targets[0] else "size"
+    return torch.stack([t[key] for t in targets], dim=0)
+
+
+class _LoaderOrder:
+    """The way every batch's results reach results_dict, in loader order: per batch one (book, index), `book` a list of dicts --
+    `filled`, filled batch by batch (fill()), or a results ring's slots, empty until the ring is read back and decoded (slot())."""
+
+    def __init__(self):
+        self.order, self.filled = [], []
+
+    def fill(self):
+        self.filled.append({})
+        self.slot(self.filled, len(self.filled) - 1)
+        return self.filled[-1]
+
+    def slot(self, book, index):
+        self.order.append((book, index))
+
+    def merge(self, results_dict):
+        for book, index in self.order:
+            results_dict.update(book[index])
+
+
+class _OwnShapeEval:
+    """A batch evaluated at its own shape: the forward (`replayed`: CapturedForward, else the model's launches), run again on the
+    launched chain when a hand-off timed out; criterion; the loss meters, handed to `book(names, vec)` BEFORE the subclass's score():
+    scoring waits for the device, and what is launched before it costs the host nothing.  vis: None or (directory, dataset)."""
+
+    def __init__(self, model, criterion, postprocessors, device, replayed, vis, book):
+        fwd = CapturedForward(model) if replayed else model
+        self.losses = _ForwardLosses(lambda samples: _run_again_on_chain(model, lambda: fwd(samples)), criterion)
+        self.post, self.device, self.vis, self.book, self.order = postprocessors, device, vis, book, _LoaderOrder()
+
+    def __call__(self, batch_no, samples, targets):
+        outputs, names, vec = self.losses(samples, targets)
+        self.book(names, vec)
+        self.score(outputs, targets, _stacked_sizes(targets, original=True))
+
+    def dump_visuals(self, outputs, targets, results, results_scaled):
+        if self.vis is not None:
+            for res, tg, scaled, att in zip(results, targets, results_scaled, outputs["mask_att"]):
+                _dump_visuals(*self.vis, int(tg["dataset_id"]), res["masks_origin"][0, 0], scaled["boxes"][0], att)
+
+
+class _TorchLoopEval(_OwnShapeEval):
+    """The reference's per-image torch loop (engine_vg.py:127-152, 205-219): Acc@0.5 and mean IoU of the predicted boxes, mean mask
+    IoU with a 'segm' post-processor; the running sums stay on the device until finish()."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.sum_accu, self.sum_iou, self.cnt, self.seg_iou = (torch.zeros((), device=self.device) for _ in range(4))
+        self.cnt_seg = 0.0
+
+    def score(self, outputs, targets, orig_sizes):
+        results = self.post["bbox"](outputs, orig_sizes)
         for res, tg in zip(results, targets):
             gt = box_cxcywh_to_xyxy(tg["boxes"])
             assert gt.size(0) == res["boxes"].size(0), (res, gt)
             iou = torch.diag(box_iou(gt, res["boxes"])[0])
-            sum_accu += (iou > 0.5).float().sum(); sum_iou += iou.sum(); cnt += len(tg["boxes"])
-        results_scaled = postprocessors["bbox"](outputs, orig_sizes, scale_to_original_shape=True)
-        if "segm" in postprocessors:
-            target_sizes = torch.stack([t["size"] for t in targets], dim=0)
-            results = postprocessors["segm"](results, outputs, orig_sizes, target_sizes)
-            for i, (res, tg) in enumerate(zip(results, targets)):
-                seg_iou += mask_iou(res["masks"][0][0], tg["masks"])
-                cnt_seg += 1
-                if vis_dir is not None:
-                    _dump_visuals(vis_dir, data_loader.dataset, int(tg["dataset_id"]), res["masks_origin"][0, 0],
-                                  results_scaled[i]["boxes"][0], outputs["mask_att"][i])
-        for tg, res in zip(targets, results_scaled):
+            self.sum_accu += (iou > 0.5).float().sum(); self.sum_iou += iou.sum(); self.cnt += len(tg["boxes"])
+        results_scaled = self.post["bbox"](outputs, orig_sizes, scale_to_original_shape=True)
+        if "segm" in self.post:
+            results = self.post["segm"](results, outputs, orig_sizes, _stacked_sizes(targets))
+            for res, tg in zip(results, targets):
+                self.seg_iou += mask_iou(res["masks"][0][0], tg["masks"])
+                self.cnt_seg += 1
+            self.dump_visuals(outputs, targets, results, results_scaled)
+        filled = self.order.fill()
+        for tg, res in zip(targets, results_scaled):             # the reference's fill, one copy per image (:203)
             if "image_id" in tg:
-                results_dict[int(tg["image_id"])] = res["boxes"].cpu().numpy().tolist()
+                filled[int(tg["image_id"])] = res["boxes"].cpu().numpy().tolist()
+
+    def finish(self, stats, results_dict):
+        if utils.is_dist_avail_and_initialized():
+            for t in (self.sum_accu, self.sum_iou, self.cnt) + ((self.seg_iou,) if "segm" in self.post else ()):
+                torch.distributed.all_reduce(t)
+        stats["accuracy_iou0.5"] = float(self.sum_accu / self.cnt.clamp(min=1))
+        stats["miou"] = float(self.sum_iou / self.cnt.clamp(min=1))
+        if "segm" in self.post:                  # the reference's formula: sum / (world x this rank's sample count), :212-219
+            stats["seg_miou"] = float(self.seg_iou / max(utils.get_world_size() * self.cnt_seg, 1.0))
+        self.order.merge(results_dict)
+
+
+class _MeteredEval(_OwnShapeEval):
+    """Scored on the device by metrics.EvalMeter (csrc/rt_eval.hip: one ABI call per batch, the running totals are read back once),
+    which adds 'seg_oiou' and 'seg_prec@0.5' ... '@0.9' for a RES model.  One device-to-host copy per batch: the result boxes."""
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.meter = EvalMeter(self.device, seg="segm" in self.post)
+
+    def score(self, outputs, targets, orig_sizes):
+        results_scaled = self.post["bbox"](outputs, orig_sizes, scale_to_original_shape=True)
+        for res, tg in zip(results_scaled, targets):         # the reference's check, on the post-processor's host counts
+            assert tg["boxes"].size(0) == res["boxes"].size(0), (res, tg["boxes"])
+        if "segm" in self.post:
+            frame = self.post["segm"].frame(outputs, orig_sizes, _stacked_sizes(targets))
+            self.meter.update(outputs, targets, masks=frame[0], sizes=frame[2])
+            if self.vis is not None:                         # the dumps alone need per-image views
+                self.dump_visuals(outputs, targets, self.post["segm"].views([{} for _ in targets], frame), results_scaled)
+        else:
+            self.meter.update(outputs, targets)
+        _fill_results(self.order.fill(), targets, results_scaled)
+
+    def finish(self, stats, results_dict):
+        stats.update(self.meter.compute())
+        self.order.merge(results_dict)
+
+
+class _CanvasEval:
+    """A batch that fits `canvas` (why_not, why_not_eval) runs as one replay of one captured graph (CapturedEvalStep; one capture per
+    canvas key) with no device-to-host copy: totals and boxes stay on the device, in the wrapped _MeteredEval's accumulators and a results
+    ring per key, read back once in finish().  A batch that does not fit goes to that path at its own shape (said once per reason).  A
+    replay whose hand-off timed out was vetoed on the device: every capture goes, the rings stay, the batch is replayed once more."""
+
+    def __init__(self, model, criterion, postprocessors, canvas, slots, own_shape):
+        assert isinstance(own_shape, _MeteredEval)           # its meter, loader order and `book` are this path's too
+        self.model, self.canvas, self.slots, self.capture_args = model, canvas, slots, (model, criterion, postprocessors, canvas)
+        self.own_shape, self.meter, self.order, self.segm = own_shape, own_shape.meter, own_shape.order, "segm" in postprocessors
+        self.steps, self.rings = {}, {}      # by canvas key: the capture; (the ring's device state, its batches as replayed, decoded)
+        self.meter.reset(fresh=False)
+
+    def _replay(self, key, samples, targets):
+        step = self.steps.get(key)
+        if step is None:
+            state = self.rings[key][0] if key in self.rings else None
+            step = self.steps[key] = CapturedEvalStep(*self.capture_args, samples, targets, self.meter.acc, self.slots, state=state)
+            self.rings.setdefault(key, (step.state, [], []))
+        return step(samples, targets)
+
+    def __call__(self, batch_no, samples, targets):
+        why = self.canvas.why_not(samples, targets) or self.canvas.why_not_eval(samples, targets, segm=self.segm)
+        if why is not None:
+            _say_once(self.model, ("eval-canvas", why), f"[reftr_amd] evaluate: a batch does not fit {self.canvas!r} ({why}): it runs at "
+                      "its own shape")
+            return self.own_shape(batch_no, samples, targets)
+        key = self.canvas.key(samples)
+        if any(st._gen != _state(self.model).coop_generation for st in self.steps.values()):
+            self.steps.clear()
+        self.own_shape.book(*_run_again_on_chain(self.model, lambda: self._replay(key, samples, targets), drop=self.steps.clear))
+        self.meter.book(len(targets), self.segm)
+        _, batches, decoded = self.rings[key]
+        self.order.slot(decoded, len(batches))
+        batches.append((batch_no, "image_id" in targets[0], [int(t["boxes"].shape[0]) for t in targets]))
+
+    def finish(self, stats, results_dict):
+        for st, batches, decoded in self.rings.values():         # the ONE read-back of the result boxes, then a pure host decode
+            decoded += decode_ring(st.boxes.cpu().numpy(), st.counts.cpu().numpy(), st.ids.cpu().numpy(), *st.cursor.tolist(), batches)
+        self.own_shape.finish(stats, results_dict)
+
+
+@torch.no_grad()
+def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=None, visualize=False, canvas=None):
+    """engine_vg.evaluate (engine_vg.py:82-225): the loss meters, Acc@0.5 / mean IoU of the predicted boxes, mask IoU with a 'segm'
+    post-processor, and the boxes scaled to the original image size in the returned results dict (:141,203).  How a batch is evaluated
+    is chosen once (_EvalPlan): scored on the device (_MeteredEval) or by the reference's torch loop (_TorchLoopEval), and with `canvas`
+    (a reftr_amd.data.canvas.BatchCanvas, which defines what a canvas batch computes) replayed from one graph where it fits (_CanvasEval).
+    `visualize` (needs 'segm', `output_dir` and a dataset with `split` / `pull_item`): _dump_visuals' images per sample (:86-96,157-192).
+    A path books a batch's loss meters on the board itself (board.add_device, handed to it), before whatever waits for the device."""
+    plan = _EvalPlan(model, criterion, postprocessors, device, visualize, canvas)
+    model.eval()
+    criterion.eval()
+    board = utils.StatBoard()
+    vis = (_vis_dirs(output_dir, data_loader.dataset.split), data_loader.dataset) if visualize else None
+    own_shape = _MeteredEval if plan.metered else _TorchLoopEval
+    path = own_shape(model, criterion, postprocessors, device, plan.replayed, vis, board.add_device)
+    if plan.on_canvas:
+        path = _CanvasEval(model, criterion, postprocessors, canvas, len(data_loader), path)
+    prefetcher = data_prefetcher(data_loader, device, prefetch=True)
+    samples, targets = prefetcher.next()
+    for batch_no in board.log_every(range(len(data_loader)), 50, "Test:"):
+        path(batch_no, samples, targets)
         samples, targets = prefetcher.next()
     _check_cooperative(model)
-    if on_canvas:
-        # the ONE read-back of the result boxes: every ring once, then a pure host decode (metrics.decode_ring), merged in loader order
-        from .metrics import decode_ring
-        decoded = {}
-        for key, (state, batches) in rings.items():
-            cursor, overflow = state.cursor.tolist()
-            decoded[key] = decode_ring(state.boxes.cpu().numpy(), state.counts.cpu().numpy(), state.ids.cpu().numpy(), cursor, overflow,
-                                       batches)
-        for entry in order:
-            results_dict.update(entry if isinstance(entry, dict) else decoded[entry[0]][entry[1]])
     board.synchronize_between_processes()
-    stats = board.global_avg()
-    if meter is not None:
-        stats.update(meter.compute())
-    else:
-        if utils.is_dist_avail_and_initialized():
-            for t in (sum_accu, sum_iou, cnt):
-                torch.distributed.all_reduce(t)
-        stats["accuracy_iou0.5"] = float(sum_accu / cnt.clamp(min=1))
-        stats["miou"] = float(sum_iou / cnt.clamp(min=1))
-        if "segm" in postprocessors:
-            if utils.is_dist_avail_and_initialized():
-                torch.distributed.all_reduce(seg_iou)
-                cnt_seg = utils.get_world_size() * cnt_seg
-            stats["seg_miou"] = float(seg_iou / max(cnt_seg, 1.0))
-    stats = {k: v for k, v in stats.items() if k.split("_")[-1] not in ("unscaled", "0", "1", "2")}      # engine_vg.py:221
-    return stats, results_dict
+    stats, results_dict = board.global_avg(), {}
+    path.finish(stats, results_dict)
+    return {k: v for k, v in stats.items() if k.split("_")[-1] not in ("unscaled", "0", "1", "2")}, results_dict      # engine_vg.py:221

@@ -106,22 +106,18 @@ class EvalMeter:
         self.acc = torch.zeros(H.EVAL_SLOTS, dtype=torch.int64, device=self.device)
         self.reset()
 
-    def reset(self):
+    def reset(self, fresh=True):
+        """Zeroes the accumulators now.  fresh: the next update also starts them from zero inside its own launch; False for a loop in
+        which another producer (engine_vg.CapturedEvalStep: rt_eval_canvas inside a replayed graph) adds to `acc` beside update()."""
         self.acc.zero_()
-        self._fresh = True          # the next update also starts the accumulators from zero inside its own launch
+        self._fresh = fresh
         self.seg = bool(self._seg)
         self.local_seg_n = 0
         self.last = None
         self._keep = None
 
-    def begin_external(self):
-        """For a loop in which another producer (engine_vg.CapturedEvalStep: rt_eval_canvas inside a replayed graph) adds to `acc`
-        beside update(): the accumulators are zeroed NOW and no later update resets them."""
-        self.acc.zero_()
-        self._fresh = False
-
-    def note_external(self, n_images, seg):
-        """Books a batch that the other producer scored: the mask keys and this rank's seg sample count, as update() books them."""
+    def book(self, n_images, seg):
+        """Books a batch that was added to `acc`, by update() or by the other producer: the mask keys and this rank's seg sample count."""
         if seg:
             self.seg = True if self._seg is None else self.seg
             self.local_seg_n += int(n_images)
@@ -145,9 +141,7 @@ class EvalMeter:
         sizes_dev = dev[5 * B:].view(torch.int32).view(B, 2) if masks is not None else None
         iou_det, iou_seg, iu = H.eval_metrics(boxes, valid, table, self.acc, masks=masks, sizes_i32=sizes_dev, reset=self._fresh)
         self._fresh = False
-        if masks is not None:
-            self.seg = True if self._seg is None else self.seg
-            self.local_seg_n += B
+        self.book(B, masks is not None)
         self._keep = (keep, dev, boxes, valid, masks)                        # alive until the next update
         self.last = SimpleNamespace(iou_det=iou_det, iou_seg=iou_seg, iu=iu)
 

@@ -111,7 +111,7 @@ def compose(model, crit, post, loader, cv, fits=None):
             un = torch.stack([ld[k].reshape(()).float() for k in names])
             sc = torch.stack([ld[k].reshape(()).float() for k in wn]) * torch.tensor([wd[k] for k in wn], dtype=torch.float32, device="cuda")
             board.add_device([f"{k}_unscaled" for k in names] + wn + ["loss"], torch.cat([un, sc, sc.sum().reshape(1)]))
-            orig = torch.stack([x["orig_size"] for x in t])
+            orig = torch.stack([x["orig_size" if "orig_size" in t[0] else "size"] for x in t])
             scaled = post["bbox"](out, orig, scale_to_original_shape=True)
             if "segm" in post:
                 sizes = [[int(a), int(b)] for a, b in torch.stack([x["size"] for x in t]).tolist()]
@@ -234,6 +234,34 @@ def test_misfits_in_the_middle_take_the_existing_path(hip, counted, capfd):
     same(got, want)
     assert res_got == res_want and list(res_got) == list(res_want)
     assert counted["captures"] == 1 and counted["forward_path"] == 3
+
+
+def rec_res_misfit_loader():
+    """REC+RES, B = 2, for a 128 x 128 masks=True canvas: fits, an image larger than the canvas, fits, `orig_size` missing on one image
+    (a misfit by why_not_eval; image 0, so that the path at the batch's own shape scales every box by `size`)."""
+    loader = [make_batch(ragged(h, w), j, masks=True) for j, (h, w) in enumerate([(96, 128), (160, 128), (64, 96), (128, 96)])]
+    del loader[3][1][0]["orig_size"]
+    return loader
+
+
+def test_rec_res_misfits_alternate_with_canvas_batches(hip, counted, capfd):
+    """The REC+RES twin of the test above: the meter's two producers (rt_eval_canvas inside the replayed graph, EvalMeter.update) and the
+    segmentation frame (the canvas, the batch's own) alternate batch by batch; totals, results and their order are the composition's."""
+    from reftr_amd.engine_vg import evaluate
+    model, crit = _build(masks=True)
+    post = _post(True)
+    loader = rec_res_misfit_loader()
+    cv = BatchCanvas(128, 128, 1, masks=True)
+    fits = [True, False, True, False]
+    assert [cv.why_not(*b) is None and cv.why_not_eval(*b, segm=True) is None for b in loader] == fits
+    want, res_want = compose(model, crit, post, loader, cv, fits=fits)
+    capfd.readouterr()
+    got, res_got = evaluate(model, crit, post, loader, torch.device("cuda"), canvas=cv)
+    lines = [ln for ln in capfd.readouterr().err.splitlines() if "does not fit" in ln]
+    assert len(lines) == 2 and "exceeds the canvas" in lines[0] and "orig_size" in lines[1], lines
+    same(got, want)
+    assert res_got == res_want and list(res_got) == list(res_want) == [0, 1, 100, 101, 200, 201, 300, 301]
+    assert counted["captures"] == 1 and counted["forward_path"] == 2 and got["seg_miou"] > 0
 
 
 def test_refusals_and_switches(hip, monkeypatch, counted):
