@@ -1,5 +1,5 @@
 """GPU: the decoder stack as one cooperative launch (rt_decoder_fwd, csrc/rt_decoder.hip) against the launched chain it replaces
-(transformer.py:231-252 per layer).  The cooperative kernel repeats the chain's arithmetic operation for operation, so the bar is
+(transformer.py:231-252 per layer).  The cooperative kernel runs the chain's arithmetic (its LayerNorm rows and one-query attention are the chain's code), so the bar is
 bit equality of every tensor the backward reads, in eval mode and with dropout on, at the test size and at configs[1]'s B = 8."""
 import os
 
@@ -72,6 +72,21 @@ def run(model, crit, s, tg, coop, train, seed=10, backward=False, coop_bwd=False
     return res
 
 
+# the last shape has 512 < S <= 768 keys: all three key slots per thread of the cooperative attention stage run.  Forward only: in the
+# backward test this shape passes the bit-identity of the decoder's own gradients but misses the whole-buffer bound of the
+# read-modify-write pass (7.2e-5 measured against 2e-6); why is an open question.
+ALL_KEY_SLOTS = (2, 2, 736, 736)
+SHAPES = [(2, 2, 96, 128), (8, 6, 192, 160), (13, 3, 64, 64), ALL_KEY_SLOTS]
+
+
+def assert_cooperative(model, B, dec_layers, H, W):
+    """The last forward took the cooperative path (the test must not compare the chain with itself), at the S the shape is here for."""
+    S = model._saved["S"]
+    assert model.net.dec_coop and model.net.dec_stack_coop_ok(B, 1, S, dec_layers, True), (B, S, dec_layers)
+    if (B, dec_layers, H, W) == ALL_KEY_SLOTS:
+        assert 513 <= S <= 768, S
+
+
 def assert_same(a, b):
     assert torch.equal(a["logits"], b["logits"])
     assert torch.equal(a["t3s"], b["t3s"])
@@ -81,7 +96,7 @@ def assert_same(a, b):
 
 
 @pytest.mark.parametrize("train", [False, True])
-@pytest.mark.parametrize("B,dec_layers,H,W", [(2, 2, 96, 128), (8, 6, 192, 160), (13, 3, 64, 64)])
+@pytest.mark.parametrize("B,dec_layers,H,W", SHAPES)
 def test_cooperative_decoder_is_bit_identical_to_the_launched_chain(hip, B, dec_layers, H, W, train):
     model, crit, s, tg = build(dec_layers, B, H, W)
     ref = run(model, crit, s, tg, coop=False, train=train)
@@ -89,6 +104,7 @@ def test_cooperative_decoder_is_bit_identical_to_the_launched_chain(hip, B, dec_
     for rep in range(5):                     # hand-offs are timing dependent: repeat
         got = run(model, crit, s, tg, coop=True, train=train)
         assert_same(got, ref)
+    assert_cooperative(model, B, dec_layers, H, W)
     if train:                                # another step seed: other masks, still identical
         a = run(model, crit, s, tg, coop=False, train=True, seed=77)
         b = run(model, crit, s, tg, coop=True, train=True, seed=77)
@@ -108,7 +124,7 @@ def test_backward_consumes_the_cooperative_forward_unchanged(hip):
 
 
 @pytest.mark.parametrize("train", [False, True])
-@pytest.mark.parametrize("B,dec_layers,H,W", [(2, 2, 96, 128), (8, 6, 192, 160), (13, 3, 64, 64)])
+@pytest.mark.parametrize("B,dec_layers,H,W", SHAPES[:3])
 def test_cooperative_backward_matches_the_launched_chain(hip, B, dec_layers, H, W, train):
     """rt_decoder_bwd against dec_layer_bwd on the same (cooperative) forward.  With the memory gradient formed as the chain forms
     it (one read-modify-write product per layer) every gradient that is not accumulated with atomics is bit-identical -- the
@@ -118,6 +134,7 @@ def test_cooperative_backward_matches_the_launched_chain(hip, B, dec_layers, H, 
     through d memory moves by rounding flips (the bf16 noise floor of DESIGN.md section 4: ~1e-3 of the buffer)."""
     model, crit, s, tg = build(dec_layers, B, H, W)
     a = run(model, crit, s, tg, coop=True, train=train, backward=True, coop_bwd=False)
+    assert_cooperative(model, B, dec_layers, H, W)
     G = lambda res, name: model.store.view_of(res["grad"], name)
     dec_keys = [f"vl_transformer.decoder.layers.{i}.{nm}" for i in range(dec_layers)
                 for nm in ("linear1.weight", "linear2.weight", "self_attn.out_proj.weight", "multihead_attn.out_proj.weight")]
@@ -182,3 +199,38 @@ def test_many_replays_under_a_captured_graph(hip):
     assert [v[0] for v in losses[True]] == [v[0] for v in losses[False]]
     # gradient norms: the atomics' order + the packed d-memory product's summation order (rounding flips downstream of d memory)
     assert all(abs(a[1] - b[1]) < 5e-3 * b[1] for a, b in zip(losses[True], losses[False]))
+
+
+# the codes of include/reftr_hip.h; which one the entry points answered for each case below was read off their source before
+# their checks became one definition
+RT_ERR_BADARG, RT_ERR_UNSUPPORTED = -1, -2
+HOST_CASES = [
+    (dict(M=0), RT_ERR_UNSUPPORTED), (dict(M=17), RT_ERR_UNSUPPORTED), (dict(S=0), RT_ERR_UNSUPPORTED), (dict(S=769), RT_ERR_UNSUPPORTED),
+    (dict(H=4), RT_ERR_UNSUPPORTED), (dict(F=1024), RT_ERR_UNSUPPORTED), (dict(ldkv=260), RT_ERR_UNSUPPORTED),
+    (dict(n_layers=0), RT_ERR_UNSUPPORTED), (dict(n_layers=9), RT_ERR_UNSUPPORTED),
+    # a missing top-level pointer is a bad argument before anything is unsupported; a missing per-layer pointer is found behind the geometry
+    (dict(handoff=None, M=17), RT_ERR_BADARG), (dict(layer_k2=None, M=17), RT_ERR_UNSUPPORTED), (dict(layer_k2=None), RT_ERR_BADARG),
+]
+
+
+def test_entry_points_refuse_the_same_calls_with_the_same_codes(hip):
+    """One valid rt_decoder_fwd / rt_decoder_bwd call (M = 2, one layer), one field changed at a time: forward and backward give the same
+    code, the one they always gave.  Every case is refused before any launch."""
+    import ctypes
+    assert hip.DEC_MAX_LAYERS == 8
+    buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")          # every pointer of the descriptors: never dereferenced
+    geo = dict(n_layers=1, M=2, H=8, S=24, F=2048, ldkv=256)
+
+    def code(name, cls, top, variation):
+        fields = dict(geo, drop_p=0.0, scale=32 ** -0.5, **{k: buf for k in top})
+        layer_k2 = variation.get("layer_k2", buf)
+        fields.update({k: v for k, v in variation.items() if k != "layer_k2"})
+        d = hip._desc(cls, **fields)
+        optional = ("dk2p", "dv2p")
+        hip._set(d.layer[0], **{n: (layer_k2 if n == "k2" else None if n in optional else buf) for n in type(d.layer[0])._PTRS})
+        return getattr(hip.lib(), name)(ctypes.byref(d), None)
+
+    for variation, want in HOST_CASES:
+        fwd = code("rt_decoder_fwd", hip.DecoderFwdDesc, ("t32", "t16", "qpos", "handoff"), variation)
+        bwd = code("rt_decoder_bwd", hip.DecoderBwdDesc, ("dta", "dqpos", "handoff"), variation)
+        assert fwd == bwd == want, (variation, fwd, bwd, want)
