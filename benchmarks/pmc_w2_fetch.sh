@@ -1,13 +1,14 @@
 # Fabric fetch bytes of the v2 weight-gradient groups (layer3, layer4, layer2 of the bench workload) per placement mode
+# (REFTR_W2_XCD: 0 = the hardware's round-robin, 2 = contiguous runs, the product's)
 export TMPDIR=/tmp; R=$PWD; cd /tmp
-for x in ${MODES:-0 1}; do
+for x in ${MODES:-0 2}; do
 rm -rf $R/gpurun_out/pmc_w2f_$x
 REFTR_W2_XCD=$x timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/gpurun_out/pmc_w2f_$x -- python $R/benchmarks/pmc_w2.py > $R/gpurun_out/pmc_w2f_$x.log 2>&1
 done
 cd $R
 python - <<'PY'
 import sqlite3, glob, collections, os
-for tag in os.environ.get("MODES", "0 1").split():
+for tag in os.environ.get("MODES", "0 2").split():
     dbs = glob.glob(f"gpurun_out/pmc_w2f_{tag}/**/*.db", recursive=True)
     if not dbs: print("no db", tag); continue
     db = sqlite3.connect(dbs[0])

@@ -13,17 +13,15 @@
 // (pre-zeroed) flat gradient buffer.
 #include "rt_common.h"
 #include "rt_lds.h"
+#include "rt_wgrad_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-struct WgradArgs {
-    const bf16_t* dy; const bf16_t* x; float* dw; const float* scale; float* dbias;
-    int B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad, dil;
-    int M, chunks_per_block, c_tiles;
+struct WgradArgs : WgGeom {
+    int chunks_per_block, c_tiles;
     float* part; int out_elems; int xcd, early, epi_lds;      // split partials workspace ([split][N*taps*SC]) or NULL -> atomics
     int overwrite;            // single-writer launches (one split, no workspace) store instead of accumulating
-    unsigned dy_bytes, x_bytes;
 };
 
 // SIMPLE: 1x1 / stride 1 / pad 0 (x row = m).  NVEC: N % 8 == 0 (16-B dy loads).
@@ -44,18 +42,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
     const int wn = wave & 1, wc = wave >> 1;
     const int li = lane & 15, lg = lane >> 4;
 
-    const int n_tiles = (p.N + BN - 1) / BN;
-    const int tile_n = blockIdx.x % n_tiles;
-    const int rest = blockIdx.x / n_tiles;
-    const int tile_c = rest % p.c_tiles;
-    const int tap = rest / p.c_tiles;
-    const int kh = tap / p.KW, kw = tap - kh * p.KW;
-    const int n0 = tile_n * BN, c0 = tile_c * BC;
-
-    const int chunk_begin = blockIdx.y * p.chunks_per_block;
-    const int total_chunks = (p.M + 31) >> 5;
-    int chunk_end = chunk_begin + p.chunks_per_block;
-    if (chunk_end > total_chunks) chunk_end = total_chunks;
+    const WgTile tl = wg_tile<BN, BC>(blockIdx.x, (p.N + BN - 1) / BN, p.c_tiles, p.KW);
+    const int tap = tl.tap, kh = tl.kh, kw = tl.kw, n0 = tl.n0, c0 = tl.c0;
+    const WgChunks ck = wg_chunks<32>(p.M, blockIdx.y, p.chunks_per_block);
+    const int chunk_begin = ck.begin, chunk_end = ck.end;
     if (chunk_begin >= chunk_end) return;
 
     const int a_chunk = t % ACH, a_row = t / ACH;          // rows a_row + A_RSTEP*j
@@ -66,12 +56,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
     const bool b_cok = b_c < p.SC;
 
     // running (batch, y, x) of each staged x-row for the gather modes (advanced by 32 rows per chunk)
-    int gb[BJ], gy[BJ], gx[BJ];
+    WgGather gw[BJ];
 #pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-        const int m = (chunk_begin << 5) + b_row + B_RSTEP * j;
-        gx[j] = m % p.DW; const int tmp = m / p.DW; gy[j] = tmp % p.DH; gb[j] = tmp / p.DH;
-    }
+    for (int j = 0; j < BJ; ++j) gw[j].init((chunk_begin << 5) + b_row + B_RSTEP * j, p.DH, p.DW);
 
     f32x4 acc[TN][TC];
 #pragma unroll
@@ -79,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
 #pragma unroll
         for (int b = 0; b < TC; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const bool do_bias = p.dbias && tile_c == 0 && tap == 0;
+    const bool do_bias = wg_do_bias(p.dbias, tl);
     float bsum = 0.f;
 
     // Two register stages + two LDS buffers, operands fetched with bounds-checked buffer loads (out-of-range offset
@@ -88,7 +75,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
     const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(dyp), 0, p.dy_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(xp), 0, p.x_bytes, 0x00020000);
     constexpr int OOB = 0x7fffffff;
-    int lc = chunk_begin;             // next chunk to load (the gather state gb/gy/gx belongs to it)
+    int lc = chunk_begin;             // next chunk to load (the gather state gw belongs to it)
 
     auto load_tiles = [&](uint4 (&ra)[AJ], uint4 (&rb)[BJ]) __attribute__((always_inline)) {
         const int mbase = lc << 5;
@@ -116,13 +103,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
             int pix;
             if (SIMPLE) pix = m;
             else {
-                const int sy = gy[j] * p.stride - p.pad + kh * p.dil, sx = gx[j] * p.stride - p.pad + kw * p.dil;
-                ok = ok && (unsigned)sy < (unsigned)p.SH && (unsigned)sx < (unsigned)p.SW;
-                pix = (gb[j] * p.SH + sy) * p.SW + sx;
-                if (!last) {
-                    gx[j] += 32;
-                    while (gx[j] >= p.DW) { gx[j] -= p.DW; if (++gy[j] >= p.DH) { gy[j] = 0; ++gb[j]; } }
-                }
+                const bool inside = gw[j].src(p, kh, kw, pix);
+                ok = ok && inside;
+                if (!last) gw[j].template advance<32>(p.DH, p.DW);
             }
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? (pix * p.SC + b_c) * 2 : OOB, 0, 0);
             rb[j] = make_uint4(v[0], v[1], v[2], v[3]);
@@ -161,14 +144,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
 #pragma unroll
             for (int b = 0; b < TC; ++b)
                 acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
-        if (do_bias) {      // fused bias gradient: column sums of the dy tile that is already in LDS
-            constexpr int TPC = 256 / BN;            // threads per column
-            constexpr int RPT = 32 / TPC;            // rows per thread
-            const int col = t % BN, r0 = (t / BN) * RPT;
-#pragma unroll
-            for (int r = 0; r < RPT; ++r)
-                bsum += (float)*reinterpret_cast<const bf16_t*>(bA + (r0 + r) * SA + col * 2);
-        }
+        if (do_bias) wg_bias_cols<BN, 32, 256, SA, WgNoSwz>(bA, t, bsum);      // (the padded tile is not swizzled)
     };
 
     const int nch = chunk_end - chunk_begin;
@@ -188,10 +164,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
         __syncthreads();
     }
 
-    if (do_bias) {
-        const int n = n0 + t % BN;
-        if (n < p.N) atomicAdd(p.dbias + n, bsum);
-    }
+    if (do_bias) wg_bias_commit<BN>(p.dbias, n0, p.N, t, bsum);
     const int taps = p.KH * p.KW;
 #pragma unroll
     for (int a = 0; a < TN; ++a) {
@@ -220,8 +193,41 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const bf16_t* __rest
 // SIMPLE operands are addressed through a buffer descriptor that is re-based per chunk with scalar arithmetic (base +=
 // chunk bytes, num_records -= chunk bytes): the per-lane offsets are loop-invariant and the ragged tail rows fall off
 // the end of the descriptor, i.e. read as zeros.
-template <int RB> __device__ __forceinline__ int wg_swz(int row) {      // XOR applied to the 16-B slot index
-    return RB >= 256 ? ((row & 7) << 1) : (((row >> 1) & 3) << 1);
+template <int RB> struct WgSwz {                                         // XOR applied to the 16-B slot index
+    static __device__ __forceinline__ int of(int row) { return RB >= 256 ? ((row & 7) << 1) : (((row >> 1) & 3) << 1); }
+};
+
+// ---- LDS-DMA staging of a [rows][RB bytes] operand tile by four waves.  Instruction j of wave `wave4` (0..3) lands lane l at tile
+// byte (j * 4 + wave4) * 1024 + 16 * l (rt_dma16 is lane-linear), so the bank swizzle SWZ::of(row), an XOR on the 16-B slot index, is
+// applied to the SOURCE column.  row[j]: the tile row of this lane's piece; voff[j]: its source byte offset relative to the chunk's
+// first row -- (row * row_elems + column) * 2, with row_elems = 0 for the gathered operand, whose row address is added per chunk --
+// or WG_OOB for a column past `cols`.
+template <int RB, int NJ, class SWZ>
+__device__ __forceinline__ void wg_dma_offsets(int (&voff)[NJ], int (&row)[NJ], int wave4, int lane, int col0, int cols, int row_elems) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int byte = (j * 4 + wave4) * 1024 + lane * 16;
+        const int r = byte / RB, sl = ((byte % RB) >> 4) ^ SWZ::of(r);
+        const int c = col0 + sl * 8;
+        row[j] = r;
+        voff[j] = c < cols ? (r * row_elems + c) * 2 : WG_OOB;
+    }
+}
+
+// Gathered x rows of filter tap (kh, kw): one source pixel per staged row, zeros for the padding and for rows past M; unless this
+// is the split's last chunk, the walkers move on to the next one.
+template <int CR, int NJ, class P>
+__device__ __forceinline__ void wg_issue_gather(const P& p, const i32x4 rs_x, int chunk, bool last, int kh, int kw, unsigned lds,
+                                                const int (&voff)[NJ], const int (&row)[NJ], WgGather (&g)[NJ]) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int m = chunk * CR + row[j];
+        int pix;
+        const bool inside = g[j].src(p, kh, kw, pix);
+        const bool ok = m < p.M && inside && voff[j] != WG_OOB;
+        rt_dma16(rs_x, lds + j * 4096, ok ? pix * p.SC * 2 + voff[j] : WG_OOB);
+        if (!last) g[j].template advance<CR>(p.DH, p.DW);
+    }
 }
 
 // `lin_raw` = linear workgroup id inside this problem's (gx x gy) grid: the kernel is launched either alone
@@ -234,10 +240,8 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
     constexpr int SPRA = BN / 8, SPRB = BC / 8;          // 16-B slots per row
     constexpr int A_BYTES = CR * RBA, B_BYTES = CR * RBB, BUF_BYTES = A_BYTES + B_BYTES;
     constexpr int AJ = CR * SPRA / 256, BJ = CR * SPRB / 256;
-    constexpr int RPIA = 64 / SPRA, RPIB = 64 / SPRB;    // rows covered by one wave instruction
     constexpr int KS = CR / 32;
     constexpr int LPT = AJ + BJ;
-    constexpr int OOB = 0x7fffffff;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -246,46 +250,24 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
     const int wn = wave & 1, wc = wave >> 1;
     const int li = lane & 15, lg = lane >> 4;
 
-    const int n_tiles = (p.N + BN - 1) / BN;
     // linear workgroup id -> (tile, split) with every split's tiles on one XCD (they read the same dy / x rows)
     const int lin = rt_xcd_remap(lin_raw, grid_x * grid_y, p.xcd);
     const int by = __builtin_amdgcn_readfirstlane(lin / grid_x);      // (integer division goes through VALU)
     const int bx = __builtin_amdgcn_readfirstlane(lin - by * grid_x);
-    const int tile_n = bx % n_tiles;
-    const int rest = bx / n_tiles;
-    const int tile_c = rest % p.c_tiles;
-    const int tap = rest / p.c_tiles;
-    const int kh = tap / p.KW, kw = tap - kh * p.KW;
-    const int n0 = tile_n * BN, c0 = tile_c * BC;
-
-    const int total_chunks = (p.M + CR - 1) / CR;
-    const int chunk_begin = by * p.chunks_per_block;
-    int chunk_end = chunk_begin + p.chunks_per_block;
-    if (chunk_end > total_chunks) chunk_end = total_chunks;
+    const WgTile tl = wg_tile<BN, BC>(bx, (p.N + BN - 1) / BN, p.c_tiles, p.KW);
+    const int tap = tl.tap, n0 = tl.n0, c0 = tl.c0;
+    const WgChunks ck = wg_chunks<CR>(p.M, by, p.chunks_per_block);
+    const int chunk_begin = ck.begin, chunk_end = ck.end;
     if (chunk_begin >= chunk_end) return;
 
     // loop-invariant per-lane source offsets (relative to the chunk's first row)
-    int voff_a[AJ];
+    int voff_a[AJ], a_r[AJ], voff_b[BJ], b_r[BJ];
+    wg_dma_offsets<RBA, AJ, WgSwz<RBA>>(voff_a, a_r, wave, lane, n0, p.N, p.N);
+    wg_dma_offsets<RBB, BJ, WgSwz<RBB>>(voff_b, b_r, wave, lane, c0, p.SC, SIMPLE ? p.SC : 0);
+    WgGather gw[BJ];
+    if (!SIMPLE) {
 #pragma unroll
-    for (int j = 0; j < AJ; ++j) {
-        const int r = (j * 4 + wave) * RPIA + lane / SPRA;
-        const int sl = (lane % SPRA) ^ wg_swz<RBA>(r);
-        const int n = n0 + sl * 8;
-        voff_a[j] = n < p.N ? (r * p.N + n) * 2 : OOB;
-    }
-    int voff_b[BJ], b_r[BJ], gb[BJ], gy[BJ], gx[BJ];
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-        const int r = (j * 4 + wave) * RPIB + lane / SPRB;
-        const int sl = (lane % SPRB) ^ wg_swz<RBB>(r);
-        const int c = c0 + sl * 8;
-        b_r[j] = r;
-        if (SIMPLE) { voff_b[j] = c < p.SC ? (r * p.SC + c) * 2 : OOB; gb[j] = gy[j] = gx[j] = 0; }
-        else {
-            voff_b[j] = c < p.SC ? c * 2 : OOB;
-            const int m = chunk_begin * CR + r;
-            gx[j] = m % p.DW; const int tmp = m / p.DW; gy[j] = tmp % p.DH; gb[j] = tmp / p.DH;
-        }
+        for (int j = 0; j < BJ; ++j) gw[j].init(chunk_begin * CR + b_r[j], p.DH, p.DW);
     }
 
     f32x4 acc[TN][TC];
@@ -294,7 +276,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
 #pragma unroll
         for (int b = 0; b < TC; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const bool do_bias = p.dbias && tile_c == 0 && tap == 0;
+    const bool do_bias = wg_do_bias(p.dbias, tl);
     float bsum = 0.f;
 
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)__builtin_amdgcn_readfirstlane(wave) * 1024u;
@@ -303,30 +285,10 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
 
     auto issue = [&](int stage) __attribute__((always_inline)) {
         const unsigned bA = lds0 + stage * BUF_BYTES, bB = bA + A_BYTES;
-        const unsigned aoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.N;
-        const i32x4 rs_dy = rt_make_rsrc(reinterpret_cast<const unsigned char*>(dyp) + aoff, p.dy_bytes - aoff);
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) rt_dma16(rs_dy, bA + j * 4096, voff_a[j]);
+        wg_issue_rows<CR>(dyp, p.dy_bytes, p.N, lc, bA, voff_a);
         const bool last = (lc + 1 >= chunk_end);
-        if (SIMPLE) {
-            const unsigned xoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.SC;
-            const i32x4 rs_x = rt_make_rsrc(reinterpret_cast<const unsigned char*>(xp) + xoff, p.x_bytes - xoff);
-#pragma unroll
-            for (int j = 0; j < BJ; ++j) rt_dma16(rs_x, bB + j * 4096, voff_b[j]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < BJ; ++j) {
-                const int m = lc * CR + b_r[j];
-                const int sy = gy[j] * p.stride - p.pad + kh * p.dil, sx = gx[j] * p.stride - p.pad + kw * p.dil;
-                const bool ok = m < p.M && (unsigned)sy < (unsigned)p.SH && (unsigned)sx < (unsigned)p.SW && voff_b[j] != OOB;
-                const int pix = (gb[j] * p.SH + sy) * p.SW + sx;
-                rt_dma16(rs_x_abs, bB + j * 4096, ok ? pix * p.SC * 2 + voff_b[j] : OOB);
-                if (!last) {
-                    gx[j] += CR;
-                    while (gx[j] >= p.DW) { gx[j] -= p.DW; if (++gy[j] >= p.DH) { gy[j] = 0; ++gb[j]; } }
-                }
-            }
-        }
+        if (SIMPLE) wg_issue_rows<CR>(xp, p.x_bytes, p.SC, lc, bB, voff_b);
+        else wg_issue_gather<CR>(p, rs_x_abs, lc, last, tl.kh, tl.kw, bB, voff_b, b_r, gw);
         if (!last) ++lc;
     };
 
@@ -337,12 +299,12 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
 #pragma unroll
     for (int a = 0; a < TN; ++a) {
         const int colb = (wn * (BN / 2) + a * 16) * 2 + tr_col;
-        addr_a[a] = tr_row0 * RBA + ((((colb >> 4) ^ wg_swz<RBA>(tr_row0)) << 4) | (colb & 15));
+        addr_a[a] = tr_row0 * RBA + ((((colb >> 4) ^ WgSwz<RBA>::of(tr_row0)) << 4) | (colb & 15));
     }
 #pragma unroll
     for (int b = 0; b < TC; ++b) {
         const int colb = (wc * (BC / 2) + b * 16) * 2 + tr_col;
-        addr_b[b] = tr_row0 * RBB + ((((colb >> 4) ^ wg_swz<RBB>(tr_row0)) << 4) | (colb & 15));
+        addr_b[b] = tr_row0 * RBB + ((((colb >> 4) ^ WgSwz<RBB>::of(tr_row0)) << 4) | (colb & 15));
     }
     auto compute = [&](int stage) __attribute__((always_inline)) {
         const unsigned char* bA = smem + stage * BUF_BYTES;
@@ -360,15 +322,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
                 for (int b = 0; b < TC; ++b)
                     acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a], bfr[b], acc[a][b], 0, 0, 0);
         }
-        if (do_bias) {      // fused bias gradient: column sums of the dy tile that is already in LDS
-            constexpr int TPC = 256 / BN, RPT = CR / TPC;
-            const int col = t % BN, r0 = (t / BN) * RPT;
-#pragma unroll
-            for (int r = 0; r < RPT; ++r) {
-                const int row = r0 + r;
-                bsum += (float)*reinterpret_cast<const bf16_t*>(bA + row * RBA + ((((col >> 3) ^ wg_swz<RBA>(row)) << 4) | ((col & 7) * 2)));
-            }
-        }
+        if (do_bias) wg_bias_cols<BN, CR, 256, RBA, WgSwz<RBA>>(bA, t, bsum);
     };
 
     const int nch = chunk_end - chunk_begin;
@@ -397,10 +351,7 @@ __device__ __forceinline__ void wgrad_dma_body(const bf16_t* __restrict__ dyp, c
     }
     rt_wait_vmcnt<0>();
 
-    if (do_bias) {
-        const int n = n0 + t % BN;
-        if (n < p.N) atomicAdd(p.dbias + n, bsum);
-    }
+    if (do_bias) wg_bias_commit<BN>(p.dbias, n0, p.N, t, bsum);
     const int taps = p.KH * p.KW;
     // Partial tile -> (a) split workspace with plain stores (reduced by wgrad_reduce_kernel) or (b) fp32 atomics.
     // fp32 atomics run at ~0.3 T elements/s chip-wide (one element per L2 channel clock,
@@ -679,13 +630,9 @@ int launch_wgrad_dma(WgradArgs a, int msplit, float* ws, long long ws_bytes, hip
     constexpr size_t smem = (size_t)NS * CR * (BN * 2 + BC * 2);
     const dim3 grid((unsigned)base_blocks, (unsigned)gy), block(256);
     const bool simple = (a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0);
-    if (simple) {
-        if (smem > 65536) (void)hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel<BN, BC, true, CR, NS, MINB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL((conv_wgrad_dma_kernel<BN, BC, true, CR, NS, MINB>), grid, block, smem, s, a.dy, a.x, a);
-    } else {
-        if (smem > 65536) (void)hipFuncSetAttribute((const void*)conv_wgrad_dma_kernel<BN, BC, false, CR, NS, MINB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL((conv_wgrad_dma_kernel<BN, BC, false, CR, NS, MINB>), grid, block, smem, s, a.dy, a.x, a);
-    }
+    const auto kernel = simple ? conv_wgrad_dma_kernel<BN, BC, true, CR, NS, MINB> : conv_wgrad_dma_kernel<BN, BC, false, CR, NS, MINB>;
+    if (smem > 65536) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(kernel, grid, block, smem, s, a.dy, a.x, a);
     RT_CHECK_LAUNCH();
     if (use_ws) {
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((out_elems / 4 + 63) / 64)), dim3(256), 0, s, ws, a.dw, a.scale,
@@ -869,25 +816,17 @@ static int wgrad_grouped_v1(const rt_conv_wgrad_desc* descs, int n, float* works
 }
 
 static int fill_wgrad_args(const rt_conv_wgrad_desc* d, WgradArgs& a) {
-    if (!d || !d->dy || !d->x || !d->dw) return RT_ERR_BADARG;
-    if (d->SC <= 0 || (d->SC & 15) || (d->N & 3) || d->N <= 0) return RT_ERR_UNSUPPORTED;
-    if (d->KH <= 0 || d->KW <= 0 || d->B <= 0 || d->DH <= 0 || d->DW <= 0 || d->stride <= 0) return RT_ERR_BADARG;
+    if (!d) return RT_ERR_BADARG;
+    const int rc = wg_fill_geom(*d, a, 15, 3);      // first generation: x in 16-channel pieces, N % 4
+    if (rc != RT_OK) return rc;
     if (d->dil > 1 && d->stride != 1) return RT_ERR_UNSUPPORTED;
-    a.dy = (const bf16_t*)d->dy; a.x = (const bf16_t*)d->x; a.dw = d->dw; a.scale = d->scale; a.dbias = d->dbias;
-    a.B = d->B; a.SH = d->SH; a.SW = d->SW; a.SC = d->SC; a.DH = d->DH; a.DW = d->DW; a.N = d->N;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil > 1 ? d->dil : 1;
-    const long long M = (long long)d->B * d->DH * d->DW;
-    if (M > 0x7fffffffLL / 4) return RT_ERR_UNSUPPORTED;
-    if (M * d->N >= 0x3fffffffLL || (long long)d->B * d->SH * d->SW * d->SC >= 0x3fffffffLL) return RT_ERR_UNSUPPORTED;
-    a.M = (int)M; a.chunks_per_block = 0; a.c_tiles = 0; a.part = nullptr; a.out_elems = 0; a.overwrite = d->overwrite ? 1 : 0;
+    a.chunks_per_block = 0; a.c_tiles = 0; a.part = nullptr; a.out_elems = 0; a.overwrite = d->overwrite ? 1 : 0;
     static const int xcd_env = RT_TUNE("REFTR_XCD", 1);
     a.xcd = xcd_env;
     static const int early_env = RT_TUNE("REFTR_EARLY", 3);
     a.early = early_env & 2 ? 1 : 0;
     static const int epi_env = RT_TUNE("REFTR_EPI", 3);
     a.epi_lds = epi_env & 2 ? 1 : 0;
-    a.dy_bytes = (unsigned)(M * d->N * 2);
-    a.x_bytes = (unsigned)((long long)d->B * d->SH * d->SW * d->SC * 2);
     return RT_OK;
 }
 
@@ -898,21 +837,21 @@ extern "C" int rt_conv_wgrad(const rt_conv_wgrad_desc* d, rt_stream_t stream) {
 }
 
 static int conv_wgrad_impl(const rt_conv_wgrad_desc* d, rt_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const WgRoute route = wg_route(*d);
+    if (route == WG_V2) {                                  // a group of one (rt_w2_eligible has checked the geometry, with its own channel granularity)
+        const int zero = 0;
+        return rt_w2_run(d, &zero, 1, d->workspace, d->workspace ? (long long)d->workspace_bytes : 0, s);
+    }
     WgradArgs a;
     const int frc = fill_wgrad_args(d, a);
     if (frc != RT_OK) return frc;
-    hipStream_t s = (hipStream_t)stream;
-    const WgRoute route = wg_route(*d);
     if (route == WG_SMALL_M) {
         const size_t total = (size_t)a.N * (a.SC >> 2);
         int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(small_m_wgrad_kernel, dim3(blocks), dim3(256), 0, s, a.dy, a.x, a.dw, a.scale, a.dbias, a.M, a.N, a.SC, a.overwrite);
         RT_CHECK_LAUNCH();
         return RT_OK;
-    }
-    if (route == WG_V2) {                                  // a group of one
-        const int zero = 0;
-        return rt_w2_run(d, &zero, 1, d->workspace, d->workspace ? (long long)d->workspace_bytes : 0, s);
     }
     float* ws = d->workspace; long long wsb = d->workspace ? d->workspace_bytes : 0;
     static const int no_ws = RT_TUNE("REFTR_WG_NOWS", 0);

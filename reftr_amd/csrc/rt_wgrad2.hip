@@ -14,20 +14,19 @@
 //     adjacent) is dealt to the 8 XCDs in contiguous runs of gridDim.x / 8 tasks (block id -> rt_xcd_remap) instead of the
 //     hardware's round-robin: the same number of tasks per XCD as the plain map (an XCD is 32 CUs: one task more than its
 //     share is a whole extra round), but a split's tiles and taps share one XCD's L2 -- fabric fetches 3.39 -> 1.89 GB over
-//     the ResNet groups at equal time, the transformer groups 15 % faster.  (A table that put whole units on XCDs round-robin,
-//     REFTR_W2_XCD=1, cut the fetches as much and lost 30 % to that imbalance.)
+//     the ResNet groups at equal time, the transformer groups 15 % faster.  (A table that put whole units on XCDs round-robin
+//     cut the fetches as much and lost 30 % to that imbalance: profiles/r02_w2_placement_probes.txt.)
 //   * software pipeline: one barrier per 32-row chunk, NS-1 chunks of LDS-DMA in flight, and the fragment reads of the next
 //     16-row step (including the first step of the NEXT chunk) are issued before the MFMAs of the current one;
-//   * wave-specialised L2 prefetch: waves 0-3 issue the stage DMAs; waves 4-7 touch every 128-B line of the chunk `pf`
-//     iterations ahead of its DMA with a 4-byte LDS-DMA into a scratch word and NEVER wait for those (vmcnt completes in
-//     order, so a wave that also had to wait for stage DMAs could not run its touches ahead), so the stage requests find their
-//     lines in L2: a miss costs 2-3 us under load and only NS-1 stages = 96 KB per CU can be in flight, a touch needs no LDS.
+//   * waves 0-3 issue the stage DMAs (4 waves x 1 KB per round) and wait for them; all eight waves multiply.  (Having waves 4-7
+//     touch the lines of later chunks into L2 ahead of the DMAs did not pay: LAB_NOTES.md, negative results.)
 // Operand staging, as before: both operands keep their natural [pixel][channel] layout, go global -> LDS by DMA
 // (buffer_load_dwordx4 ... lds, 16 B per lane, lane-linear), and become MFMA fragments through the LDS transpose read
 // (ds_read_b64_tr_b16).  The DMA cannot scatter, so the bank swizzle (16-B slot ^= (row & 3) << 2: the four rows x 64 B a
 // 32-lane half of the transpose read touches land on four different 64-B bank groups) is applied to the SOURCE address.
 #include "rt_common.h"
 #include "rt_lds.h"
+#include "rt_wgrad_tile.h"
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -35,18 +34,22 @@ namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-struct W2Prob {
-    const bf16_t* dy; const bf16_t* x; float* dw; const float* scale; float* dbias; float* part; float* sqacc; bf16_t* g16;
-    int SH, SW, SC, DH, DW, N, KH, KW, stride, pad, M, dil;
+struct W2Prob : WgGeom {
+    float* part; float* sqacc; bf16_t* g16;
     int n_tiles, c_tiles, tiles, splits, chunks_per_split, out_elems;
-    unsigned dy_bytes, x_bytes;
-    int simple, accumulate, xrot, cfg;
+    int simple, accumulate, cfg;
 };
 constexpr int W2_MAXP = 20;
-// cum[x][i]: workgroups of problems 0 .. i-1 that run on XCD x (block id b -> XCD b & 7, position b >> 3 in its order)
-struct W2Group { W2Prob p[W2_MAXP]; int cum[8][W2_MAXP + 1]; int n; int xcd; int abl; int pf; int remap; };
+// cum[i]: tile tasks (tiles x splits) of problems 0 .. i-1 in the linear task order
+struct W2Group {
+    W2Prob p[W2_MAXP]; int cum[W2_MAXP + 1]; int n;
+#ifdef RT_LAB
+    int abl, remap;       // REFTR_W2_ABL (ablation probes, wrong results), REFTR_W2_XCD (0: the hardware's round-robin placement)
+#endif
+};
 
-__device__ __forceinline__ int w2_swz(int row) { return (row & 3) << 2; }
+struct W2Swz { static __device__ __forceinline__ int of(int row) { return (row & 3) << 2; } };
+__device__ __forceinline__ int w2_swz(int row) { return W2Swz::of(row); }
 
 // BN x BC output tile, WN x WC waves (WN * WC == 8), CR contraction rows per stage, NS stages.
 // TAPS = 3 (3x3, stride 1, pad 1 only): a workgroup accumulates the three kw taps of ONE kernel row kh of its output tile.  For a
@@ -57,7 +60,7 @@ __device__ __forceinline__ int w2_swz(int row) { return (row & 3) << 2; }
 // removed by AND-ing the x fragments with a row mask (ballot of the validity of the chunk's 32 rows per tap, expanded through a
 // 256-entry LDS table: byte of 8 row bits -> 8 x 16-bit lanes).  3x the flop per staged byte and per dy fragment read.
 template <int BN, int BC, int WN, int WC, int CR, int NS, bool SIMPLE, int TAPS = 1>
-__device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const int tile, const int abl, const int pf) {
+__device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const int tile, const int abl) {
     static_assert(WN * WC == 8, "8 waves");
     constexpr bool FUSED = TAPS == 3;
     static_assert(TAPS == 1 || (TAPS == 3 && !SIMPLE), "taps");
@@ -72,9 +75,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
     constexpr int LPT = AJ + BJ;
     constexpr int KS = CR / 16;
     static_assert(KS == 2, "the software pipeline below is written for two 16-row steps per chunk");
-    constexpr int OOB = 0x7fffffff;
-    constexpr int PFA = CR * RBA / 128, PFB = CR * RBB / 128;    // 128-B lines of a chunk (one per thread of waves 4-7)
-    static_assert(PFA + PFB <= 256, "prefetch lines");
+    constexpr int OOB = WG_OOB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -82,18 +83,10 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
     const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wn = wave % WN, wc = wave / WN;
 
-    const int tile_n = tile % p.n_tiles;
-    const int rest = tile / p.n_tiles;
-    const int tile_c = rest % p.c_tiles;
-    const int tap = rest / p.c_tiles;
-    const int kh = tap / p.KW, kw = tap - kh * p.KW;
-    const int n0 = tile_n * BN, c0 = tile_c * BC;
-
-    const int total_chunks = (p.M + CR - 1) / CR;
-    const int chunk_begin = split * p.chunks_per_split;
-    int chunk_end = chunk_begin + p.chunks_per_split;
-    if (chunk_end > total_chunks) chunk_end = total_chunks;
-    const int nch = chunk_end - chunk_begin;
+    const WgTile tl = wg_tile<BN, BC>(tile, p.n_tiles, p.c_tiles, p.KW);
+    const int tile_c = tl.tile_c, tap = tl.tap, kh = tl.kh, kw = tl.kw, n0 = tl.n0, c0 = tl.c0;
+    const WgChunks ck = wg_chunks<CR>(p.M, split, p.chunks_per_split);
+    const int chunk_begin = ck.begin, chunk_end = ck.end, nch = chunk_end - chunk_begin;
 
     // ---- DMA source offsets (loop-invariant, relative to the chunk's first row); LDS destination is lane-linear
     int voff_a[AJ];
@@ -119,24 +112,6 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
             gx[j] = m % p.DW; const int tmp = m / p.DW; gy[j] = tmp % p.DH; gb[j] = tmp / p.DH;
         }
     }
-    // ---- L2 prefetch touch (waves 4-7): thread u = t - 256 owns the u-th 128-B line of a chunk (dy lines first, then x lines).
-    // For the gather path the x rows of a stride-1 tap are the chunk's rows shifted by (kh - pad) * SW + (kw - pad) pixels
-    // (image borders ignored: a few lines too many); stride-2 gathers are not prefetched.
-    int voff_pf = OOB;
-    const bool pf_is_a = (wave - 4) * 64 < PFA;            // wave-uniform: PFA and PFB are multiples of 64
-    if (t >= 256) {
-        const int u = t - 256;
-        if (u < PFA) {
-            const int r = u / (RBA / 128), col = n0 * 2 + (u % (RBA / 128)) * 128;
-            if (col < p.N * 2) voff_pf = r * p.N * 2 + col;
-        } else if (u < PFA + PFB) {
-            const int v = u - PFA;
-            const int r = v / (RBB / 128), col = c0 * 2 + (v % (RBB / 128)) * 128;
-            if (col < p.SC * 2 && (SIMPLE || p.stride == 1)) voff_pf = r * p.SC * 2 + col;
-        }
-    }
-    const int pf_shift = SIMPLE ? 0 : ((kh * p.dil - p.pad) * p.SW + (kw * p.dil - p.pad)) * p.SC * 2;       // bytes
-
     f32x16 acc[TAPS][TN][TC];
 #pragma unroll
     for (int tp = 0; tp < TAPS; ++tp)
@@ -147,7 +122,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[tp][a][b][r] = 0.f;
 
-    const bool do_bias = p.dbias && tile_c == 0 && tap == 0;      // fused: tap = kh, kernel row 0 holds tap 0
+    const bool do_bias = wg_do_bias(p.dbias, tl);      // fused: tap = kh, kernel row 0 holds tap 0
 
     // ---- fused taps: row-mask table (byte of 8 row bits -> eight 16-bit lanes) and the (h, w) of this lane's row of the chunk
     // whose fragments are read next
@@ -179,16 +154,14 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
     float bsum = 0.f;
 
     const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)(wave & 3) * 1024u;
-    const unsigned lds_pf = (unsigned)(uintptr_t)(lds_ptr)smem + (unsigned)(NS * BUF_BYTES) + (unsigned)(wave & 3) * 256u;
     const i32x4 rs_x_abs = rt_make_rsrc(p.x, p.x_bytes);
     int lc = chunk_begin;
 
-    auto issue_dma = [&](int stage) __attribute__((always_inline)) {             // waves 0-3
+    const bool dma_wave = wave < 4;
+    auto issue = [&](int stage) __attribute__((always_inline)) {                 // waves 0-3
+        if (!dma_wave) return;
         const unsigned bA = lds0 + stage * BUF_BYTES, bB = bA + A_BYTES;
-        const unsigned aoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.N;
-        const i32x4 rs_dy = rt_make_rsrc(reinterpret_cast<const unsigned char*>(p.dy) + aoff, p.dy_bytes - aoff);
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) rt_dma16(rs_dy, bA + j * 4096, voff_a[j]);
+        wg_issue_rows<CR>(p.dy, p.dy_bytes, p.N, lc, bA, voff_a);
         const bool last = (lc + 1 >= chunk_end);
         if (FUSED) {
             // rows g0 .. g0 + 33 of x (flat pixel index, may start before the tensor / end behind it: those rows read as zero)
@@ -199,12 +172,8 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
                 if (off < 0) off = OOB;
                 rt_dma16(rs_x_abs, bB + j * 4096, off);
             }
-        } else if (SIMPLE) {
-            const unsigned xoff = (unsigned)lc * (unsigned)(CR * 2) * (unsigned)p.SC;
-            const i32x4 rs_x = rt_make_rsrc(reinterpret_cast<const unsigned char*>(p.x) + xoff, p.x_bytes - xoff);
-#pragma unroll
-            for (int j = 0; j < BJ; ++j) rt_dma16(rs_x, bB + j * 4096, voff_b[j]);
-        } else {
+        } else if (SIMPLE) wg_issue_rows<CR>(p.x, p.x_bytes, p.SC, lc, bB, voff_b);
+        else {      // (the walker and the offset set-up are written out here: through rt_wgrad_tile.h's they measured slower, profiles/wgrad_kernels_bench.txt)
 #pragma unroll
             for (int j = 0; j < BJ; ++j) {
                 const int m = lc * CR + b_r[j];
@@ -220,27 +189,6 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
         }
         if (!last) ++lc;
     };
-    auto issue_touch = [&]() __attribute__((always_inline)) {                     // waves 4-7: chunk lc + pf, never waited for
-        const int pc = lc + pf;
-        const bool on = pc < chunk_end;                     // wave-uniform: the descriptor below must live in SGPRs
-        if (pf_is_a) {
-            const unsigned off = (unsigned)pc * (unsigned)(CR * 2) * (unsigned)p.N;
-            const i32x4 rs = rt_make_rsrc_uniform(reinterpret_cast<const unsigned char*>(p.dy) + (on ? off : 0u), on ? p.dy_bytes - off : 0u);
-            rt_dma4(rs, lds_pf, voff_pf);
-        } else {
-            const long long off = (long long)pc * (CR * 2) * p.SC + pf_shift;
-            const bool in = on && off >= 0 && off < (long long)p.x_bytes;
-            const i32x4 rs = rt_make_rsrc_uniform(reinterpret_cast<const unsigned char*>(p.x) + (in ? off : 0), in ? p.x_bytes - (unsigned)off : 0u);
-            rt_dma4(rs, lds_pf, voff_pf);
-        }
-        if (lc + 1 < chunk_end) ++lc;
-    };
-    const bool dma_wave = wave < 4;
-    auto issue = [&](int stage) __attribute__((always_inline)) {
-        if (dma_wave) issue_dma(stage);
-        else if (pf > 0) issue_touch();
-    };
-
     // ---- transpose-read addresses.  16-lane group g = lane >> 4: channel block (g & 1) * 16, k block g >> 1 (8 rows);
     // lane i of a group supplies row (i >> 2) of a 4-row block and the 8 bytes of channels 4 * (i & 3) .. + 3.
     const int g = lane >> 4, li = lane & 15;
@@ -311,18 +259,6 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
                 for (int b = 0; b < TC; ++b)
                     acc[q][a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a], bfr[q][b], acc[q][a][b], 0, 0, 0);
     };
-    auto bias_rows = [&](int stage) __attribute__((always_inline)) {
-        // fused bias gradient: column sums of the dy tile that is in LDS (512 threads: BN columns x 512 / BN row groups)
-        const unsigned char* bA = smem + stage * BUF_BYTES;
-        constexpr int TPC = 512 / BN, RPT = CR / TPC;
-        const int col = t % BN, r0 = (t / BN) * RPT;
-#pragma unroll
-        for (int r = 0; r < RPT; ++r) {
-            const int row = r0 + r;
-            bsum += (float)*reinterpret_cast<const bf16_t*>(bA + row * RBA + ((((col >> 3) ^ w2_swz(row)) << 4) | ((col & 7) * 2)));
-        }
-    };
-
     // ---- main loop.  Stages hold chunks c .. c+NS-1 at the top of iteration c.  Per iteration:
     //   reads(c, step 1) | MFMA(c, step 0) | wait chunk c+1, BARRIER (chunk c+1 visible; nobody reads chunk c any more)
     //   | DMA chunk c+NS into chunk c's stage | reads(c+1, step 0) | MFMA(c, step 1)
@@ -341,7 +277,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
         const int nbuf = cbuf + 1 == NS ? 0 : cbuf + 1;
         if (!(abl & 2)) {
             load_frags(cbuf, 1, fa1, fb1);
-            if (do_bias) bias_rows(cbuf);
+            if (do_bias) wg_bias_cols<BN, CR, 512, RBA, W2Swz>(smem + cbuf * BUF_BYTES, t, bsum);
             mma(fa0, fb0);
         }
         if (dma_wave && !(abl & 1)) rt_wait_vmcnt<(NS - 2) * LPT>();      // this thread's pieces of chunk c+1 have landed
@@ -356,10 +292,7 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
     }
     rt_wait_vmcnt<0>();
 
-    if (do_bias) {
-        const int n = n0 + t % BN;
-        if (n < p.N) atomicAdd(p.dbias + n, bsum);
-    }
+    if (do_bias) wg_bias_commit<BN>(p.dbias, n0, p.N, t, bsum);
     // ---- epilogue.  C/D layout of the 32x32 MFMA: lane l holds column (l & 31) = input channel c and rows
     // (r & 3) + 8 * (r >> 2) + 4 * (l >> 5) = output channel n.  Each wave turns its 32-row blocks around through its own slice
     // of the (dead) stage memory, so that every global access is a 16-B piece of ONE output row per lane -- a wave instruction
@@ -421,45 +354,31 @@ __device__ __forceinline__ void w2_body(const W2Prob& p, const int split, const 
 // with four tails and four reductions.
 template <int CR, int NS>
 __global__ __launch_bounds__(512, 1) void w2_grouped_kernel(const W2Group g) {
-    // block id -> XCD x = id & 7 (hardware round-robin), position q = id >> 3 in that XCD's order -> (problem, split, tile):
-    // problem i owns positions [cum[x][i], cum[x][i+1]); inside, its row splits s with (s + xrot) % 8 == x follow each other,
-    // each with all of its tiles adjacent (they read the same dy / x rows: one trip over the fabric per XCD-resident split).
-    const int x = (int)blockIdx.x & 7, q = (int)blockIdx.x >> 3;
-    // remap (REFTR_W2_XCD=2): the linear task order (problem, row split, tile -- the tasks that read the same rows are adjacent) is
-    // dealt to the XCDs in CONTIGUOUS runs of gridDim.x / 8 instead of round-robin: same task count per XCD as the linear map
-    // (no balance cost), but a split's tiles / taps share one XCD's L2
-    const int b = g.remap ? rt_xcd_remap((int)blockIdx.x, (int)gridDim.x, 1) : (int)blockIdx.x;
-    int lo = 0, hi = g.n;
-    if (g.xcd) {
-        if (q >= g.cum[x][g.n]) return;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (g.cum[x][mid] <= q) lo = mid; else hi = mid; }
-    } else {
-        if (b >= g.cum[0][g.n]) return;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (g.cum[0][mid] <= b) lo = mid; else hi = mid; }
-    }
-    lo = __builtin_amdgcn_readfirstlane(lo);
+#ifdef RT_LAB
+    const int abl = g.abl, remap = g.remap;
+#else
+    constexpr int abl = 0, remap = 1;
+#endif
+    // The linear task order (problem, row split, tile -- the tasks that read the same rows are adjacent) is dealt to the XCDs in
+    // CONTIGUOUS runs of gridDim.x / 8 instead of round-robin: same task count per XCD (no balance cost), but a split's tiles /
+    // taps share one XCD's L2
+    const int b = rt_xcd_remap((int)blockIdx.x, (int)gridDim.x, remap);
+    const int lo = __builtin_amdgcn_readfirstlane(rt_job_of(g.cum, g.n, b));
     const W2Prob& p = g.p[lo];
-    int split, tile;
-    if (g.xcd) {
-        const int local = q - g.cum[x][lo];
-        tile = local % p.tiles;
-        split = ((x - p.xrot) & 7) + 8 * (local / p.tiles);
-    } else {
-        const int local = b - g.cum[0][lo];
-        split = local / p.tiles; tile = local - split * p.tiles;
-    }
-    split = __builtin_amdgcn_readfirstlane(split); tile = __builtin_amdgcn_readfirstlane(tile);
+    const int local = b - g.cum[lo];
+    const int split = __builtin_amdgcn_readfirstlane(local / p.tiles);
+    const int tile = __builtin_amdgcn_readfirstlane(local - (local / p.tiles) * p.tiles);
     const int sel = __builtin_amdgcn_readfirstlane(p.cfg * 2 + (p.simple ? 1 : 0));
     switch (sel) {
-        case 0: w2_body<256, 256, 4, 2, CR, NS, false>(p, split, tile, g.abl, g.pf); break;
-        case 1: w2_body<256, 256, 4, 2, CR, NS, true>(p, split, tile, g.abl, g.pf); break;
-        case 2: w2_body<128, 256, 2, 4, CR, NS, false>(p, split, tile, g.abl, g.pf); break;
-        case 3: w2_body<128, 256, 2, 4, CR, NS, true>(p, split, tile, g.abl, g.pf); break;
-        case 4: w2_body<256, 128, 4, 2, CR, NS, false>(p, split, tile, g.abl, g.pf); break;
-        case 5: w2_body<256, 128, 4, 2, CR, NS, true>(p, split, tile, g.abl, g.pf); break;
-        case 6: w2_body<128, 128, 2, 4, CR, NS, false>(p, split, tile, g.abl, g.pf); break;
-        case 7: w2_body<128, 128, 2, 4, CR, NS, true>(p, split, tile, g.abl, g.pf); break;
-        default: w2_body<128, 128, 2, 4, CR, NS, false, 3>(p, split, tile, g.abl, 0); break;      // cfg 4: three taps per workgroup
+        case 0: w2_body<256, 256, 4, 2, CR, NS, false>(p, split, tile, abl); break;
+        case 1: w2_body<256, 256, 4, 2, CR, NS, true>(p, split, tile, abl); break;
+        case 2: w2_body<128, 256, 2, 4, CR, NS, false>(p, split, tile, abl); break;
+        case 3: w2_body<128, 256, 2, 4, CR, NS, true>(p, split, tile, abl); break;
+        case 4: w2_body<256, 128, 4, 2, CR, NS, false>(p, split, tile, abl); break;
+        case 5: w2_body<256, 128, 4, 2, CR, NS, true>(p, split, tile, abl); break;
+        case 6: w2_body<128, 128, 2, 4, CR, NS, false>(p, split, tile, abl); break;
+        case 7: w2_body<128, 128, 2, 4, CR, NS, true>(p, split, tile, abl); break;
+        default: w2_body<128, 128, 2, 4, CR, NS, false, 3>(p, split, tile, abl); break;      // cfg 4: three taps per workgroup
     }
 }
 
@@ -496,7 +415,7 @@ __global__ __launch_bounds__(256) void w2_reduce_kernel(const W2Reduce g) {
 
 template <int CR, int NS>
 int w2_launch(const W2Group& g, int blocks, hipStream_t s) {
-    constexpr size_t smem = (size_t)NS * CR * (256 + 256) * 2 + 4 * 256;      // the largest configuration's stages + the prefetch scratch words
+    constexpr size_t smem = (size_t)NS * CR * (256 + 256) * 2 + 4 * 256;      // the largest configuration's stages (+ 1 KB nothing uses: the request is kept as measured)
     static_assert((size_t)NS * (CR * 256 + 48 * 256) + 4096 <= smem, "fused-tap stages + mask table");
     static bool attr_done = false;
     if (!attr_done) {
@@ -513,10 +432,10 @@ int w2_launch(const W2Group& g, int blocks, hipStream_t s) {
 // Eligibility: channel counts the DMA path can address in 16-B pieces, enough rows for the pipeline to matter.
 bool rt_w2_eligible(const rt_conv_wgrad_desc& d) {
     static const int minm_env = RT_TUNE("REFTR_W2_MINM", 256);
-    const long long M = (long long)d.B * d.DH * d.DW;
-    if (M < minm_env || (d.N & 7) || (d.SC & 7) || d.N < 64 || d.SC < 64) return false;
+    WgGeom g;
+    if (wg_fill_geom(d, g, 7, 7) != RT_OK) return false;
+    if (g.M < minm_env || d.N < 64 || d.SC < 64) return false;
     if (d.variant != 0 || d.msplit > 0) return false;
-    if (M * d.N >= 0x3fffffffLL || (long long)d.B * d.SH * d.SW * d.SC >= 0x3fffffffLL) return false;
     if ((long long)d.N * d.KH * d.KW * d.SC >= 0x7fffffffLL) return false;
     return true;
 }
@@ -534,42 +453,56 @@ static int w2_cfg_of(const rt_conv_wgrad_desc& d) {       // 0: 256x256, 1: 128x
     return n_big ? (c_big ? 0 : 2) : (c_big ? 1 : 3);
 }
 
+constexpr int W2_CR = 32;
+static const double* w2_wts() {         // cost of one chunk of a tile task per configuration, in 128x128-tile units (lab: REFTR_W2_WTS="a,b,c,d,e")
+    static double wts[5] = {4, 2, 2, 1, 3};
+#ifdef RT_LAB
+    static const bool read = [] { if (const char* e = getenv("REFTR_W2_WTS")) sscanf(e, "%lf,%lf,%lf,%lf,%lf", &wts[0], &wts[1], &wts[2], &wts[3], &wts[4]); return true; }();
+#endif
+    return wts;
+}
+
+// The launch policy of one problem: its tile configuration and tile tasks, its row chunks, and into how many row splits it is cut when
+// a workgroup should own `per_wg` weighted chunks (per_wg <= 0: the group has enough tile tasks, nothing is cut) -- at least
+// REFTR_W2_MINROWS rows per split.
+struct W2Plan { int cfg, n_tiles, c_tiles, tiles, total_chunks, splits; };
+static W2Plan w2_plan(const rt_conv_wgrad_desc& d, double per_wg) {
+    static const int minrows_env = RT_TUNE("REFTR_W2_MINROWS", 256);
+    static const int BNs[5] = {256, 128, 256, 128, 128}, BCs[5] = {256, 256, 128, 128, 128};
+    W2Plan pl;
+    pl.cfg = w2_cfg_of(d);
+    const long long M = (long long)d.B * d.DH * d.DW;
+    pl.n_tiles = (d.N + BNs[pl.cfg] - 1) / BNs[pl.cfg]; pl.c_tiles = (d.SC + BCs[pl.cfg] - 1) / BCs[pl.cfg];
+    pl.tiles = pl.n_tiles * pl.c_tiles * (pl.cfg == 4 ? 3 : d.KH * d.KW);
+    pl.total_chunks = (int)((M + W2_CR - 1) / W2_CR);
+    pl.splits = 1;
+    if (per_wg > 0) {
+        pl.splits = (int)((double)pl.total_chunks * w2_wts()[pl.cfg] / per_wg + 0.5);
+        const int maxs = (int)(M / minrows_env);
+        if (pl.splits > maxs) pl.splits = maxs;
+        if (pl.splits < 1) pl.splits = 1;
+    }
+    return pl;
+}
+// `splits` asked for -> chunks per split and the number of splits that are not empty
+static int w2_cut(int total_chunks, int splits, int& chunks_per_split) {
+    chunks_per_split = (total_chunks + splits - 1) / splits;
+    return (total_chunks + chunks_per_split - 1) / chunks_per_split;
+}
+
 // Launches every descriptor of `idx` (all eligible) as grouped v2 launches.  Split policy: see the file header.
 int rt_w2_run(const rt_conv_wgrad_desc* descs, const int* idx, int n, float* workspace, long long workspace_bytes, hipStream_t s) {
     static const int target_env = RT_TUNE("REFTR_W2_TARGET", 0);
-    static const int xcd_env = RT_TUNE("REFTR_W2_XCD", 2);      // 0 linear, 1 per-XCD table (round-robin units), 2 contiguous runs
-    static const int minrows_env = RT_TUNE("REFTR_W2_MINROWS", 256);
-#ifdef RT_LAB                                      // lab builds only (hipcc -DRT_LAB): ablation probes, wrong results
-    static const int abl_env = RT_TUNE("REFTR_W2_ABL", 0);
-#else
-    constexpr int abl_env = 0;
-#endif
-    static const int pf_env = RT_TUNE("REFTR_W2_PF", 0);
-    constexpr int CR = 32;
-    static const int BNs[5] = {256, 128, 256, 128, 128}, BCs[5] = {256, 256, 128, 128, 128};
-    static double wts[5] = {4, 2, 2, 1, 3};                   // cost of one chunk of a tile task, in 128x128-tile units (REFTR_W2_WTS="a,b,c,d,e")
-    static bool wts_done = false;
-    if (!wts_done) {
-#ifdef RT_LAB
-        if (const char* e = getenv("REFTR_W2_WTS")) sscanf(e, "%lf,%lf,%lf,%lf,%lf", &wts[0], &wts[1], &wts[2], &wts[3], &wts[4]);
-#endif
-        wts_done = true;
-    }
-    static const int slots[4] = {256, 256, 256, 512};         // resident workgroups on the chip (LDS: 130 / 98 / 98 / 66 KB each)
+    const int target = target_env > 0 ? target_env : 256;       // resident workgroups on the chip (one per CU: 130 KB of LDS each)
     for (int base = 0; base < n; base += W2_MAXP) {         // one launch (and one split policy) per W2_MAXP problems
         // ---- group-level split policy: cut the m axis only while the group has fewer tile tasks than resident slots; work is
         // counted in 128x128-tile chunk units so that problems of different tile configurations end up with equally long workgroups
         const int* list = idx + base; const int m = n - base < W2_MAXP ? n - base : W2_MAXP;
         long long tiles_total = 0; double work = 0;
         for (int k = 0; k < m; ++k) {
-            const rt_conv_wgrad_desc& d = descs[list[k]];
-            const int cfg = w2_cfg_of(d); const int BN = BNs[cfg], BC = BCs[cfg];
-            const long long M = (long long)d.B * d.DH * d.DW;
-            const long long tl = (long long)((d.N + BN - 1) / BN) * ((d.SC + BC - 1) / BC) * (cfg == 4 ? 3 : d.KH * d.KW);
-            tiles_total += tl; work += (double)tl * (double)((M + CR - 1) / CR) * (double)wts[cfg];
+            const W2Plan pl = w2_plan(descs[list[k]], 0);
+            tiles_total += pl.tiles; work += (double)pl.tiles * (double)pl.total_chunks * w2_wts()[pl.cfg];
         }
-        const int cfg = 0;
-        const int target = target_env > 0 ? target_env : slots[cfg];
         double per_wg = work / (double)target;                // chunks a workgroup should own so that ~`target` workgroups cover the group
         // The per-problem rounding of the split counts must not push the launch over the resident slots: a 257th workgroup of
         // a long task is a whole extra task time for everybody (measured: a layer3 stage went from 288 to 352 us).  Coarsen
@@ -579,33 +512,23 @@ int rt_w2_run(const rt_conv_wgrad_desc* descs, const int* idx, int n, float* wor
             for (int it = 0; it < 24; ++it) {
                 long long total = 0;
                 for (int k = 0; k < m; ++k) {
-                    const rt_conv_wgrad_desc& d = descs[list[k]];
-                    const int cfg = w2_cfg_of(d); const int BN = BNs[cfg], BC = BCs[cfg];
-                    const long long M = (long long)d.B * d.DH * d.DW;
-                    const long long tl = (long long)((d.N + BN - 1) / BN) * ((d.SC + BC - 1) / BC) * (cfg == 4 ? 3 : d.KH * d.KW);
-                    const int total_chunks = (int)((M + CR - 1) / CR);
-                    int sp = (int)((double)total_chunks * (double)wts[cfg] / per_wg + 0.5);
-                    const int maxs = (int)(M / minrows_env);
-                    if (sp > maxs) sp = maxs;
-                    if (sp < 1) sp = 1;
-                    const int cps = (total_chunks + sp - 1) / sp;
-                    total += tl * ((total_chunks + cps - 1) / cps);
+                    const W2Plan pl = w2_plan(descs[list[k]], per_wg);
+                    int cps;
+                    total += (long long)pl.tiles * w2_cut(pl.total_chunks, pl.splits, cps);
                 }
                 if (total <= target) break;
                 per_wg *= 1.03;
             }
         }
-        W2Group g; W2Reduce r; g.n = 0; r.n = 0; g.xcd = xcd_env == 1; g.remap = xcd_env == 2; g.abl = abl_env; g.pf = pf_env;
+        W2Group g; W2Reduce r; g.n = 0; r.n = 0; g.cum[0] = 0;
+#ifdef RT_LAB
+        static const int abl_env = RT_TUNE("REFTR_W2_ABL", 0), xcd_env = RT_TUNE("REFTR_W2_XCD", 2);
+        g.abl = abl_env; g.remap = xcd_env != 0;
+#endif
         int rblocks = 0; long long ws_off = 0;
-        double xload[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int xcount[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lin_total = 0;
-        for (int x = 0; x < 8; ++x) g.cum[x][0] = 0;
         auto flush = [&]() -> int {
             if (g.n > 0) {
-                int blocks;
-                if (xcd_env == 1) { int mx = 0; for (int x = 0; x < 8; ++x) if (xcount[x] > mx) mx = xcount[x]; blocks = mx * 8; }
-                else blocks = lin_total;
-                const int rc = w2_launch<CR, 4>(g, blocks, s);
+                const int rc = w2_launch<W2_CR, 4>(g, g.cum[g.n], s);
                 if (rc != RT_OK) return rc;
             }
             if (r.n > 0) {
@@ -613,33 +536,21 @@ int rt_w2_run(const rt_conv_wgrad_desc* descs, const int* idx, int n, float* wor
                 hipLaunchKernelGGL(w2_reduce_kernel, dim3((unsigned)rblocks), dim3(256), 0, s, r);
                 RT_CHECK_LAUNCH();
             }
-            g.n = 0; r.n = 0; rblocks = 0; ws_off = 0; lin_total = 0;
-            for (int x = 0; x < 8; ++x) { xload[x] = 0; xcount[x] = 0; g.cum[x][0] = 0; }
+            g.n = 0; r.n = 0; rblocks = 0; ws_off = 0;
             return RT_OK;
         };
         for (int k = 0; k < m; ++k) {
             const rt_conv_wgrad_desc& d = descs[list[k]];
+            const W2Plan pl = w2_plan(d, tiles_total < target ? per_wg : 0);
             W2Prob p;
-            p.cfg = w2_cfg_of(d);
-            const int BN = BNs[p.cfg], BC = BCs[p.cfg];
-            p.dy = (const bf16_t*)d.dy; p.x = (const bf16_t*)d.x; p.dw = d.dw; p.scale = d.scale; p.dbias = d.dbias; p.part = nullptr; p.sqacc = d.sqacc; p.g16 = (bf16_t*)d.g16;
-            p.SH = d.SH; p.SW = d.SW; p.SC = d.SC; p.DH = d.DH; p.DW = d.DW; p.N = d.N; p.KH = d.KH; p.KW = d.KW; p.stride = d.stride; p.pad = d.pad; p.dil = d.dil > 1 ? d.dil : 1;
-            const long long M = (long long)d.B * d.DH * d.DW;
-            p.M = (int)M;
-            p.n_tiles = (d.N + BN - 1) / BN; p.c_tiles = (d.SC + BC - 1) / BC;
-            p.tiles = p.n_tiles * p.c_tiles * (p.cfg == 4 ? 3 : d.KH * d.KW);
+            const int grc = wg_fill_geom(d, p, 7, 7);
+            if (grc != RT_OK) return grc;
+            p.part = nullptr; p.sqacc = d.sqacc; p.g16 = (bf16_t*)d.g16;
+            p.cfg = pl.cfg; p.n_tiles = pl.n_tiles; p.c_tiles = pl.c_tiles; p.tiles = pl.tiles;
             p.out_elems = d.N * d.KH * d.KW * d.SC;
-            p.dy_bytes = (unsigned)(M * d.N * 2); p.x_bytes = (unsigned)((long long)d.B * d.SH * d.SW * d.SC * 2);
             p.simple = (d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad == 0) ? 1 : 0;
             p.accumulate = d.overwrite ? 0 : 1;
-            const int total_chunks = (int)((M + CR - 1) / CR);
-            int splits = 1;
-            if (tiles_total < target) {
-                splits = (int)((double)total_chunks * (double)wts[p.cfg] / per_wg + 0.5);
-                const int maxs = (int)(M / minrows_env);
-                if (splits > maxs) splits = maxs;
-                if (splits < 1) splits = 1;
-            }
+            int splits = pl.splits;
             long long need = splits > 1 ? (long long)splits * p.out_elems * 4 : 0;
             if (need > 0 && (p.out_elems & 3)) { splits = 1; need = 0; }
             if (need > workspace_bytes) {                 // never larger than the caller's scratch
@@ -651,8 +562,7 @@ int rt_w2_run(const rt_conv_wgrad_desc* descs, const int* idx, int n, float* wor
                 const int frc = flush();
                 if (frc != RT_OK) return frc;
             }
-            p.chunks_per_split = (total_chunks + splits - 1) / splits;
-            p.splits = (total_chunks + p.chunks_per_split - 1) / p.chunks_per_split;
+            p.splits = w2_cut(pl.total_chunks, splits, p.chunks_per_split);
             if (p.splits > 1 && workspace) {
                 p.part = workspace + ws_off / 4;
                 r.part[r.n] = p.part; r.dw[r.n] = p.dw; r.scale[r.n] = p.scale; r.sqacc[r.n] = p.sqacc; r.g16[r.n] = p.g16; r.out_elems[r.n] = p.out_elems;
@@ -660,23 +570,12 @@ int rt_w2_run(const rt_conv_wgrad_desc* descs, const int* idx, int n, float* wor
                 rblocks += (p.out_elems / 4 + 255) / 256;
                 ws_off += ((long long)p.splits * p.out_elems * 4 + 255) / 256 * 256;
             } else if (p.splits > 1) {                    // no scratch: do not split
-                p.splits = 1; p.chunks_per_split = total_chunks;
-            }
-            // XCD placement: split s -> XCD (s + xrot) % 8; xrot = the XCD with the least work so far in this launch
-            int best = 0;
-            for (int x = 1; x < 8; ++x) if (xload[x] < xload[best]) best = x;
-            p.xrot = xcd_env == 1 ? best : 0;
-            for (int x = 0; x < 8; ++x) {
-                const int j0 = (x - p.xrot) & 7;                                  // first split of this problem on XCD x
-                const int cnt = j0 < p.splits ? (p.splits - j0 + 7) / 8 : 0;      // splits j0, j0 + 8, ...
-                xcount[x] += cnt * p.tiles; xload[x] += (double)cnt * p.tiles * p.chunks_per_split;
-                g.cum[x][g.n + 1] = xcount[x];
+                p.splits = 1; p.chunks_per_split = pl.total_chunks;
             }
             static const int dbg_env = RT_TUNE("REFTR_W2_DEBUG", 0);
             if (dbg_env) fprintf(stderr, "[w2] M=%d N=%d C=%d k=%d s=%d cfg=%d tiles=%d splits=%d chunks/split=%d  (group tiles %lld, per_wg %.0f)\n",
                                  p.M, p.N, p.SC, p.KH, p.stride, p.cfg, p.tiles, p.splits, p.chunks_per_split, tiles_total, per_wg);
-            lin_total += p.tiles * p.splits;
-            if (xcd_env != 1) g.cum[0][g.n + 1] = lin_total;
+            g.cum[g.n + 1] = g.cum[g.n] + p.tiles * p.splits;
             g.p[g.n] = p; ++g.n;
         }
         const int frc = flush();

@@ -1473,10 +1473,11 @@ class WgradBatch:
         self.keep.append((dy, x))
         self._account(geom)
 
-    def add_conv(self, dy, x, dw, geom, scale=None, overwrite=False, dil=1):
+    def add_conv(self, dy, x, dw, geom, scale=None, overwrite=False, dil=1, dbias=None):
         """A convolution weight gradient (any geometry: the non-groupable ones are forwarded to rt_conv_wgrad at run())."""
         _req(dy, torch.bfloat16, "dy"); _req(x, torch.bfloat16, "x"); _req(dw, torch.float32, "dw"); _req(scale, torch.float32, "scale")
-        self.descs.append(_wgrad_desc(dy, x, dw, geom, scale=scale, overwrite=int(bool(overwrite)), dil=int(dil)))
+        _req(dbias, torch.float32, "dbias")
+        self.descs.append(_wgrad_desc(dy, x, dw, geom, scale=scale, dbias=dbias, overwrite=int(bool(overwrite)), dil=int(dil)))
         self.keep.append((dy, x, scale))
         self._account(geom)
 

@@ -448,6 +448,59 @@ def test_wgrad_v2_single_problem_splits_the_row_axis(hip):
         assert rel(db, dy.float().sum(0)) < 1e-5
 
 
+_W2_EDGES = {
+    # strided gather over narrow rows: DW = 9, M = 324 -- every 32-row chunk wraps three or four image rows, and 81 is no multiple
+    # of 32, so chunks straddle images
+    "strided_narrow": (4, 17, 17, 64, 64, 3, 2, 1),
+    "ragged_tiles": (300, 1, 1, 72, 136, 1, 1, 0),       # Linear 300 x 72 -> 136: a tail chunk, N and C off the tile
+    "odd_chunks": (2080, 1, 1, 64, 64, 1, 1, 0),         # Linear: 65 chunks, cut into 7 splits of 9 and a last one of 2
+}
+_W2_EDGE_REFS = {}
+
+
+def _w2_edge(name):
+    """geom, dy and x (bf16, NHWC, on the CPU), torch fp32 dw [Co, k, k, Ci] and dbias of an edge shape: computed once"""
+    if name not in _W2_EDGE_REFS:
+        B, H, W, Ci, Co, k, s, p = _W2_EDGES[name]
+        g = torch.Generator().manual_seed(sum(map(ord, name)))
+        x = bf(torch.randn(B, Ci, H, W, generator=g)).float()
+        w = torch.zeros(Co, Ci, k, k, requires_grad=True)
+        y = F.conv2d(x, w, None, stride=s, padding=p)
+        dy = bf(torch.randn(y.shape, generator=g))
+        y.backward(dy.float())
+        Ho, Wo = y.shape[-2:]
+        _W2_EDGE_REFS[name] = ((B, H, W, Ci, Ho, Wo, Co, k, k, s, p), nhwc(dy).reshape(-1, Co), nhwc(x).bfloat16().reshape(-1, Ci),
+                               w.grad.permute(0, 2, 3, 1).contiguous(), dy.float().sum((0, 2, 3)))
+    return _W2_EDGE_REFS[name]
+
+
+@pytest.mark.parametrize("overwrite", [False, True])
+@pytest.mark.parametrize("name", list(_W2_EDGES))
+def test_wgrad_v2_tile_walk_edges(hip, name, overwrite):
+    """The second generation's tile walk where it can go wrong -- the gather walker wrapping several image rows and an image end
+    per chunk, tiles ragged on both sides with a tail chunk, a short last split -- against torch fp32: dw and the fused bias
+    gradient, through rt_conv_wgrad and through a grouped launch, assigning and accumulating onto a non-zero dw."""
+    geom, dy, x, ref, ref_b = _w2_edge(name)
+    dyc, xc = dy.cuda(), x.cuda()
+    base = 0.0 if overwrite else 0.25
+
+    def fresh():
+        return torch.full(tuple(ref.shape), 7.0 if overwrite else base, device="cuda"), torch.full((geom[6],), 2.0, device="cuda")
+    dw, db = fresh()
+    hip.conv_wgrad(dyc, xc, dw, geom=geom, dbias=db, overwrite=overwrite)
+    dw2, db2 = fresh()
+    batch = hip.WgradBatch(workspace_mb=256)
+    if geom[7] * geom[8] > 1:
+        batch.add_conv(dyc, xc, dw2, geom, dbias=db2, overwrite=overwrite)
+    else:
+        batch.add(dyc, xc, dw2.view(geom[6], geom[3]), db2, overwrite=overwrite)
+    batch.run()
+    errs = [rel(dw - base, ref), rel(db - 2.0, ref_b), rel(dw2 - base, ref), rel(db2 - 2.0, ref_b)]
+    print("tile walk edges", name, "overwrite" if overwrite else "accumulate", errs)
+    assert errs[0] < TOL_F32 and errs[2] < TOL_F32
+    assert errs[1] < 1e-5 and errs[3] < 1e-5
+
+
 @pytest.mark.parametrize("B,H,W,Ci,Co", [
     (2, 40, 40, 256, 256),       # layer3: two channel tiles each side
     (1, 80, 80, 128, 128),       # layer2: rows of 80 (a 32-row chunk crosses an image row 2 times out of 5)
