@@ -32,10 +32,10 @@ def nchw(t, hh, ww, c):            # HIP [B*HW, ld] (channels padded) -> [B, c, 
 
 h, w = sv["h"], sv["w"]
 rows = [("X0 (bf16 operand)", nchw(sv["X0"], h, w, cv["lay1"].cin), "X0", True),
-        ("u1 = lay1(X0)", nchw(sv["u1"], h, w, cv["lay1"].cout), "u1", False),
-        ("a1 = relu(gn1)", nchw(sv["a1"], h, w, cv["lay1"].cout), "a1", True),
-        ("u2 = lay2(a1)", nchw(sv["u2"], h, w, cv["lay2"].cout), "u2", False)]
-for j, stg in enumerate(sv["stages"]):
+        ("u1 = lay1(X0)", nchw(sv["stages"][0]["u"], h, w, cv["lay1"].cout), "u1", False),
+        ("a1 = relu(gn1)", nchw(sv["stages"][1]["x"], h, w, cv["lay1"].cout), "a1", True),
+        ("u2 = lay2(a1)", nchw(sv["stages"][1]["u"], h, w, cv["lay2"].cout), "u2", False)]
+for j, stg in enumerate(sv["stages"][2:]):          # the three FPN stages
     lay = cv[f"lay{j + 3}"]
     rows.append((f"x{j} = adapter + up(a) (bf16 operand)", nchw(stg["x"], stg["fh"], stg["fw"], lay.cin), f"x{j}", True))
     rows.append((f"u{j + 3} = lay{j + 3}(x{j})", nchw(stg["u"], stg["fh"], stg["fw"], lay.cout), f"u{j + 3}", False))
@@ -52,7 +52,7 @@ a, b = rel(out["pred_masks"], o["pred_masks"]), rel(o1["pred_masks"], o["pred_ma
 print("%-40s %12.3e %12.3e %8.2f" % ("pred_masks", a, b, a / b))
 a, b = rel(out["mask_att"], o["mask_att"]), rel(o1["mask_att"], o["mask_att"])
 print("%-40s %12.3e %12.3e %8.2f" % ("mask_att", a, b, a / b))
-feats = model._saved["seg"]["stages"]
+feats = model._saved["seg"]["stages"][2:]
 hip_f = {2 - j: st["f16"] for j, st in enumerate(feats)}          # stages use (layer3, layer2, layer1) outputs
 for li in (0, 1, 2):
     ref, alt = o["feats"][li], o1["feats"][li]

@@ -3,6 +3,7 @@
 // (fp32 residual stream, bf16 operand copy, bf16 copy of y + pos) so no separate cast/add kernels run.
 #include "rt_common.h"
 #include "rt_ln_row.h"
+#include "rt_gn.h"
 #include <stdlib.h>
 
 namespace {
@@ -272,14 +273,11 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const rt_groupnorm_desc p
     __syncthreads();
     const int c = tid;
     if (c >= p.C) return;
-    const float inv_n = 1.f / (float)(cpg * p.HW);
-    const float mean = sm[c / cpg][0] * inv_n;
-    const float var = fmaxf(sm[c / cpg][1] * inv_n - mean * mean, 0.f);
-    const float rstd = rsqrtf(var + p.eps);
+    const GnStat st = rt_gn_stat(sm[c / cpg], rt_gn_inv_n(cpg, p.HW), p.eps);
     bf16_t* yb = (bf16_t*)p.y_bf16; bf16_t* ypb = (bf16_t*)p.ypos_bf16;
     for (int pix = blockIdx.x; pix < p.HW; pix += gridDim.x) {
         const size_t i = ((size_t)b * p.HW + pix) * p.C + c;
-        const float y = (p.x[i] - mean) * rstd * p.gamma[c] + p.beta[c];
+        const float y = rt_gn_xhat(p.x[i], st) * p.gamma[c] + p.beta[c];
         const size_t o = ((size_t)b * p.out_rows_per_img + p.out_row_off + pix) * p.C + c;
         if (p.y_f32) p.y_f32[o] = y;
         if (yb) yb[o] = (bf16_t)y;
@@ -292,12 +290,9 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const rt_groupnorm_bw
     const int b = blockIdx.y, c = threadIdx.x;
     const int p0 = blockIdx.x * GN_BWD_PIX, p1 = min(p0 + GN_BWD_PIX, p.HW);
     const int cpg = p.C / p.G;
-    const float inv_n = 1.f / (float)(cpg * p.HW);
     float s1 = 0.f, s2 = 0.f, dg = 0.f, db = 0.f;
     if (c < p.C) {
-        const float* st = p.stats + ((size_t)b * p.G + c / cpg) * 2;
-        const float mean = st[0] * inv_n;
-        const float rstd = rsqrtf(fmaxf(st[1] * inv_n - mean * mean, 0.f) + p.eps);
+        const GnStat st = rt_gn_stat(p.stats + ((size_t)b * p.G + c / cpg) * 2, rt_gn_inv_n(cpg, p.HW), p.eps);
         const float gam = p.gamma[c];
         // 8 pixels' loads in flight at a time (the plain loop is a chain of load -> accumulate round trips), 32 pixels per workgroup:
         // a quarter of the per-channel atomics of the 8-pixel blocking (round 3: 22.7 -> see profiles/r03 kernel stats)
@@ -315,7 +310,7 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const rt_groupnorm_bw
             for (int j = 0; j < 8; ++j) {
                 if (q0 + j >= p1) continue;
                 const float d = dv[j];
-                const float xh = (xv[j] - mean) * rstd;
+                const float xh = rt_gn_xhat(xv[j], st);
                 dg += d * xh; db += d;
                 s1 += d * gam; s2 += d * gam * xh;
             }
@@ -335,24 +330,20 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(const rt_groupnorm_bw
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const rt_groupnorm_bwd_desc p) {
     const size_t total = (size_t)p.B * p.HW * p.C;
     const int cpg = p.C / p.G;
-    const float inv_n = 1.f / (float)(cpg * p.HW);
+    const float inv_n = rt_gn_inv_n(cpg, p.HW);
     bf16_t* dxb = (bf16_t*)p.dx_bf16;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % p.C);
         const size_t pixg = i / p.C;
         const int b = (int)(pixg / p.HW);
         const int pix = (int)(pixg % p.HW);
-        const int g = c / cpg;
-        const float* st = p.stats + ((size_t)b * p.G + g) * 2;
-        const float mean = st[0] * inv_n;
-        const float rstd = rsqrtf(fmaxf(st[1] * inv_n - mean * mean, 0.f) + p.eps);
-        const float xh = (p.x[i] - mean) * rstd;
+        const size_t bg = ((size_t)b * p.G + c / cpg) * 2;
+        const GnStat st = rt_gn_stat(p.stats + bg, inv_n, p.eps);
+        const float xh = rt_gn_xhat(p.x[i], st);
         const size_t o = ((size_t)b * p.out_rows_per_img + p.out_row_off + pix) * p.C + c;
         float d = p.dy[o];
         if (p.dy2) d += p.dy2[o];
-        const float m1 = p.bstats[((size_t)b * p.G + g) * 2] * inv_n;
-        const float m2 = p.bstats[((size_t)b * p.G + g) * 2 + 1] * inv_n;
-        const float dx = rstd * (d * p.gamma[c] - m1 - xh * m2);
+        const float dx = rt_gn_dx(d * p.gamma[c], xh, st.rstd, p.bstats + bg, inv_n);
         if (p.dx_f32) p.dx_f32[i] = dx;
         if (dxb) dxb[i] = (bf16_t)dx;
     }
@@ -423,10 +414,12 @@ extern "C" int rt_layernorm_bwd(const rt_layernorm_bwd_desc* d, rt_stream_t stre
     return RT_OK;
 }
 
+// one thread per channel, a group inside one wave: what both directions of the token-major GroupNorm ask of (C, G)
+static bool gn_token_groups_bad(int C, int G) { return C <= 0 || C > 256 || G <= 0 || (C % G) || C / G > 64; }
+
 extern "C" int rt_groupnorm_fwd(const rt_groupnorm_desc* d, rt_stream_t stream) {
     if (!d || !d->x || !d->gamma || !d->beta || !d->stats) return RT_ERR_BADARG;
-    if (d->C <= 0 || d->C > 256 || d->G <= 0 || (d->C % d->G) || (d->C / d->G) > 64 || ((d->C / d->G) & (d->C / d->G - 1)))
-        return RT_ERR_UNSUPPORTED;
+    if (gn_token_groups_bad(d->C, d->G) || ((d->C / d->G) & (d->C / d->G - 1))) return RT_ERR_UNSUPPORTED;
     if (!d->partials || d->chunks < 1 || d->chunks > 64) return RT_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const int ppc = (d->HW + d->chunks - 1) / d->chunks;          // chunks past the last pixel write zeros
@@ -440,7 +433,7 @@ extern "C" int rt_groupnorm_fwd(const rt_groupnorm_desc* d, rt_stream_t stream) 
 
 extern "C" int rt_groupnorm_bwd(const rt_groupnorm_bwd_desc* d, rt_stream_t stream) {
     if (!d || !d->x || !d->dy || !d->gamma || !d->stats || !d->bstats) return RT_ERR_BADARG;
-    if (d->C <= 0 || d->C > 256 || d->G <= 0 || (d->C % d->G) || (d->C / d->G) > 64) return RT_ERR_UNSUPPORTED;
+    if (gn_token_groups_bad(d->C, d->G)) return RT_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = rt_zero_f32(d->bstats, 2 * (size_t)d->B * d->G, s);
     if (e != hipSuccess) return (int)e;

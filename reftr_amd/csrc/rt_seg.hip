@@ -3,8 +3,22 @@
 // attention map of MHAttentionMap, the concat that builds the mask head's input, and the bilinear + focal + dice loss.
 // All HBM-bound streaming kernels: 16-B row accesses where the channel count allows, fp32 statistics.
 #include "rt_common.h"
+#include "rt_gn.h"
 
 namespace {
+
+// The walk every bf16 operand of the head is written by: a grid-stride loop over `rows` rows of `ld` columns, consecutive threads on
+// consecutive columns.  f(row, c) is the value of a real column c < C; columns C..ld-1 are the zero padding the next convolution's
+// K tiles expect, except [keep0, keep1), which belong to another kernel and are left alone.
+template <class F>
+__device__ __forceinline__ void padded_rows(bf16_t* out, size_t rows, int ld, int C, F f, int keep0 = 0, int keep1 = 0) {
+    const size_t total = rows * ld;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / ld; const int c = (int)(i - row * ld);
+        if (c < C) out[i] = (bf16_t)f(row, c);
+        else if (c < keep0 || c >= keep1) out[i] = (bf16_t)0.f;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // GroupNorm over x[b][p][c] (row stride ldx), C real channels in G groups; stats[b][g] = {sum, sumsq}.
@@ -53,23 +67,14 @@ __global__ __launch_bounds__(64) void gn_nhwc_finalize_kernel(const float* __res
 }
 
 __global__ __launch_bounds__(256) void gn_nhwc_apply_kernel(const rt_gn_nhwc_desc p) {
-    const size_t rows = (size_t)p.B * p.HW;
     const int cpg = p.C / p.G;
-    const float inv_n = 1.f / ((float)cpg * (float)p.HW);
-    bf16_t* yb = (bf16_t*)p.y_bf16;
-    const size_t total = rows * p.ldy;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t row = i / p.ldy; const int c = (int)(i - row * p.ldy);
-        float y = 0.f;
-        if (c < p.C) {
-            const int b = (int)(row / p.HW), g = c / cpg;
-            const float mean = p.stats[((size_t)b * p.G + g) * 2] * inv_n;
-            const float var = fmaxf(p.stats[((size_t)b * p.G + g) * 2 + 1] * inv_n - mean * mean, 0.f);
-            y = (p.x[row * p.ldx + c] - mean) * rsqrtf(var + p.eps) * p.gamma[c] + p.beta[c];
-            if (p.act == RT_ACT_RELU) y = fmaxf(y, 0.f);
-        }
-        yb[i] = (bf16_t)y;          // channels C..ldy-1 are the zero padding the next convolution's K tiles expect
-    }
+    const float inv_n = rt_gn_inv_n(cpg, p.HW);
+    padded_rows((bf16_t*)p.y_bf16, (size_t)p.B * p.HW, p.ldy, p.C, [&](size_t row, int c) {
+        const int b = (int)(row / p.HW), g = c / cpg;
+        const GnStat st = rt_gn_stat(p.stats + ((size_t)b * p.G + g) * 2, inv_n, p.eps);
+        const float y = rt_gn_xhat(p.x[row * p.ldx + c], st) * p.gamma[c] + p.beta[c];
+        return p.act == RT_ACT_RELU ? fmaxf(y, 0.f) : y;
+    });
 }
 
 // backward, pass 1: bstats[b][g] = {sum g, sum g*xhat} with g = dy*gamma (dy through the ReLU mask); dgamma / dbeta.
@@ -83,22 +88,20 @@ __global__ __launch_bounds__(256) void gn_nhwc_bstats_kernel(const rt_gn_nhwc_bw
     const int b = blockIdx.y;
     const int p0 = blockIdx.x * pix_per_block, p1 = min(p0 + pix_per_block, p.HW);
     const int cpg = p.C / p.G;
-    const float inv_n = 1.f / ((float)cpg * (float)p.HW);
+    const float inv_n = rt_gn_inv_n(cpg, p.HW);
     for (int i = threadIdx.x; i < 2 * p.G; i += 256) sm[i] = 0.f;
     for (int i = threadIdx.x; i < 2 * p.C; i += 256) dgb[i] = 0.f;
     __syncthreads();
     const int cl = threadIdx.x % CP, prow = threadIdx.x / CP, rows = 256 / CP;
     for (int c = cl; c < p.C; c += CP) {
         const int g = c / cpg;
-        const float mean = p.stats[((size_t)b * p.G + g) * 2] * inv_n;
-        const float var = fmaxf(p.stats[((size_t)b * p.G + g) * 2 + 1] * inv_n - mean * mean, 0.f);
-        const float rstd = rsqrtf(var + p.eps), gam = p.gamma[c], bet = p.beta[c];
+        const GnStat st = rt_gn_stat(p.stats + ((size_t)b * p.G + g) * 2, inv_n, p.eps);
+        const float gam = p.gamma[c], bet = p.beta[c];
         float a_dg = 0.f, a_db = 0.f, a_g = 0.f, a_gx = 0.f;
         for (int pix = p0 + prow; pix < p1; pix += rows) {
             const size_t row = (size_t)b * p.HW + pix;
-            const float xh = (p.x[row * p.ldx + c] - mean) * rstd;
-            float d = p.dy[row * p.lddy + c];
-            if (p.act == RT_ACT_RELU && xh * gam + bet <= 0.f) d = 0.f;
+            const float xh = rt_gn_xhat(p.x[row * p.ldx + c], st);
+            const float d = rt_gn_gate(p.dy[row * p.lddy + c], xh, gam, bet, p.act == RT_ACT_RELU);
             a_dg += d * xh; a_db += d;
             const float gg = d * gam;
             a_g += gg; a_gx += gg * xh;
@@ -115,67 +118,44 @@ __global__ __launch_bounds__(256) void gn_nhwc_bstats_kernel(const rt_gn_nhwc_bw
 }
 
 __global__ __launch_bounds__(256) void gn_nhwc_bwd_apply_kernel(const rt_gn_nhwc_bwd_desc p) {
-    const size_t rows = (size_t)p.B * p.HW;
     const int cpg = p.C / p.G;
-    const float inv_n = 1.f / ((float)cpg * (float)p.HW);
-    bf16_t* dxb = (bf16_t*)p.dx_bf16;
-    const size_t total = rows * p.lddx;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t row = i / p.lddx; const int c = (int)(i - row * p.lddx);
-        float dx = 0.f;
-        if (c < p.C) {
-            const int b = (int)(row / p.HW), g = c / cpg;
-            const float mean = p.stats[((size_t)b * p.G + g) * 2] * inv_n;
-            const float var = fmaxf(p.stats[((size_t)b * p.G + g) * 2 + 1] * inv_n - mean * mean, 0.f);
-            const float rstd = rsqrtf(var + p.eps);
-            const float xh = (p.x[row * p.ldx + c] - mean) * rstd;
-            float d = p.dy[row * p.lddy + c];
-            if (p.act == RT_ACT_RELU && xh * p.gamma[c] + p.beta[c] <= 0.f) d = 0.f;
-            const float m1 = p.bstats[((size_t)b * p.G + g) * 2] * inv_n, m2 = p.bstats[((size_t)b * p.G + g) * 2 + 1] * inv_n;
-            dx = rstd * (d * p.gamma[c] - m1 - xh * m2);
-        }
-        dxb[i] = (bf16_t)dx;
-    }
+    const float inv_n = rt_gn_inv_n(cpg, p.HW);
+    padded_rows((bf16_t*)p.dx_bf16, (size_t)p.B * p.HW, p.lddx, p.C, [&](size_t row, int c) {
+        const size_t bg = ((size_t)(row / p.HW) * p.G + c / cpg) * 2;
+        const GnStat st = rt_gn_stat(p.stats + bg, inv_n, p.eps);
+        const float xh = rt_gn_xhat(p.x[row * p.ldx + c], st);
+        const float d = rt_gn_gate(p.dy[row * p.lddy + c], xh, p.gamma[c], p.beta[c], p.act == RT_ACT_RELU);
+        return rt_gn_dx(rt_gn_mul_rounded(d, p.gamma[c]), xh, st.rstd, p.bstats + bg, inv_n);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // out[b][y][x][c] = fpn[b][y][x][c] + a[b][y*h/H][x*w/W][c]   (F.interpolate nearest: src = floor(dst * in / out))
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void upsample_add_kernel(const rt_upsample_add_desc p) {
-    bf16_t* out = (bf16_t*)p.out_bf16; const bf16_t* a = (const bf16_t*)p.a_bf16;
-    const size_t total = (size_t)p.B * p.H * p.W * p.ldo;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t row = i / p.ldo; const int c = (int)(i - row * p.ldo);
-        float v = 0.f;
-        if (c < p.C) {
-            const int x = (int)(row % p.W); const size_t t = row / p.W; const int y = (int)(t % p.H); const int b = (int)(t / p.H);
-            const int ys = min((int)((long long)y * p.h / p.H), p.h - 1), xs = min((int)((long long)x * p.w / p.W), p.w - 1);
-            v = p.fpn[row * p.ldf + c] + (float)a[(((size_t)b * p.h + ys) * p.w + xs) * p.lda + c];
-        }
-        out[i] = (bf16_t)v;
-    }
+    const bf16_t* a = (const bf16_t*)p.a_bf16;
+    padded_rows((bf16_t*)p.out_bf16, (size_t)p.B * p.H * p.W, p.ldo, p.C, [&](size_t row, int c) {
+        const int x = (int)(row % p.W); const size_t t = row / p.W; const int y = (int)(t % p.H); const int b = (int)(t / p.H);
+        const int ys = min((int)((long long)y * p.h / p.H), p.h - 1), xs = min((int)((long long)x * p.w / p.W), p.w - 1);
+        return p.fpn[row * p.ldf + c] + (float)a[(((size_t)b * p.h + ys) * p.w + xs) * p.lda + c];
+    });
 }
 
 // backward: dyb = bf16(dy) (the FPN adapter's output gradient), da[b][ys][xs][c] = sum of dy over the pixels mapped there
 __global__ __launch_bounds__(256) void upsample_add_bwd_kernel(const rt_upsample_add_bwd_desc p) {
-    bf16_t* dyb = (bf16_t*)p.dy_bf16;
-    const size_t nsrc = (size_t)p.B * p.h * p.w * p.C, ndst = (size_t)p.B * p.H * p.W * p.lddyb;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nsrc + ndst; i += (size_t)gridDim.x * 256) {
-        if (i < nsrc) {
-            const int c = (int)(i % p.C); size_t t = i / p.C;
-            const int xs = (int)(t % p.w); t /= p.w; const int ys = (int)(t % p.h); const int b = (int)(t / p.h);
-            const int y0 = (int)(((long long)ys * p.H + p.h - 1) / p.h), y1 = (int)(((long long)(ys + 1) * p.H + p.h - 1) / p.h);
-            const int x0 = (int)(((long long)xs * p.W + p.w - 1) / p.w), x1 = (int)(((long long)(xs + 1) * p.W + p.w - 1) / p.w);
-            float s = 0.f;
-            for (int y = y0; y < y1 && y < p.H; ++y)
-                for (int x = x0; x < x1 && x < p.W; ++x) s += p.dy[(((size_t)b * p.H + y) * p.W + x) * p.lddy + c];
-            p.da[(((size_t)b * p.h + ys) * p.w + xs) * p.ldda + c] = s;
-        } else if (dyb) {
-            const size_t j = i - nsrc;
-            const size_t row = j / p.lddyb; const int c = (int)(j - row * p.lddyb);
-            dyb[j] = (bf16_t)(c < p.C ? p.dy[row * p.lddy + c] : 0.f);
-        }
+    const size_t nsrc = (size_t)p.B * p.h * p.w * p.C;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < nsrc; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % p.C); size_t t = i / p.C;
+        const int xs = (int)(t % p.w); t /= p.w; const int ys = (int)(t % p.h); const int b = (int)(t / p.h);
+        const int y0 = (int)(((long long)ys * p.H + p.h - 1) / p.h), y1 = (int)(((long long)(ys + 1) * p.H + p.h - 1) / p.h);
+        const int x0 = (int)(((long long)xs * p.W + p.w - 1) / p.w), x1 = (int)(((long long)(xs + 1) * p.W + p.w - 1) / p.w);
+        float s = 0.f;
+        for (int y = y0; y < y1 && y < p.H; ++y)
+            for (int x = x0; x < x1 && x < p.W; ++x) s += p.dy[(((size_t)b * p.H + y) * p.W + x) * p.lddy + c];
+        p.da[(((size_t)b * p.h + ys) * p.w + xs) * p.ldda + c] = s;
     }
+    if (p.dy_bf16)
+        padded_rows((bf16_t*)p.dy_bf16, (size_t)p.B * p.H * p.W, p.lddyb, p.C, [&](size_t row, int c) { return p.dy[row * p.lddy + c]; });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -184,7 +164,7 @@ __global__ __launch_bounds__(256) void upsample_add_bwd_kernel(const rt_upsample
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_map_fwd_kernel(const rt_attn_map_desc p) {
     extern __shared__ float lg[];            // [nh * HW] logits, then probabilities
-    __shared__ float red[8];
+    __shared__ float red[16];
     const int b = blockIdx.x, t = threadIdx.x;
     const int dh = p.E / p.nh, n_ent = p.nh * p.HW;
     const float* q = p.q + (size_t)b * p.E;
@@ -206,11 +186,7 @@ __global__ __launch_bounds__(256) void attn_map_fwd_kernel(const rt_attn_map_des
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float sum = 0.f;
     for (int e = t; e < n_ent; e += 256) { const float v = __expf(lg[e] - mx); lg[e] = v; sum += v; }
-    sum = rt_wave_sum(sum);
-    __syncthreads();
-    if ((t & 63) == 0) red[4 + (t >> 6)] = sum;
-    __syncthreads();
-    const float inv = 1.f / (red[4] + red[5] + red[6] + red[7]);
+    const float inv = 1.f / rt_block_sum(sum, red);
     bf16_t* xc = (bf16_t*)p.concat_bf16;
     for (int e = t; e < n_ent; e += 256) {
         const int n = e / p.HW, pix = e - n * p.HW;
@@ -220,6 +196,7 @@ __global__ __launch_bounds__(256) void attn_map_fwd_kernel(const rt_attn_map_des
     }
 }
 
+// (its four-wave sum stays written out: through rt_block_sum, one more barrier, the kernel took 0.4 us more per launch of 62)
 // dlogit = norm * P * (dP - sum(P * dP));  dq[n*dh+c] = sum_p dlogit[n][p] k[p][n*dh+c];  dk[p][n*dh+c] = dlogit[n][p] q[n*dh+c]
 __global__ __launch_bounds__(256) void attn_map_bwd_kernel(const rt_attn_map_bwd_desc p) {
     extern __shared__ float dl[];            // [nh * HW]
@@ -256,15 +233,11 @@ __global__ __launch_bounds__(256) void attn_map_bwd_kernel(const rt_attn_map_bwd
 
 // X0[b*HW+p] = [ bf16(src[b][p][0:E]) | bf16(mem[b*S + off + p][0:E]) | (attention map, written by attn_map_fwd) | 0 ]
 __global__ __launch_bounds__(256) void seg_concat_kernel(const rt_seg_concat_desc p) {
-    bf16_t* out = (bf16_t*)p.out_bf16;
-    const size_t total = (size_t)p.B * p.HW * p.ldo;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t row = i / p.ldo; const int c = (int)(i - row * p.ldo);
+    padded_rows((bf16_t*)p.out_bf16, (size_t)p.B * p.HW, p.ldo, 2 * p.E, [&](size_t row, int c) {
         const int b = (int)(row / p.HW), pix = (int)(row - (size_t)b * p.HW);
-        if (c < p.E) out[i] = (bf16_t)p.src[((size_t)b * p.src_rows_per_img + p.src_row_off + pix) * p.E + c];
-        else if (c < 2 * p.E) out[i] = (bf16_t)p.mem[((size_t)b * p.mem_rows_per_img + p.mem_row_off + pix) * p.E + (c - p.E)];
-        else if (c >= 2 * p.E + p.nh) out[i] = (bf16_t)0.f;
-    }
+        return c < p.E ? p.src[((size_t)b * p.src_rows_per_img + p.src_row_off + pix) * p.E + c]
+                       : p.mem[((size_t)b * p.mem_rows_per_img + p.mem_row_off + pix) * p.E + (c - p.E)];
+    }, 2 * p.E, 2 * p.E + p.nh);          // the attention-map columns are attn_map_fwd_kernel's
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -282,6 +255,7 @@ __device__ __forceinline__ Bilin bilin(int y, int x, int h, int w, float sy, flo
     return r;
 }
 
+// (pixel terms written out here and in mask_loss_grad_kernel, own four-sum table: one shared pixel function cost 0.7, rt_block_sum 2.5 of 24.8 us)
 __global__ __launch_bounds__(256) void mask_loss_fwd_kernel(const rt_mask_loss_desc p) {
     __shared__ float sm[4][4];
     const int b = blockIdx.y;
@@ -397,117 +371,115 @@ __global__ __launch_bounds__(256) void mask_loss_gather_kernel(const rt_mask_los
     p.dpred[((size_t)b * p.h * p.w + src) * p.lddp] += acc;          // one owner per element
 }
 
+// ---- host side: every entry point answers RT_ERR_BADARG for a missing pointer and RT_ERR_UNSUPPORTED for a geometry the kernels do
+// not cover, before anything is launched
 static inline int grid_for(size_t total, int cap = 4096) {
     size_t b = (total + 255) / 256;
     return (int)(b > (size_t)cap ? cap : (b < 1 ? 1 : b));
 }
+template <class... P> inline bool any_null(const P*... p) { return (... || !p); }
+// a row stride that cannot hold the C real channels of its rows
+template <class... L> inline bool any_below(int C, L... ld) { return (... || (ld < C)); }
+// C channels in G groups, as both directions of the NHWC GroupNorm need them (bstats keeps 2 * G <= 128 sums in LDS)
+inline bool gn_groups_bad(int C, int G, int max_g) { return C <= 0 || G <= 0 || G > max_g || (C % G); }
+// pixels of one image per workgroup of the two GroupNorm reductions: about 4096 elements each
+inline int gn_nhwc_ppb(int C) { const int ppb = (4096 + C - 1) / C; return ppb < 1 ? 1 : ppb; }
+
+template <class K, class... A> int launch(K kernel, dim3 grid, int block, size_t smem, rt_stream_t stream, const A&... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(block), smem, (hipStream_t)stream, args...);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
+
+// The attention-map kernels keep one image's nh * HW logits in dynamic LDS, one workgroup per image.  Above the 64 KB any kernel may
+// ask for, the kernel's own limit is raised first: once, and again only when a later call needs more than every call before it.
+template <auto kernel, class D> int attn_map_launch(const D& d, rt_stream_t stream) {
+    static size_t granted = 65536;          // one per kernel (the template argument); like rt_stem_pool's flag: one device, one host thread
+    const size_t smem = (size_t)d.nh * d.HW * sizeof(float);
+    if (smem > granted) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return (int)e;
+        granted = smem;
+    }
+    return launch(kernel, dim3(d.B), 256, smem, stream, d);
+}
+template <class D> inline bool attn_map_bad(const D& d) { return d.E <= 0 || d.nh <= 0 || (d.E % d.nh) || (size_t)d.nh * d.HW * 4 > 150000; }
 
 }  // namespace
 
 extern "C" int rt_gn_nhwc_fwd(const rt_gn_nhwc_desc* d, rt_stream_t stream) {
-    if (!d || !d->x || !d->gamma || !d->beta || !d->stats || !d->y_bf16) return RT_ERR_BADARG;
-    if (d->C <= 0 || d->G <= 0 || d->G > 64 || (d->C % d->G) || d->ldx < d->C || d->ldy < d->C || d->B <= 0 || d->HW <= 0) return RT_ERR_UNSUPPORTED;
-    if (d->G > 16) return RT_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    int ppb = (int)((4096 + d->C - 1) / d->C); if (ppb < 1) ppb = 1;
-    const int nblk = (d->HW + ppb - 1) / ppb;
+    if (!d || any_null(d->x, d->gamma, d->beta, d->stats, d->y_bf16)) return RT_ERR_BADARG;
+    // G <= 16: gn_nhwc_stats_kernel keeps 2 * G * 256 floats of LDS
+    if (gn_groups_bad(d->C, d->G, 16) || any_below(d->C, d->ldx, d->ldy) || d->B <= 0 || d->HW <= 0) return RT_ERR_UNSUPPORTED;
+    const int ppb = gn_nhwc_ppb(d->C), nblk = (d->HW + ppb - 1) / ppb;
     if (!d->partials || d->partial_blocks < nblk) return RT_ERR_BADARG;
-    hipLaunchKernelGGL(gn_nhwc_stats_kernel, dim3(nblk, d->B), dim3(256), 2 * d->G * 256 * sizeof(float), s,
-                       d->x, d->partials, d->HW, d->C, d->ldx, d->G, ppb);
-    RT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_nhwc_finalize_kernel, dim3(2 * d->G, d->B), dim3(64), 0, s, d->partials, d->stats, nblk, 2 * d->G);
-    RT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_nhwc_apply_kernel, dim3(grid_for((size_t)d->B * d->HW * d->ldy)), dim3(256), 0, s, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    int rc = launch(gn_nhwc_stats_kernel, dim3(nblk, d->B), 256, 2 * d->G * 256 * sizeof(float), stream,
+                    d->x, d->partials, d->HW, d->C, d->ldx, d->G, ppb);
+    if (rc == RT_OK) rc = launch(gn_nhwc_finalize_kernel, dim3(2 * d->G, d->B), 64, 0, stream, d->partials, d->stats, nblk, 2 * d->G);
+    if (rc == RT_OK) rc = launch(gn_nhwc_apply_kernel, dim3(grid_for((size_t)d->B * d->HW * d->ldy)), 256, 0, stream, *d);
+    return rc;
 }
 
 extern "C" int rt_gn_nhwc_bwd(const rt_gn_nhwc_bwd_desc* d, rt_stream_t stream) {
-    if (!d || !d->x || !d->dy || !d->gamma || !d->beta || !d->stats || !d->bstats || !d->dx_bf16) return RT_ERR_BADARG;
-    if (d->C <= 0 || d->G <= 0 || d->G > 64 || (d->C % d->G) || d->ldx < d->C || d->lddy < d->C || d->lddx < d->C || d->C > 4096) return RT_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = rt_zero_f32(d->bstats, 2 * (size_t)d->B * d->G, s);
+    if (!d || any_null(d->x, d->dy, d->gamma, d->beta, d->stats, d->bstats, d->dx_bf16)) return RT_ERR_BADARG;
+    if (gn_groups_bad(d->C, d->G, 64) || any_below(d->C, d->ldx, d->lddy, d->lddx) || d->C > 4096) return RT_ERR_UNSUPPORTED;
+    const hipError_t e = rt_zero_f32(d->bstats, 2 * (size_t)d->B * d->G, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    int ppb = (int)((4096 + d->C - 1) / d->C); if (ppb < 1) ppb = 1;
+    const int ppb = gn_nhwc_ppb(d->C);
     const int CP = (d->C <= 256 && 256 % d->C == 0) ? d->C : 256;
-    hipLaunchKernelGGL(gn_nhwc_bstats_kernel, dim3((d->HW + ppb - 1) / ppb, d->B), dim3(256), 2 * d->C * sizeof(float), s, *d, ppb, CP);
-    RT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gn_nhwc_bwd_apply_kernel, dim3(grid_for((size_t)d->B * d->HW * d->lddx)), dim3(256), 0, s, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    const int rc = launch(gn_nhwc_bstats_kernel, dim3((d->HW + ppb - 1) / ppb, d->B), 256, 2 * d->C * sizeof(float), stream, *d, ppb, CP);
+    return rc != RT_OK ? rc : launch(gn_nhwc_bwd_apply_kernel, dim3(grid_for((size_t)d->B * d->HW * d->lddx)), 256, 0, stream, *d);
 }
 
 extern "C" int rt_upsample_add(const rt_upsample_add_desc* d, rt_stream_t stream) {
-    if (!d || !d->fpn || !d->a_bf16 || !d->out_bf16) return RT_ERR_BADARG;
-    if (d->C <= 0 || d->ldf < d->C || d->lda < d->C || d->ldo < d->C || d->h <= 0 || d->w <= 0 || d->H < d->h || d->W < d->w) return RT_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(upsample_add_kernel, dim3(grid_for((size_t)d->B * d->H * d->W * d->ldo)), dim3(256), 0, (hipStream_t)stream, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    if (!d || any_null(d->fpn, d->a_bf16, d->out_bf16)) return RT_ERR_BADARG;
+    if (d->C <= 0 || any_below(d->C, d->ldf, d->lda, d->ldo) || d->h <= 0 || d->w <= 0 || d->H < d->h || d->W < d->w) return RT_ERR_UNSUPPORTED;
+    return launch(upsample_add_kernel, dim3(grid_for((size_t)d->B * d->H * d->W * d->ldo)), 256, 0, stream, *d);
 }
 
 extern "C" int rt_upsample_add_bwd(const rt_upsample_add_bwd_desc* d, rt_stream_t stream) {
-    if (!d || !d->dy || !d->da) return RT_ERR_BADARG;
-    if (d->C <= 0 || d->lddy < d->C || d->ldda < d->C || (d->dy_bf16 && d->lddyb < d->C)) return RT_ERR_UNSUPPORTED;
+    if (!d || any_null(d->dy, d->da)) return RT_ERR_BADARG;
+    if (d->C <= 0 || any_below(d->C, d->lddy, d->ldda) || (d->dy_bf16 && d->lddyb < d->C)) return RT_ERR_UNSUPPORTED;
     const size_t total = (size_t)d->B * d->h * d->w * d->C + (d->dy_bf16 ? (size_t)d->B * d->H * d->W * d->lddyb : 0);
-    hipLaunchKernelGGL(upsample_add_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    return launch(upsample_add_bwd_kernel, dim3(grid_for(total)), 256, 0, stream, *d);
 }
 
 extern "C" int rt_attn_map_fwd(const rt_attn_map_desc* d, rt_stream_t stream) {
-    if (!d || !d->q || !d->k || !d->mask || !d->P) return RT_ERR_BADARG;
-    if (d->E <= 0 || d->nh <= 0 || (d->E % d->nh) || d->HW <= 0 || (size_t)d->nh * d->HW * 4 > 150000) return RT_ERR_UNSUPPORTED;
-    const size_t smem = (size_t)d->nh * d->HW * sizeof(float);
-    if (smem > 65536) (void)hipFuncSetAttribute((const void*)attn_map_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(attn_map_fwd_kernel, dim3(d->B), dim3(256), smem, (hipStream_t)stream, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    if (!d || any_null(d->q, d->k, d->mask, d->P)) return RT_ERR_BADARG;
+    if (attn_map_bad(*d) || d->HW <= 0) return RT_ERR_UNSUPPORTED;
+    return attn_map_launch<attn_map_fwd_kernel>(*d, stream);
 }
 
 extern "C" int rt_attn_map_bwd(const rt_attn_map_bwd_desc* d, rt_stream_t stream) {
-    if (!d || !d->q || !d->k || !d->P || !d->dconcat || !d->dq || !d->dk) return RT_ERR_BADARG;
-    if (d->E <= 0 || d->E > 256 || d->nh <= 0 || (d->E % d->nh) || (size_t)d->nh * d->HW * 4 > 150000) return RT_ERR_UNSUPPORTED;
-    const size_t smem = (size_t)d->nh * d->HW * sizeof(float);
-    if (smem > 65536) (void)hipFuncSetAttribute((const void*)attn_map_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(attn_map_bwd_kernel, dim3(d->B), dim3(256), smem, (hipStream_t)stream, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    if (!d || any_null(d->q, d->k, d->P, d->dconcat, d->dq, d->dk)) return RT_ERR_BADARG;
+    if (attn_map_bad(*d) || d->E > 256) return RT_ERR_UNSUPPORTED;          // one thread per feature
+    return attn_map_launch<attn_map_bwd_kernel>(*d, stream);
 }
 
 extern "C" int rt_seg_concat(const rt_seg_concat_desc* d, rt_stream_t stream) {
-    if (!d || !d->src || !d->mem || !d->out_bf16) return RT_ERR_BADARG;
+    if (!d || any_null(d->src, d->mem, d->out_bf16)) return RT_ERR_BADARG;
     if (d->ldo < 2 * d->E + d->nh || d->E <= 0) return RT_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(seg_concat_kernel, dim3(grid_for((size_t)d->B * d->HW * d->ldo)), dim3(256), 0, (hipStream_t)stream, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    return launch(seg_concat_kernel, dim3(grid_for((size_t)d->B * d->HW * d->ldo)), 256, 0, stream, *d);
 }
 
 extern "C" int rt_mask_loss(const rt_mask_loss_desc* d, rt_stream_t stream) {
-    if (!d || !d->pred || !d->target || !d->sums) return RT_ERR_BADARG;
+    if (!d || any_null(d->pred, d->target, d->sums)) return RT_ERR_BADARG;
     if (d->B <= 0 || d->h <= 0 || d->w <= 0 || d->Ht <= 0 || d->Wt <= 0 || d->ldp <= 0) return RT_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    const int gx = grid_for((size_t)d->Ht * d->Wt, 256);
     if (!d->dpred) {
         if (!d->losses) return RT_ERR_BADARG;
         if (!d->gbuf) {
-            hipError_t e = rt_zero_f32(d->sums, 4 * (size_t)d->B, s);
+            const hipError_t e = rt_zero_f32(d->sums, 4 * (size_t)d->B, (hipStream_t)stream);
             if (e != hipSuccess) return (int)e;
         }
-        hipLaunchKernelGGL(mask_loss_fwd_kernel, dim3(gx, d->B), dim3(256), 0, s, *d);
-        RT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(mask_loss_final_kernel, dim3(1), dim3(64), 0, s, d->sums, d->losses, d->B, d->Ht * d->Wt, d->inv_norm,
-                           (const float*)d->gbuf, gx);
-        RT_CHECK_LAUNCH();
-    } else {
-        if (!d->g_focal || !d->g_dice || d->lddp <= 0 || !d->gbuf) return RT_ERR_BADARG;
-        hipLaunchKernelGGL(mask_loss_grad_kernel, dim3(grid_for((size_t)d->Ht * d->Wt, 1024), d->B), dim3(256), 0, s, *d);
-        RT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(mask_loss_gather_kernel, dim3((d->h * d->w + 255) / 256, d->B), dim3(256), 0, s, *d);
-        RT_CHECK_LAUNCH();
+        const int gx = grid_for((size_t)d->Ht * d->Wt, 256);
+        const int rc = launch(mask_loss_fwd_kernel, dim3(gx, d->B), 256, 0, stream, *d);
+        return rc != RT_OK ? rc : launch(mask_loss_final_kernel, dim3(1), 64, 0, stream, d->sums, d->losses, d->B, d->Ht * d->Wt, d->inv_norm,
+                                         (const float*)d->gbuf, gx);
     }
-    return RT_OK;
+    if (any_null(d->g_focal, d->g_dice, d->gbuf) || d->lddp <= 0) return RT_ERR_BADARG;
+    const int rc = launch(mask_loss_grad_kernel, dim3(grid_for((size_t)d->Ht * d->Wt, 1024), d->B), 256, 0, stream, *d);
+    return rc != RT_OK ? rc : launch(mask_loss_gather_kernel, dim3((d->h * d->w + 255) / 256, d->B), 256, 0, stream, *d);
 }
-
 
 // ------------------------------------------------------------------------------------------------ CEM block
 namespace {
@@ -535,6 +507,11 @@ __device__ __forceinline__ void cem_unit(const float* u, float (&r)[16], float& 
 #pragma unroll
     for (int c = 0; c < 16; ++c) r[c] = u[c] / un;
 }
+
+// Online softmax over the pixels: a partial result is (m, s, e) = (maximum, sum exp(a - m), sum t exp(a - m)); merging moves each partial
+// to the common maximum M by this factor, and an empty one (m = -inf) adds nothing instead of a NaN.  The lane butterfly merges pairs at
+// max(m, m2); the 16-wave fold takes the maximum of all first and moves every wave once (a chain of pairs would round differently).
+__device__ __forceinline__ float cem_rescale(float m, float M) { return m == -INFINITY ? 0.f : __expf(m - M); }
 
 __global__ __launch_bounds__(1024) void cem_fwd_kernel(const rt_cem_desc p) {
     __shared__ float sm[3][16];
@@ -567,7 +544,7 @@ __global__ __launch_bounds__(1024) void cem_fwd_kernel(const rt_cem_desc p) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64), e2 = __shfl_xor(e, o, 64);
-        const float mn = fmaxf(m, m2), c1 = (m == -INFINITY) ? 0.f : __expf(m - mn), c2 = (m2 == -INFINITY) ? 0.f : __expf(m2 - mn);
+        const float mn = fmaxf(m, m2), c1 = cem_rescale(m, mn), c2 = cem_rescale(m2, mn);
         s = s * c1 + s2 * c2; e = e * c1 + e2 * c2; m = mn;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -577,7 +554,7 @@ __global__ __launch_bounds__(1024) void cem_fwd_kernel(const rt_cem_desc p) {
         float M = -INFINITY;
         for (int w = 0; w < 16; ++w) M = fmaxf(M, sm[0][w]);
         float S = 0.f, E = 0.f;
-        for (int w = 0; w < 16; ++w) { const float c = (sm[0][w] == -INFINITY) ? 0.f : __expf(sm[0][w] - M); S += sm[1][w] * c; E += sm[2][w] * c; }
+        for (int w = 0; w < 16; ++w) { const float c = cem_rescale(sm[0][w], M); S += sm[1][w] * c; E += sm[2][w] * c; }
         const float energy = E / S;
         p.energy[b] = energy; p.stats[2 * b] = M; p.stats[2 * b + 1] = S;
         atomicAdd(p.loss, -__logf(energy + 1e-6f) / (float)p.B);
@@ -661,24 +638,23 @@ __global__ __launch_bounds__(1024) void cem_bwd_kernel(const rt_cem_desc p) {
 
 }  // namespace
 
+// what both directions ask of the geometry.  E == 256: the kernels hold hidden / 16 == 16 channels per image in 16 waves / fixed arrays
+static int cem_geometry(const rt_cem_desc& d, bool bwd) {
+    if (d.B <= 0 || d.HW <= 0 || d.E <= 0 || d.ld < 16 || (d.ld & 7) || (bwd && (d.lddr < 16 || (d.lddr & 3)))) return RT_ERR_BADARG;
+    return d.E != 256 ? RT_ERR_UNSUPPORTED : RT_OK;
+}
+
 extern "C" int rt_cem_fwd(const rt_cem_desc* d, rt_stream_t stream) {
-    if (!d || !d->hs || !d->w3 || !d->b3 || !d->u || !d->res || !d->w2 || !d->b2 || !d->energy || !d->stats || !d->loss) return RT_ERR_BADARG;
-    if (d->B <= 0 || d->HW <= 0 || d->E <= 0 || d->ld < 16 || (d->ld & 7)) return RT_ERR_BADARG;
-    if (d->E != 256) return RT_ERR_UNSUPPORTED;      // the kernels hold hidden/16 == 16 channels per image in 16 waves / fixed arrays
-    hipStream_t s = (hipStream_t)stream;
-    const hipError_t e = rt_zero_f32(d->loss, 1, s);
+    if (!d || any_null(d->hs, d->w3, d->b3, d->u, d->res, d->w2, d->b2, d->energy, d->stats, d->loss)) return RT_ERR_BADARG;
+    if (const int rc = cem_geometry(*d, false)) return rc;
+    const hipError_t e = rt_zero_f32(d->loss, 1, (hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(cem_fwd_kernel, dim3((unsigned)d->B), dim3(1024), 0, s, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    return launch(cem_fwd_kernel, dim3((unsigned)d->B), 1024, 0, stream, *d);
 }
 
 extern "C" int rt_cem_bwd(const rt_cem_desc* d, rt_stream_t stream) {
-    if (!d || !d->hs || !d->w3 || !d->u || !d->res || !d->w2 || !d->b2 || !d->energy || !d->stats || !d->g || !d->dres || !d->dhs ||
-        !d->dw3 || !d->db3 || !d->dw2) return RT_ERR_BADARG;
-    if (d->B <= 0 || d->HW <= 0 || d->E <= 0 || d->ld < 16 || (d->ld & 7) || d->lddr < 16 || (d->lddr & 3)) return RT_ERR_BADARG;
-    if (d->E != 256) return RT_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(cem_bwd_kernel, dim3((unsigned)d->B), dim3(1024), 0, (hipStream_t)stream, *d);
-    RT_CHECK_LAUNCH();
-    return RT_OK;
+    if (!d || any_null(d->hs, d->w3, d->u, d->res, d->w2, d->b2, d->energy, d->stats, d->g, d->dres, d->dhs, d->dw3, d->db3, d->dw2))
+        return RT_ERR_BADARG;
+    if (const int rc = cem_geometry(*d, true)) return rc;
+    return launch(cem_bwd_kernel, dim3((unsigned)d->B), 1024, 0, stream, *d);
 }

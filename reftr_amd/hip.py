@@ -1553,6 +1553,13 @@ class WeightPrepBatch:
 # --------------------------------------------------------------------------------------------
 # RES head (RefTRSeg) kernels
 # --------------------------------------------------------------------------------------------
+def gn_nhwc_blocks(HW, C):
+    """Workgroups per image of rt_gn_nhwc_fwd's statistics pass (gn_nhwc_ppb in csrc/rt_seg.hip: about 4096 elements per workgroup):
+    the rows of the `partials` workspace the caller has to bring."""
+    ppb = max(1, (4096 + C - 1) // C)
+    return (HW + ppb - 1) // ppb
+
+
 def gn_nhwc_fwd(x, gamma, beta, B, HW, C, G=8, ldy=None, act=ACT_RELU, eps=1e-5):
     """y = [relu](GroupNorm(G, C)(x)) as a bf16 [B*HW, ldy] operand (padding zero); returns (y_bf16, stats)."""
     _req(x, torch.float32, "x"); _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta")
@@ -1561,8 +1568,7 @@ def gn_nhwc_fwd(x, gamma, beta, B, HW, C, G=8, ldy=None, act=ACT_RELU, eps=1e-5)
     assert x.numel() == B * HW * ldx and gamma.numel() >= C
     y = torch.empty((B * HW, ldy), dtype=torch.bfloat16, device=x.device)
     stats = torch.empty((B, G, 2), dtype=torch.float32, device=x.device)
-    ppb = max(1, (4096 + C - 1) // C)          # rt_gn_nhwc_fwd cuts the pixels the same way
-    nblk = (HW + ppb - 1) // ppb
+    nblk = gn_nhwc_blocks(HW, C)
     partials = torch.empty((B, nblk, G, 2), dtype=torch.float32, device=x.device)
     _call("rt_gn_nhwc_fwd", _desc(GnNhwcDesc, x=x, gamma=gamma, beta=beta, stats=stats, y_bf16=y, B=B, HW=HW, C=C, G=G, ldx=ldx, ldy=ldy,
                                   act=act, eps=eps, partials=partials, partial_blocks=nblk))

@@ -6,6 +6,8 @@ of 64 (models/layout.py:phys_dims — the padding is zero in weights, biases and
 GroupNorm(8)+ReLU, the FPN nearest-upsample+add, the joint-softmax attention map and the concat are rt_seg.hip kernels.
 Layout of the head's input rows X0[b*hw + p] = [input_proj(+GN) 256 | encoder memory 256 | attention map 8 | 0 x 56].
 """
+import collections
+
 import torch
 
 from .. import hip as H
@@ -14,6 +16,11 @@ from . import layout as L
 
 class _Conv:
     __slots__ = ("name", "cin", "cout", "k", "cip", "cop", "W", "WT", "w32", "gw", "b32", "gb")
+
+
+# One conv -> GroupNorm(8) + ReLU step of the mask head.  The FPN stages first add an adapted ResNet feature (`feat` indexes the
+# backbone's stage outputs) to the upsampled activation; lay1 / lay2 have no adapter.
+_Stage = collections.namedtuple("_Stage", "gn lay adapter feat", defaults=(None, None))
 
 
 class SegHead:
@@ -29,6 +36,10 @@ class SegHead:
             c.W = torch.empty(c.cop, k * k, c.cip, dtype=torch.bfloat16, device=dev)
             c.WT = torch.empty(c.cip, k * k, c.cop, dtype=torch.bfloat16, device=dev)
             self.convs[name.split(".")[-1]] = c
+        cv = self.convs
+        # FPN: stride 16, 8, 4 features (layer3, layer2, layer1 outputs)
+        self.stages = [_Stage(1, cv["lay1"]), _Stage(2, cv["lay2"])] + \
+                      [_Stage(j + 3, cv[f"lay{j + 3}"], cv[f"adapter{j + 1}"], fi) for j, fi in enumerate((2, 1, 0))]
         self._prep = None
 
     def refresh(self):
@@ -75,20 +86,18 @@ class SegHead:
         H.seg_concat(src32, mem32, X0, B, HW, E, nh, S, Lq)
         Pm = H.attn_map_fwd(q, kall, pad_u8, B, HW, E, nh, S, Lq, concat=X0, concat_col=2 * E)
         sv = dict(q=q, kall=kall, P=Pm, X0=X0, hs_last16=hs_last16, mem16=mem16, B=B, S=S, Lq=Lq, h=h, w=w, stages=[])
-        u1, g1 = self._conv(cv["lay1"], X0, B, h, w); a1, s1 = self._gn(1, u1, B, HW, cv["lay1"].cout)
-        u2, g2 = self._conv(cv["lay2"], a1, B, h, w); a2, s2 = self._gn(2, u2, B, HW, cv["lay2"].cout)
-        sv.update(u1=u1, g1=g1, a1=a1, s1=s1, u2=u2, g2=g2, s2=s2)
-        a, (ph, pw) = a2, (h, w)
-        # FPN: stride 16, 8, 4 features (layer3, layer2, layer1 outputs)
-        for j, fi in enumerate((2, 1, 0)):
-            f16, (_, fh, fw) = feats[fi]
-            ad, lay = cv[f"adapter{j + 1}"], cv[f"lay{j + 3}"]
-            _, fo = H.linear(f16, ad.W.view(ad.cop, ad.cip), bias=ad.b32, out_bf16=False, out_f32=True)
-            x = H.upsample_add(fo, a, B, fh, fw, ph, pw, ad.cout, ldo=lay.cip)
-            u, g = self._conv(lay, x, B, fh, fw)
-            a_new, st = self._gn(j + 3, u, B, fh * fw, lay.cout)
-            sv["stages"].append(dict(f16=f16, x=x, u=u, g=g, st=st, fh=fh, fw=fw, ph=ph, pw=pw))
-            a, (ph, pw) = a_new, (fh, fw)
+        a, (ph, pw) = X0, (h, w)
+        for gn, lay, ad, feat in self.stages:
+            rec = dict(ph=ph, pw=pw)
+            if ad is not None:
+                rec["f16"], (_, fh, fw) = feats[feat]
+                _, fo = H.linear(rec["f16"], ad.W.view(ad.cop, ad.cip), bias=ad.b32, out_bf16=False, out_f32=True)
+                a = H.upsample_add(fo, a, B, fh, fw, ph, pw, ad.cout, ldo=lay.cip)
+                ph, pw = fh, fw
+            u, g = self._conv(lay, a, B, ph, pw)
+            rec.update(x=a, u=u, g=g, fh=ph, fw=pw)
+            a, rec["st"] = self._gn(gn, u, B, ph * pw, lay.cout)
+            sv["stages"].append(rec)
         sv["a5"] = a
         po, gout = self._conv(cv["out_lay"], a, B, ph, pw)
         sv["gout"] = gout
@@ -121,22 +130,16 @@ class SegHead:
                                  P["cem_block.c2.weight"], P["cem_block.c2.bias"], sv["cem"], dcem, da,
                                  G["cem_block.c3.weight"], G["cem_block.c3.bias"], G["cem_block.c2.weight"], B, st5["fh"] * st5["fw"])
         extra = {}
-        for j in (2, 1, 0):
-            stg = sv["stages"][j]
-            ad, lay = cv[f"adapter{j + 1}"], cv[f"lay{j + 3}"]
-            fh, fw, ph, pw = stg["fh"], stg["fw"], stg["ph"], stg["pw"]
-            du = self._gn_bwd(j + 3, da, stg["u"], stg["st"], B, fh * fw, lay.cout)
-            dx = self._conv_bwd(lay, du, stg["x"], stg["g"])
-            prev_ld = cv[f"lay{j + 2}"].cop
-            da, dyb = H.upsample_add_bwd(dx, B, fh, fw, ph, pw, ad.cout, ldda=prev_ld, lddyb=ad.cop)
-            fi = (2, 1, 0)[j]
-            self.net.wg.run(lambda dyb=dyb, stg=stg, ad=ad: H.linear_wgrad(dyb, stg["f16"], ad.gw.view(ad.cop, ad.cip), dbias=ad.gb), dyb, stg["f16"])
-            if fi > 0:          # layer1 is frozen: no gradient w.r.t. the stride-4 features is needed
-                _, extra[fi] = H.linear(dyb, ad.WT.view(ad.cip, ad.cop), out_bf16=False, out_f32=True)
-        du2 = self._gn_bwd(2, da, sv["u2"], sv["s2"], B, HW, cv["lay2"].cout)
-        da1 = self._conv_bwd(cv["lay2"], du2, sv["a1"], sv["g2"])
-        du1 = self._gn_bwd(1, da1, sv["u1"], sv["s1"], B, HW, cv["lay1"].cout)
-        dX0 = self._conv_bwd(cv["lay1"], du1, sv["X0"], sv["g1"])
+        for k in reversed(range(len(self.stages))):
+            (gn, lay, ad, feat), rec = self.stages[k], sv["stages"][k]
+            du = self._gn_bwd(gn, da, rec["u"], rec["st"], B, rec["fh"] * rec["fw"], lay.cout)
+            da = self._conv_bwd(lay, du, rec["x"], rec["g"])
+            if ad is not None:
+                da, dyb = H.upsample_add_bwd(da, B, rec["fh"], rec["fw"], rec["ph"], rec["pw"], ad.cout, ldda=self.stages[k - 1].lay.cop, lddyb=ad.cop)
+                self.net.wg.run(lambda dyb=dyb, rec=rec, ad=ad: H.linear_wgrad(dyb, rec["f16"], ad.gw.view(ad.cop, ad.cip), dbias=ad.gb), dyb, rec["f16"])
+                if feat > 0:          # layer1 is frozen: no gradient w.r.t. the stride-4 features is needed
+                    _, extra[feat] = H.linear(dyb, ad.WT.view(ad.cip, ad.cop), out_bf16=False, out_f32=True)
+        dX0 = da
         dq, dk = H.attn_map_bwd(sv["q"], sv["kall"], sv["P"], dX0, B, HW, E, nh, S, Lq, 2 * E)
         dq16 = dq.to(torch.bfloat16); dk16 = dk.to(torch.bfloat16)
         _, d_hs = net.lin_bwd("bbox_attention.q_linear.", dq16, sv["hs_last16"], out_bf16=False, out_f32=True)
