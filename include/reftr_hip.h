@@ -694,6 +694,53 @@ int rt_batch_stage(const float* src_img, const uint8_t* src_mask, int B, int hs,
                    uint8_t* tgt_masks, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * rt_raw_stage — one batch of RAW images (decoded uint8 [h][w][3], any sizes) with boxes in pixels and raw-sized target masks into
+ * the same canvas buffers, ONE launch: what rt_resample_u8 x 2 + rt_img_collate_norm(pad_to) + DeviceInputPipeline._target +
+ * rt_batch_stage write, bit for bit.  Per image b (HOST values, all by value in the kernel's argument block like rt_batch_stage's):
+ *   src[b] uint8 [h[b]][w[b]][3]; the resized size oh[b] x ow[b] (reftr_amd/data/resample.py size_with_aspect_ratio, <= the canvas);
+ *   box_ptr[b] fp32 [box_n[b], 4] xyxy pixels of the raw frame (NULL when box_n[b] = 0); tm_ptr[b] one byte per pixel [h[b]][w[b]]
+ *   (read only when tgt_masks is given); rw[b] = (float)((double)ow / w), rh[b] = (float)((double)oh / h).
+ *   img fp32 [B,3,Hc,Wc]: Pillow's 8-bit bilinear resample (horizontal pass, clip8'd uint8 intermediate, vertical pass -- the filter
+ *     taps are computed in the kernel, in double, operation for operation as reftr_amd/data/resample.py taps), then
+ *     ((float)px / 255.0f - mean[c]) / std[c]; zeros outside oh x ow;
+ *   mask u8 [B,Hc,Wc]: 0 inside oh x ow, 1 outside;
+ *   tgt_masks u8 [B,1,Hc,Wc] | NULL: torch's `nearest` of the raw mask, src = min((int)floorf(dst * ((float)in / out)), in - 1) per
+ *     axis, as 0 / 1 (non-zero source byte -> 1); zeros outside oh x ow;
+ *   boxes fp32 [B*boxes_per_image, 4]: cxcywh normalised -- x * rw, y * rh, then (x0 + x1) / 2, x1 - x0, then / (float)ow, oh, no fused
+ *     multiply-add -- packed in image order, zeros behind; tgt_off int32 [B+1]; num_boxes fp32 [1], as rt_batch_stage.
+ * A workgroup owns one RT_RAW_STAGE_TILE_H x RT_RAW_STAGE_TILE_W tile of one image's canvas: it resamples horizontally, into LDS, the
+ * source rows its tile's vertical taps need; the uint8 intermediate never exists in memory.  The LDS budget bounds the down-scale:
+ * h > RT_RAW_STAGE_MAX_SCALE * oh or w > RT_RAW_STAGE_MAX_SCALE * ow on any image -> RT_ERR_UNSUPPORTED, nothing launched (also
+ * B > RT_BATCH_STAGE_MAX_B, Hc * Wc >= 2^31).  RT_ERR_BADARG, nothing launched: a NULL required pointer, a non-positive size,
+ * oh > Hc, ow > Wc, a count < 0 or > boxes_per_image.  Every byte of every destination is written by every call; 16-byte stores when
+ * Wc % 4 == 0 (fp32) / Wc % 16 == 0 (bytes) and the base is 16-byte aligned, element stores otherwise; no atomics: the same bits
+ * from run to run.
+ * rt_resample_taps — the kernel's tap function alone, for tests: bounds int32 [out_size][2] = {first index, count}, coeffs int32
+ *   [out_size][ksize] (zero behind the count); RT_ERR_BADARG for ksize < 2 * ceil(max(in / out, 1)) + 1.
+ * ------------------------------------------------------------------------------------------ */
+#define RT_RAW_STAGE_MAX_SCALE 4
+#define RT_RAW_STAGE_TILE_H 32
+#define RT_RAW_STAGE_TILE_W 64
+typedef struct rt_raw_stage_args {
+    float*   img;
+    uint8_t* mask;
+    uint8_t* tgt_masks;     /* | NULL */
+    float*   boxes;
+    int32_t* tgt_off;
+    float*   num_boxes;
+    int32_t  B, Hc, Wc, boxes_per_image;
+    float    mean[3], std[3];
+    const uint8_t* src[RT_BATCH_STAGE_MAX_B];
+    const float*   box_ptr[RT_BATCH_STAGE_MAX_B];
+    const uint8_t* tm_ptr[RT_BATCH_STAGE_MAX_B];
+    int32_t h[RT_BATCH_STAGE_MAX_B], w[RT_BATCH_STAGE_MAX_B], oh[RT_BATCH_STAGE_MAX_B], ow[RT_BATCH_STAGE_MAX_B];
+    int32_t box_n[RT_BATCH_STAGE_MAX_B];
+    float   rw[RT_BATCH_STAGE_MAX_B], rh[RT_BATCH_STAGE_MAX_B];
+} rt_raw_stage_args;
+int rt_raw_stage(const rt_raw_stage_args* a, rt_stream_t stream);
+int rt_resample_taps(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * rt_cem_fwd / rt_cem_bwd — the CEM block of RefTRSeg (--ablation cem_loss, models/reftr_segmentation.py:16-41) for the one
  * query per image of RES: u_b = c3(hs_b) (hs bf16 [B, E] = last decoder output, w3 [16, E], b3 [16]), res bf16 [B*HW, ld] =
  * MaskHeadSmallConv's last feature map (16 channels in front of the padding), a_p = res_p . w2 + b2,

@@ -10,11 +10,17 @@ on it is the existing code's step at an existing shape.
 
 `pad_on_host` is that definition in plain torch; `stage` is the same bytes written by ONE rt_batch_stage launch into buffers that
 stay where they are, which is what a captured step needs.  Opt-in: engine_vg's entry points take `canvas=None`.
+
+A RAW batch (reftr_amd.data.raw: `samples["img"]` a RawImages, targets in the raw frame) is defined the same way: `pad_on_host` runs
+the DeviceInputPipeline chain to the canvas's size and then the padding above; `stage` writes the same bytes with ONE rt_raw_stage
+launch -- resize, ToTensor, Normalize, the target transforms and the padding all happen on the way into the buffers.
 """
 import torch
 
 from .. import hip as H
 from ..util.misc import NestedTensor
+from .device_input import MEAN, STD, DeviceInputPipeline
+from .raw import RawImages
 
 
 def _token_shapes(samples):
@@ -48,6 +54,7 @@ class BatchCanvas:
         self.height, self.width, self.boxes_per_image, self.masks = int(height), int(width), int(boxes_per_image), bool(masks)
         assert self.height > 0 and self.width > 0 and self.boxes_per_image > 0
         self.tokens = tokens                     # token field shapes, bound by the first batch (from_args / bind)
+        self._pipes = {}                         # (size, max_size, padded to the canvas) -> the DeviceInputPipeline of a raw batch
 
     @classmethod
     def from_args(cls, args, samples, masks=None):
@@ -70,17 +77,44 @@ class BatchCanvas:
     def key(self, samples):
         """What a capture on this canvas depends on: the canvas, the batch size and the token field shapes -- not the image size, not
         the box counts, not the target mask sizes."""
-        return ("canvas", self.height, self.width, self.boxes_per_image, self.masks, int(samples["img"].tensors.shape[0]),
-                _token_shapes(samples))
+        img = samples["img"]
+        B = len(img) if isinstance(img, RawImages) else int(img.tensors.shape[0])
+        return ("canvas", self.height, self.width, self.boxes_per_image, self.masks, B, _token_shapes(samples))
+
+    def _why_not_raw(self, img, targets):
+        """The image and mask part of why_not for a raw batch."""
+        if not img.well_formed():
+            return "a raw image that is not uint8 [h, w, 3]"
+        S = H.RAW_STAGE_MAX_SCALE
+        for im, (oh, ow) in zip(img.images, img.out_sizes()):
+            h, w = int(im.shape[0]), int(im.shape[1])
+            if oh <= 0 or ow <= 0 or oh > self.height or ow > self.width:
+                return f"raw image {h} x {w} resized to {oh} x {ow} exceeds the canvas"
+            if h > S * oh or w > S * ow:
+                return f"raw image {h} x {w} resized to {oh} x {ow} is scaled down by more than {S}"
+        if self.masks and len(targets) == len(img):
+            for im, t in zip(img.images, targets):
+                m = t.get("masks")
+                if m is not None and m.dim() == 3 and tuple(m.shape[-2:]) != tuple(im.shape[:2]):
+                    return f"target mask {m.shape[-2]} x {m.shape[-1]} on a raw image {im.shape[0]} x {im.shape[1]}"
+        return None
 
     def why_not(self, samples, targets):
         """None when the batch fits, else the reason as a short phrase."""
         img = samples.get("img")
+        if isinstance(img, RawImages):
+            why = self._why_not_raw(img, targets)
+            return why if why is not None else self._why_not_rest(samples, targets, len(img), raw=True)
         if not isinstance(img, NestedTensor) or img.tensors.dim() != 4 or img.tensors.shape[1] != 3:
             return "no [B, 3, h, w] image NestedTensor"
         B, _, h, w = img.tensors.shape
         if h > self.height or w > self.width:
             return f"image {h} x {w} exceeds the canvas"
+        return self._why_not_rest(samples, targets, B)
+
+    def _why_not_rest(self, samples, targets, B, raw=False):
+        """Batch size, token fields, boxes and target masks: the same for both forms of a batch (a raw mask has its image's size and is
+        resized with it, so it cannot exceed the canvas)."""
         if B > H.BATCH_STAGE_MAX_B:
             return f"more than {H.BATCH_STAGE_MAX_B} images"
         if len(targets) != B:
@@ -99,7 +133,7 @@ class BatchCanvas:
                 m = t.get("masks")
                 if m is None or m.dim() != 3 or m.shape[0] != 1:
                     return "no [1, h, w] target mask"
-                if m.shape[-2] > self.height or m.shape[-1] > self.width:
+                if not raw and (m.shape[-2] > self.height or m.shape[-1] > self.width):
                     return f"target mask {m.shape[-2]} x {m.shape[-1]} exceeds the canvas"
         return None
 
@@ -134,9 +168,26 @@ class BatchCanvas:
         return None
 
     # ------------------------------------------------------------------ the definition, in plain torch
+    def resized(self, samples, targets, to_canvas=False):
+        """A raw batch through the existing device chain (DeviceInputPipeline: rt_resample_u8 per pass and image, rt_img_collate_norm,
+        the target transforms in torch): the NestedTensor form of the batch, collated to its own largest image -- or, `to_canvas`,
+        straight to the canvas's size."""
+        img = samples["img"]
+        pkey = (img.size, img.max_size, bool(to_canvas))
+        if pkey not in self._pipes:
+            self._pipes[pkey] = DeviceInputPipeline(img.size, img.max_size, device=img.device if img.is_cuda else "cuda",
+                                                    pad_to=(self.height, self.width) if to_canvas else None)
+        nested, out_t = self._pipes[pkey](img.images, targets)
+        s = dict(samples)
+        s["img"] = nested
+        return s, out_t
+
     def pad_on_host(self, samples, targets):
-        """The batch as the reference's collate would deliver it with one canvas-sized image in it: new tensors, any device."""
+        """The batch as the reference's collate would deliver it with one canvas-sized image in it: new tensors, any device.  A raw
+        batch: what the existing device chain makes of it (`resized`), padded the same way."""
         assert self.fits(samples, targets), self.why_not(samples, targets)
+        if isinstance(samples["img"], RawImages):
+            samples, targets = self.resized(samples, targets, to_canvas=True)
         img = samples["img"]
         B, C, h, w = img.tensors.shape
         t = img.tensors.new_zeros((B, C, self.height, self.width))
@@ -160,7 +211,7 @@ class BatchCanvas:
     def alloc(self, samples):
         """Static buffers for batches like `samples` (B, token shapes, device); the token fields start as copies of `samples`'s."""
         img = samples["img"]
-        dev, B = img.tensors.device, int(img.tensors.shape[0])
+        dev, B = (img.device, len(img)) if isinstance(img, RawImages) else (img.tensors.device, int(img.tensors.shape[0]))
         s = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in samples.items() if k != "img"}
         s["img"] = NestedTensor(torch.empty((B, 3, self.height, self.width), dtype=torch.float32, device=dev),
                                 torch.empty((B, self.height, self.width), dtype=torch.bool, device=dev))
@@ -170,13 +221,34 @@ class BatchCanvas:
         return StagedBatch(s, static, tm)
 
     def stage(self, samples, targets, out=None, tokens=True):
-        """Writes the batch into `out` (a StagedBatch; a fresh one when None) with one rt_batch_stage launch on the current stream
-        and returns it.  `tokens=False` leaves the token fields to the caller (the engine copies them with its grouped copy)."""
+        """Writes the batch into `out` (a StagedBatch; a fresh one when None) with one launch on the current stream -- rt_batch_stage,
+        or rt_raw_stage for a raw batch -- and returns it.  `tokens=False` leaves the token fields to the caller (the engine copies
+        them with its grouped copy)."""
         assert self.fits(samples, targets), self.why_not(samples, targets)
         fresh = out is None
         if fresh:
             out = self.alloc(samples)
         img = samples["img"]
+        if isinstance(img, RawImages):
+            self._stage_raw(img, targets, out)
+        else:
+            self._stage_nested(img, targets, out)
+        if tokens and not fresh:
+            for k, v in samples.items():
+                if torch.is_tensor(v):
+                    out.samples[k].copy_(v, non_blocking=True)
+        return out
+
+    def _stage_raw(self, img, targets, out):
+        boxes = [t["boxes"] if t["boxes"].dtype == torch.float32 else t["boxes"].float() for t in targets]
+        masks = None
+        if self.masks:           # (DeviceInputPipeline._target thresholds what is not a byte already: `.float() > 0.5`)
+            masks = [(t["masks"] if t["masks"].element_size() == 1 else t["masks"].float() > 0.5).contiguous() for t in targets]
+        H.raw_stage([im.contiguous() for im in img.images], img.out_sizes(), out.samples["img"].tensors, out.samples["img"].mask,
+                    [b.contiguous() for b in boxes], self.boxes_per_image, *out.targets_static, MEAN, STD, mask_list=masks,
+                    tgt_masks=out.tgt_masks)
+
+    def _stage_nested(self, img, targets, out):
         src = img.tensors if img.tensors.dtype == torch.float32 else img.tensors.float()
         src_mask = img.mask if img.mask.element_size() == 1 else img.mask.bool()
         boxes = [t["boxes"] if t["boxes"].dtype == torch.float32 else t["boxes"].float() for t in targets]
@@ -186,8 +258,3 @@ class BatchCanvas:
             masks = [m.contiguous() for m in masks]
         H.batch_stage(src.contiguous(), src_mask.contiguous(), out.samples["img"].tensors, out.samples["img"].mask,
                       [b.contiguous() for b in boxes], self.boxes_per_image, *out.targets_static, mask_list=masks, tgt_masks=out.tgt_masks)
-        if tokens and not fresh:
-            for k, v in samples.items():
-                if torch.is_tensor(v):
-                    out.samples[k].copy_(v, non_blocking=True)
-        return out

@@ -14,6 +14,7 @@ import sys
 import torch
 
 from . import hip as H
+from .data.raw import RawImages
 from .metrics import EvalMeter, decode_ring
 from .util import misc as utils
 from .util.box_ops import box_cxcywh_to_xyxy, box_iou, mask_iou
@@ -231,6 +232,40 @@ def _canvas_fits(model, canvas, samples, targets):
     return False
 
 
+def _is_raw(samples):
+    return isinstance(samples, dict) and isinstance(samples.get("img"), RawImages)
+
+
+def _on_device(samples):
+    """Whether the batch's image -- a NestedTensor, or a raw batch's RawImages -- is in device memory."""
+    img = samples.get("img")
+    return img.is_cuda if isinstance(img, RawImages) else isinstance(img, utils.NestedTensor) and img.tensors.is_cuda
+
+
+def _raw_batch(model, canvas, samples, targets):
+    """A raw batch (reftr_amd.data.raw) at the door of a step: -> (samples, targets, canvas) as the step machinery takes them.  One
+    that fits the canvas goes on as it is: BatchCanvas.stage writes it with one rt_raw_stage launch.  One that does not is converted
+    once by the existing device chain (BatchCanvas.resized) and takes the existing path at its own shape, without the canvas; said
+    once per reason.  Without a canvas there is nowhere to stage it: refused."""
+    if not _is_raw(samples):
+        return samples, targets, canvas
+    if canvas is None:
+        raise NotImplementedError("a raw batch (reftr_amd.data.RawImages) needs canvas=: rt_raw_stage writes it into a canvas's "
+                                  "buffers; without one, run reftr_amd.data.DeviceInputPipeline in the loader's collate")
+    _canvas_single_process(model)
+    cap = _state(model).staged_cap
+    if cap is not None and cap._staged is not None and cap._staged[0] is samples:
+        return samples, targets, canvas               # checked when the previous iteration's lookahead staged it
+    if not samples["img"].is_cuda:                    # a host batch: the raw bytes cross, everything else happens on the device
+        samples, targets = _to_device(samples, targets, _inner(model).store.device)
+    why = canvas.why_not(samples, targets)
+    if why is None:
+        return samples, targets, canvas
+    _say_once(model, ("canvas", why), f"[reftr_amd] raw batch does not fit {canvas!r} ({why}): it is resized by the DeviceInputPipeline "
+              "chain and runs at its own shape, captured if fewer than max_shapes shapes are in use, else eagerly")
+    return (*canvas.resized(samples, targets), None)
+
+
 _UNSCALED = "{}_unscaled".format          # a loss term's name on the stats board beside its weighted value
 
 
@@ -266,8 +301,7 @@ def _eager_iteration(model, criterion, samples, targets, optimizer):
 def _train_step_canvas(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end, canvas):
     """train_step on the canvas form of the batch: staged by rt_batch_stage into fresh buffers (device batches; the criterion reads
     the staged targets), or padded by canvas.pad_on_host (host batches).  The same step as `train_step` of the padded batch."""
-    img = samples.get("img")
-    if not (isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and hasattr(criterion, "targets_static")):
+    if not (_on_device(samples) and hasattr(criterion, "targets_static")):
         samples, targets = canvas.pad_on_host(samples, targets)
         return train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end)
     staged = canvas.stage(samples, targets)
@@ -293,6 +327,7 @@ def train_step(model, criterion, samples, targets, optimizer, lr_scheduler=None,
     (optimizer.finish_accumulation(), s = 1 / r), then clips, updates and steps the scheduler ONCE and returns the norm of the
     averaged gradient.  The non-finite-loss stop and the cooperative decoder's re-run act on every micro-batch."""
     accum_steps = int(accum_steps)
+    samples, targets, canvas = _raw_batch(model, canvas, samples, targets)
     if canvas is not None and _canvas_fits(model, canvas, samples, targets):
         return _train_step_canvas(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end, canvas)
     if accum_steps > 1:
@@ -986,8 +1021,7 @@ def _find_capture(model, criterion, samples, targets, optimizer, max_norm, max_s
     state.staged_cap = None
     inner = _inner(model)
     caps = inner.__dict__.setdefault("_captured_steps", {})
-    img = samples.get("img")
-    ok = isinstance(img, utils.NestedTensor) and img.tensors.is_cuda and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1"
+    ok = _on_device(samples) and os.environ.get("REFTR_TRAIN_GRAPH", "1") == "1"
     if accumulate:                                    # (the caller has checked _require_accumulation)
         ok = ok and not dist_on and model is inner
     else:
@@ -1080,6 +1114,7 @@ def begin_train_step(model, criterion, samples, targets, optimizer, lr_scheduler
     accumulate = accum_steps > 1
     if accumulate:
         _require_accumulation(optimizer)
+    samples, targets, canvas = _raw_batch(model, canvas, samples, targets)
     how, cap, on_canvas, nb_reduced = _find_capture(model, criterion, samples, targets, optimizer, max_norm, max_shapes, canvas, accumulate)
     if how == "eager":
         return _EagerResult(train_step(model, criterion, samples, targets, optimizer, lr_scheduler, max_norm, accum_steps, window_end,
@@ -1614,6 +1649,9 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     prefetcher = data_prefetcher(data_loader, device, prefetch=True)
     samples, targets = prefetcher.next()
     for batch_no in board.log_every(range(len(data_loader)), 50, "Test:"):
+        if _is_raw(samples):
+            raise NotImplementedError("evaluate: a raw batch (reftr_amd.data.RawImages) is not taken: the metric tail reads the resized "
+                                      "`size` of every image from device memory (rt_eval_facts), which a raw batch has on the host only")
         path(batch_no, samples, targets)
         samples, targets = prefetcher.next()
     _check_cooperative(model)

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 # The Python copy of the header's #defines and enumerators (tests/test_abi.py prints each from C and compares) ...
 CONSTANTS = {
@@ -23,6 +23,8 @@ CONSTANTS = {
     "RT_SQ_SLOTS": 256, "RT_SQ_STRIDE": 32,
     "RT_MASK_LOSS_PARTIALS": 1024, "RT_STATS_MAX": 40,
     "RT_BATCH_STAGE_MAX_B": 64,          # what fits the kernel's argument block
+    # rt_raw_stage: the largest in / out per axis its LDS budget admits, and its output tile
+    "RT_RAW_STAGE_MAX_SCALE": 4, "RT_RAW_STAGE_TILE_H": 32, "RT_RAW_STAGE_TILE_W": 64,
     # rt_eval_metrics: accumulator slots (8 bytes each: int64 but for the two double sums) and the mask kernel's pixels per workgroup
     "RT_EVAL_DET_N": 0, "RT_EVAL_DET_HIT": 1, "RT_EVAL_SEG_N": 6, "RT_EVAL_SEG_HIT": 7, "RT_EVAL_SEG_I": 12, "RT_EVAL_SEG_U": 13,
     "RT_EVAL_DET_SUM": 14, "RT_EVAL_SEG_SUM": 15, "RT_EVAL_SLOTS": 16, "RT_EVAL_CHUNK": 16384,
@@ -252,6 +254,16 @@ class EvalCanvasArgs(_Abi, c="rt_eval_canvas_args"):
                 ("Wc", c_int32), ("tgt_rows", c_int32), ("slots", c_int32), ("threshold", c_float)]
 
 
+class RawStageArgs(_Abi, c="rt_raw_stage_args"):
+    _N = CONSTANTS["RT_BATCH_STAGE_MAX_B"]
+    _fields_ = [("img", c_void_p), ("mask", c_void_p), ("tgt_masks", c_void_p), ("boxes", c_void_p), ("tgt_off", c_void_p),
+                ("num_boxes", c_void_p), ("B", c_int32), ("Hc", c_int32), ("Wc", c_int32), ("boxes_per_image", c_int32),
+                ("mean", c_float * 3), ("std", c_float * 3),
+                ("src", c_void_p * _N), ("box_ptr", c_void_p * _N), ("tm_ptr", c_void_p * _N),
+                ("h", c_int32 * _N), ("w", c_int32 * _N), ("oh", c_int32 * _N), ("ow", c_int32 * _N), ("box_n", c_int32 * _N),
+                ("rw", c_float * _N), ("rh", c_float * _N)]
+
+
 class DecoderLayerFwd(_Abi, c="rt_decoder_layer_fwd"):
     _PTRS = ("Wv", "Wo", "Wq", "Wo2", "W1", "W2", "bv", "bo", "bq", "bo2", "b1", "b2", "g1", "be1", "g2", "be2", "g3", "be3",
              "k2", "v2", "o", "t1q16", "q2", "o2", "t2_16", "hdn", "t3_16", "u", "u2", "u3",
@@ -371,6 +383,8 @@ _SIGNATURES = {
     "rt_batch_stage": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, POINTER(c_void_p),
                                POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_int32),
                                c_void_p, c_void_p]),
+    "rt_raw_stage": (c_int, [POINTER(RawStageArgs), c_void_p]),
+    "rt_resample_taps": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "rt_gn_nhwc_fwd": (c_int, [POINTER(GnNhwcDesc), c_void_p]),
     "rt_gn_nhwc_bwd": (c_int, [POINTER(GnNhwcBwdDesc), c_void_p]),
     "rt_upsample_add": (c_int, [POINTER(UpsampleAddDesc), c_void_p]),
@@ -1712,6 +1726,52 @@ def batch_stage(src_img, src_mask, img, mask, box_list, boxes_per_image, boxes, 
         thw = (c_int32 * (2 * B))(*[v for t in mask_list for v in t.shape[-2:]])
     _call("rt_batch_stage", src_img, src_mask, B, hs, ws, img, mask, Hc, Wc, bp, bn, int(boxes_per_image), boxes, tgt_off, num_boxes, tp, thw,
           tgt_masks if mask_list is not None else None)
+
+
+def raw_stage(images, out_sizes, img, mask, box_list, boxes_per_image, boxes, tgt_off, num_boxes, mean, std, mask_list=None,
+              tgt_masks=None):
+    """rt_raw_stage: one batch of raw images into fixed canvas buffers, one launch, every destination byte rewritten.
+    images: B uint8 [h_b, w_b, 3] device tensors, out_sizes: their resized (oh_b, ow_b) (resample.size_with_aspect_ratio) ->
+    img fp32 [B,3,Hc,Wc] (Pillow's bilinear resize, ToTensor, Normalize, zero padded) / mask [B,Hc,Wc] (1 = padding);
+    box_list: B fp32 [n_b, 4] xyxy pixels of the raw frame -> boxes [B*boxes_per_image, 4] cxcywh normalised and packed, tgt_off
+    int32 [B+1], num_boxes fp32 [1]; mask_list (optional): B one-byte [1, h_b, w_b] raw masks -> tgt_masks u8 [B,1,Hc,Wc] (nearest).
+    Every pointer and size goes by value in the kernel arguments: nothing is copied to the device and nothing synchronises."""
+    _req(img, torch.float32, "img"); _req(boxes, torch.float32, "boxes"); _req(tgt_off, torch.int32, "tgt_off")
+    _req(num_boxes, torch.float32, "num_boxes")
+    B = len(images)
+    Hc, Wc = img.shape[-2:]
+    assert 0 < B <= BATCH_STAGE_MAX_B and len(out_sizes) == B and len(box_list) == B
+    assert img.is_contiguous() and mask.is_contiguous() and mask.element_size() == 1
+    assert tuple(img.shape) == (B, 3, Hc, Wc) and tuple(mask.shape) == (B, Hc, Wc)
+    assert boxes.numel() == B * boxes_per_image * 4 and tgt_off.numel() == B + 1 and num_boxes.numel() == 1
+    for t in images:
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3
+    for t in box_list:
+        assert t.numel() == 0 or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4)
+    if mask_list is not None:
+        assert len(mask_list) == B and tgt_masks is not None and tgt_masks.numel() == B * Hc * Wc and tgt_masks.element_size() == 1
+        for t, im in zip(mask_list, images):
+            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous() and tuple(t.shape[-2:]) == tuple(im.shape[:2])
+            assert t.numel() == im.shape[0] * im.shape[1]
+    hs, ws = [t.shape[0] for t in images], [t.shape[1] for t in images]
+    ohs, ows = [int(s[0]) for s in out_sizes], [int(s[1]) for s in out_sizes]
+    n = BATCH_STAGE_MAX_B          # (ready-made ctypes arrays: _desc copies them as they are, a list it would convert element by element)
+    _call("rt_raw_stage", _desc(
+        RawStageArgs, img=img, mask=mask, tgt_masks=tgt_masks if mask_list is not None else None, boxes=boxes, tgt_off=tgt_off,
+        num_boxes=num_boxes, B=B, Hc=Hc, Wc=Wc, boxes_per_image=int(boxes_per_image), mean=(c_float * 3)(*mean), std=(c_float * 3)(*std),
+        src=(c_void_p * n)(*[t.data_ptr() for t in images]), box_ptr=(c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in box_list]),
+        tm_ptr=(c_void_p * n)(*[t.data_ptr() for t in mask_list]) if mask_list is not None else (c_void_p * n)(),
+        h=(c_int32 * n)(*hs), w=(c_int32 * n)(*ws), oh=(c_int32 * n)(*ohs), ow=(c_int32 * n)(*ows),
+        box_n=(c_int32 * n)(*[t.shape[0] for t in box_list]), rw=(c_float * n)(*[float(o) / float(i) for o, i in zip(ows, ws)]),
+        rh=(c_float * n)(*[float(o) / float(i) for o, i in zip(ohs, hs)])))
+
+
+def resample_taps(in_size, out_size, ksize, device="cuda"):
+    """rt_resample_taps: the filter taps rt_raw_stage computes for one axis -> (bounds int32 [out, 2], coeffs int32 [out, ksize])."""
+    bounds = torch.empty((out_size, 2), dtype=torch.int32, device=device)
+    coeffs = torch.empty((out_size, ksize), dtype=torch.int32, device=device)
+    _call("rt_resample_taps", int(in_size), int(out_size), bounds, coeffs, int(ksize))
+    return bounds, coeffs
 
 
 # --------------------------------------------------------------------------------------------
