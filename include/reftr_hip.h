@@ -55,9 +55,10 @@ int rt_device_arch(int dev, char* buf, int buflen);
  *
  * src   bf16 [B, SH, SW, SC]  (NHWC)         wgt  bf16 [N][KH][KW][SC]
  * out   [B, DH, DW, N] written as bf16 (out_bf16) and/or fp32 (out_f32)
- * forward gather   : src pixel = (dy*stride - pad + kh, dx*stride - pad + kw)
- * transposed gather: src pixel = ((dy + pad - kh)/stride, (dx + pad - kw)/stride) where divisible
- * epilogue order   : +bias[n] -> act -> dropout(drop_p, drop_seed; index m*N+n) -> +res -> *gate -> *gelu'(preact) -> *(1-dtanh^2)
+ * forward gather   : src pixel = (dy*stride - pad + kh*dil, dx*stride - pad + kw*dil)
+ * transposed gather: src pixel = ((dy + pad - kh*dil)/stride, (dx + pad - kw*dil)/stride) where divisible
+ * epilogue order   : +bias[n] -> store out_preact -> [+res if res_first] -> act -> dropout(drop_p, drop_seed; index (m*N+n) >> drop_shift)
+ *                    -> [+res unless res_first] -> *gate -> *gelu'(preact) -> *(1-dtanh^2) -> out_f32, acc2_f32 +=, out_bf16
  * constraints      : SC % 64 == 0, N % 4 == 0, stride in {1,2}
  * ------------------------------------------------------------------------------------------ */
 typedef struct rt_conv_gemm_desc {

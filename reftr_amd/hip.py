@@ -617,7 +617,7 @@ def conv_gemm(src, wgt, *, geom, bias=None, res_f32=None, res_bf16=None, gate=No
     """out[B,DH,DW,N] = epilogue(implicit_gemm(src[B,SH,SW,SC], wgt[N,KH,KW,SC])).
 
     geom = (B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad).  Returns (out_bf16 | None, out_f32 | None)
-    (+ the bf16 pre-activation as a third value when out_preact=True).  out_bf16 / out_f32 may be True (allocate
+    (+ the bf16 pre-activation as a third value when out_preact is given).  out_bf16 / out_f32 / out_preact may be True (allocate
     [M, N]) or an existing tensor to write into (in-place accumulation when it is also `res_f32`).
     """
     B, SH, SW, SC, DH, DW, N, KH, KW, stride, pad = geom
@@ -637,9 +637,8 @@ def conv_gemm(src, wgt, *, geom, bias=None, res_f32=None, res_bf16=None, gate=No
                    transposed=int(bool(transposed)), act=act, gate_scale=gate_scale, drop_p=drop_p, drop_seed=drop_seed & 0xFFFFFFFF,
                    tile_hint=tile_hint, dtanh=dtanh, res_first=int(bool(res_first)), seed_dev=_seedp(drop_p), drop_shift=drop_shift,
                    acc2_f32=acc2_f32, dil=int(dil))
-    op = None
-    if out_preact:
-        op = torch.empty((M, N), dtype=torch.bfloat16, device=src.device)
+    op = _out_buffer(out_preact, torch.bfloat16, "out_preact", M, N, src.device)
+    if op is not None:
         _set(d, out_preact=op)
     if transposed:     # algorithmic FLOPs of backward-data = those of the forward conv it differentiates
         flops = 2.0 * B * SH * SW * SC * N * KH * KW
@@ -650,12 +649,12 @@ def conv_gemm(src, wgt, *, geom, bias=None, res_f32=None, res_bf16=None, gate=No
     # every output beyond the first bf16 one
     epi = M * N * (2.0 * sum(t is not None for t in (res_bf16, gate, preact, dtanh)) + 4.0 * (res_f32 is not None)
                    + 8.0 * (acc2_f32 is not None) + (4.0 if of is not None else 0.0) + (2.0 if ob is not None else 0.0) - 2.0
-                   + (2.0 if out_preact else 0.0))
+                   + (2.0 if op is not None else 0.0))
     if group is not None:      # queued: GemmGroup.run() launches every queued product at once
         group.add(d, flops, ("T" if transposed else "F",) + tuple(geom), (src, wgt, ob, of, op, bias, res_f32, res_bf16, gate, preact, dtanh), epi)
     else:
         _timed("conv_gemm", flops, lambda: _call("rt_conv_gemm", d), tag=("T" if transposed else "F",) + tuple(geom), epi_bytes=epi)
-    if out_preact:
+    if op is not None:
         return ob, of, op
     return ob, of
 
