@@ -31,9 +31,43 @@ __global__ __launch_bounds__(256) void img_pack_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------- stem conv
-// One wave per output row (b, oh): the 64x224 folded weight lives in registers as 7 x 4 bf16x8 MFMA A
-// fragments; for every 16-pixel tile and kernel row kh the B fragment is ONE 16-byte global load per lane:
+// The 64x224 folded weight lives in registers as 7 x 4 bf16x8 MFMA A fragments (lane (li, lg)'s), beside the lane's four bias pieces;
+// for a 16-pixel tile and kernel row kh the B fragment is ONE 16-byte global load per lane:
 // lane (i, g) needs taps 2g, 2g+1 of output pixel ow0+i = padded input columns 2*(ow0+i) + 2g, +1 (8 bf16).
+struct StemWeights {
+    bf16x8 wf[7][4];
+    f32x4 bv[4];
+    __device__ __forceinline__ StemWeights(const bf16_t* __restrict__ w, const float* __restrict__ bias, int li, int lg) {
+#pragma unroll
+        for (int kh = 0; kh < 7; ++kh)
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                wf[kh][nt] = *reinterpret_cast<const bf16x8*>(w + ((size_t)(nt * 16 + li) * 7 + kh) * 32 + lg * 8);
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) bv[nt] = *reinterpret_cast<const f32x4*>(bias + nt * 16 + lg * 4);
+    }
+    // one tile: 28 MFMAs over the seven input fragments x(kh), each asked for where it is used; ov[nt] = bf16(max(acc + bias, 0)) of
+    // channels nt * 16 + lg * 4 .. + 3
+    template <class X>
+    __device__ __forceinline__ void tile(X x, bf16x4 (&ov)[4]) const {
+        f32x4 acc[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kh = 0; kh < 7; ++kh) {
+            const bf16x8 xf = x(kh);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kh][nt], xf, acc[nt], 0, 0, 0);
+        }
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ov[nt][r] = (bf16_t)fmaxf(acc[nt][r] + bv[nt][r], 0.f);
+    }
+};
+
+// One wave per output row (b, oh), walking its 16-pixel tiles.
 __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_t* __restrict__ xp, const bf16_t* __restrict__ w,
                                                         const float* __restrict__ bias, bf16_t* __restrict__ out,
                                                         int B, int Hp, int Wp, int Ho, int Wo) {
@@ -43,38 +77,17 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const bf16_t* __restrict
     const int row = rt_xcd_remap((int)blockIdx.x, (int)gridDim.x, 1) * 4 + wave;          // (b, oh)
     if (row >= B * Ho) return;
     const int b = row / Ho, oh = row % Ho;
-    bf16x8 wf[7][4];
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-            wf[kh][nt] = *reinterpret_cast<const bf16x8*>(w + ((size_t)(nt * 16 + li) * 7 + kh) * 32 + lg * 8);
-    f32x4 bv[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) bv[nt] = *reinterpret_cast<const f32x4*>(bias + nt * 16 + lg * 4);
+    const StemWeights sw(w, bias, li, lg);
     const bf16_t* xrow = xp + ((size_t)b * Hp + 2 * oh) * Wp * 4;
     const int tiles = (Wo + 15) >> 4;
     for (int tile = 0; tile < tiles; ++tile) {
         const int ow = tile * 16 + li;
-        f32x4 acc[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kh = 0; kh < 7; ++kh) {
-            const bf16x8 xf = *reinterpret_cast<const bf16x8*>(xrow + ((size_t)kh * Wp + 2 * ow + 2 * lg) * 4);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kh][nt], xf, acc[nt], 0, 0, 0);
-        }
+        bf16x4 ov[4];
+        sw.tile([&](int kh) { return *reinterpret_cast<const bf16x8*>(xrow + ((size_t)kh * Wp + 2 * ow + 2 * lg) * 4); }, ov);
         if (ow < Wo) {
             bf16_t* o = out + (((size_t)b * Ho + oh) * Wo + ow) * 64;
 #pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                bf16x4 ov;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)fmaxf(acc[nt][r] + bv[nt][r], 0.f);
-                *reinterpret_cast<bf16x4*>(o + nt * 16 + lg * 4) = ov;
-            }
+            for (int nt = 0; nt < 4; ++nt) *reinterpret_cast<bf16x4*>(o + nt * 16 + lg * 4) = ov[nt];
         }
     }
 }
@@ -116,7 +129,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const bf16_t* __restrict__
 
 // ---------------------------------------------------------------- stem conv + max pool in one launch
 // A workgroup owns an 8 x 16 tile of POOLED pixels: its four waves compute the 17 x 33 stem pixels under it (36 MFMA pixel tiles
-// of 16, nine per wave, weights in registers exactly as in stem_conv_kernel; the next tile's seven 16-byte loads are in flight
+// of 16, nine per wave, stem_conv_kernel's StemWeights and tile; the next tile's seven 16-byte loads are in flight
 // under the 28 MFMAs of the current one), round them to bf16 into LDS (72 KB, 16-byte slots XOR-swizzled by the pixel), and pool
 // from there: the 105 MB stem output of a 640 x 640 batch of 8 is neither written nor read back.  Same products, same K order,
 // same rounding point as the two launches it replaces, and max commutes with the (monotonic) rounding: bit-identical.
@@ -139,15 +152,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
     const int b = blk / tiles_y;
     const int py0 = ty * SP_PH, px0 = tx * SP_PW;
     const int sy0 = 2 * py0 - 1, sx0 = 2 * px0 - 1;                    // stem pixel of tile-local (0, 0)
-    bf16x8 wf[7][4];
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-            wf[kh][nt] = *reinterpret_cast<const bf16x8*>(w + ((size_t)(nt * 16 + li) * 7 + kh) * 32 + lg * 8);
-    f32x4 bv[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) bv[nt] = *reinterpret_cast<const f32x4*>(bias + nt * 16 + lg * 4);
+    const StemWeights sw(w, bias, li, lg);
     const bf16_t* ximg = xp + (size_t)b * Hp * Wp * 4;
     // stem pixels outside the image (the pool's padding, tile overhang) are computed at a clamped position and never read back
     auto src = [&](int t) -> const bf16_t* {
@@ -163,22 +168,13 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
         for (int kh = 0; kh < 7; ++kh) x[kh] = *reinterpret_cast<const bf16x8*>(s0 + (size_t)kh * Wp * 4);
     };
     auto compute = [&](const bf16x8 (&x)[7], int t) {
-        f32x4 acc[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[kh][nt], x[kh], acc[nt], 0, 0, 0);
+        bf16x4 ov[4];
+        sw.tile([&](int kh) { return x[kh]; }, ov);
         const int p = (wave + 4 * t) * 16 + li;
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
-            bf16x4 ov;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ov[r] = (bf16_t)fmaxf(acc[nt][r] + bv[nt][r], 0.f);
             const int slot = (nt * 2 + (lg >> 1)) ^ (p & 7);
-            *reinterpret_cast<bf16x4*>(sm + (size_t)p * 64 + slot * 8 + (lg & 1) * 4) = ov;
+            *reinterpret_cast<bf16x4*>(sm + (size_t)p * 64 + slot * 8 + (lg & 1) * 4) = ov[nt];
         }
     };
     static_assert(SP_TILES % 4 == 0 && (SP_TILES / 4) % 2 == 1, "nine tiles per wave: four pairs and one");
@@ -223,39 +219,14 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const bf16_t* __restr
 }
 
 // ---------------------------------------------------------------- weight prep
-// src fp32 [N][T][C] -> dst bf16 [N][T][Cpad] (C padded with zeros; used by the stem with T=7x8 taps) and/or
-// dst_t bf16 [C][T][N]; both multiplied by scale[n] when given.
-__global__ __launch_bounds__(256) void weight_prep_kernel(const float* __restrict__ src, const float* __restrict__ scale,
-                                                          bf16_t* __restrict__ dst, bf16_t* __restrict__ dst_t,
-                                                          int N, int T, int C) {
-    const size_t total = (size_t)N * T * C;
-    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        const size_t r = i / C;
-        const int t = (int)(r % T);
-        const int n = (int)(r / T);
-        float v = src[i];
-        if (scale) v *= scale[n];
-        const bf16_t bvv = (bf16_t)v;
-        if (dst) dst[i] = bvv;
-        if (dst_t) dst_t[((size_t)c * T + t) * N + n] = bvv;
-    }
-}
-
-// One launch for all per-step operand refreshes: job table in device memory, 64(n) x 64(c) tiles per tap.  A thread moves 8
-// consecutive elements: two 16-B fp32 loads, one 16-B bf16 store per copy (the element-per-thread version wrote 2 B per lane and
-// ran at 3.4 TB/s); the transposed copy goes through a padded LDS tile and is written in 16-B pieces of the [C][T][N] rows.
-// Jobs whose C (direct copy) or N (transposed copy) is not a multiple of 8, or whose rows are not 16-B aligned, take the
-// element-wise path of the same tile.
-__global__ __launch_bounds__(256) void weight_prep_batched_kernel(const int64_t* __restrict__ table, int njobs) {
+// src fp32 [N][T][C] -> dst bf16 [N][T][C] and/or dst_t bf16 [C][T][N]; both multiplied by scale[n] when given.
+// Tile `local` of one job: 64(n) x 64(c) tiles per tap.  A thread moves 8 consecutive elements: two 16-B fp32 loads, one 16-B bf16
+// store per copy (an element-per-thread version wrote 2 B per lane and ran at 3.4 TB/s); the transposed copy goes through a padded
+// LDS tile and is written in 16-B pieces of the [C][T][N] rows.  Jobs whose C (direct copy) or N (transposed copy) is not a multiple
+// of 8, or whose rows are not 16-B aligned, take the element-wise path of the same tile.
+__device__ __forceinline__ void weight_prep_tile(const float* src, const float* scale, bf16_t* dst, bf16_t* dst_t, int N, int T, int C,
+                                                 int local) {
     __shared__ float tile[64][65];
-    const int64_t* j = table + rt_job_of(table, njobs, blockIdx.x) * 8;
-    const float* src = reinterpret_cast<const float*>(j[0]);
-    const float* scale = reinterpret_cast<const float*>(j[1]);
-    bf16_t* dst = reinterpret_cast<bf16_t*>(j[2]);
-    bf16_t* dst_t = reinterpret_cast<bf16_t*>(j[3]);
-    const int N = (int)j[4], T = (int)j[5], C = (int)j[6];
-    const int local = blockIdx.x - (int)j[7];
     const int ct = (C + 63) >> 6, nt = (N + 63) >> 6;
     const int tc = local % ct, tn = (local / ct) % nt, tap = local / (ct * nt);
     const bool vec_c = (C & 7) == 0 && ((uintptr_t)src & 15) == 0 && (!dst || ((uintptr_t)dst & 15) == 0);
@@ -316,6 +287,19 @@ __global__ __launch_bounds__(256) void weight_prep_batched_kernel(const int64_t*
             if (n < N && c < C) dst_t[((size_t)c * T + tap) * N + n] = (bf16_t)tile[tx][ty + r * 4];
         }
     }
+}
+
+// One launch for all per-step operand refreshes: the jobs {src, scale, dst, dst_t, N, T, C, first tile} in a device table ...
+__global__ __launch_bounds__(256) void weight_prep_batched_kernel(const int64_t* __restrict__ table, int njobs) {
+    const int64_t* j = table + rt_job_of(table, njobs, blockIdx.x) * 8;
+    weight_prep_tile(reinterpret_cast<const float*>(j[0]), reinterpret_cast<const float*>(j[1]), reinterpret_cast<bf16_t*>(j[2]),
+                     reinterpret_cast<bf16_t*>(j[3]), (int)j[4], (int)j[5], (int)j[6], blockIdx.x - (int)j[7]);
+}
+
+// ... and one job in the arguments: no table to allocate or copy for a single call
+__global__ __launch_bounds__(256) void weight_prep_one_kernel(const float* src, const float* scale, bf16_t* dst, bf16_t* dst_t, int N, int T,
+                                                              int C) {
+    weight_prep_tile(src, scale, dst, dst_t, N, T, C, blockIdx.x);
 }
 
 // stem: src fp32 [64][7][7][3] (channels_last view of [64,3,7,7]) -> bf16 [64][7][8][4], zero padded
@@ -438,9 +422,9 @@ extern "C" int rt_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int 
 extern "C" int rt_weight_prep(const float* src, const float* scale, void* dst, void* dst_t, int N, int T, int C,
                               rt_stream_t stream) {
     if (!src || (!dst && !dst_t)) return RT_ERR_BADARG;
-    const size_t total = (size_t)N * T * C;
-    int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(weight_prep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+    const size_t tiles = (size_t)((N + 63) / 64) * ((C + 63) / 64) * T;
+    if (tiles >= ((size_t)1 << 31)) return RT_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(weight_prep_one_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream,
                        src, scale, (bf16_t*)dst, (bf16_t*)dst_t, N, T, C);
     RT_CHECK_LAUNCH();
     return RT_OK;

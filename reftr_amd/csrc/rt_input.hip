@@ -3,16 +3,9 @@
 // ToTensor + Normalize + batch padding (transforms.py:233-263, util/collate_fn.py:24-41) in one pass.
 // Integer / byte work, HBM-bound: bit-exact by construction -- the 22-bit fixed-point filter taps are computed on the host
 // in double precision exactly as Pillow does (reftr_amd/data/resample.py) and the kernels only multiply-accumulate int32.
-#include "rt_common.h"
+#include "rt_stage.h"
 
 namespace {
-
-constexpr int PRECISION_BITS = 32 - 8 - 2;
-
-__device__ __forceinline__ uint8_t clip8(int v) {
-    v >>= PRECISION_BITS;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
 
 // One resampling pass along `axis` (0 = rows / vertical, 1 = columns / horizontal) of src[n0][n1][C] (uint8):
 // out[i][j][c] = clip8(2^21 + sum_t src[..][lo + t][..] * k[t]); bounds[o] = {lo, n taps}, coeffs[o][ksize].
@@ -27,7 +20,7 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const uint8_t* __restr
         const int o = axis == 0 ? y : x;
         const int lo = bounds[2 * o], n = bounds[2 * o + 1];
         const int* k = coeffs + (size_t)o * ksize;
-        int acc = 1 << (PRECISION_BITS - 1);
+        int acc = RT_RESAMPLE_HALF;
         if (axis == 1) {
             const uint8_t* s = src + ((size_t)y * n1 + lo) * C + c;
             for (int j = 0; j < n; ++j) acc += (int)s[(size_t)j * C] * k[j];
@@ -35,7 +28,7 @@ __global__ __launch_bounds__(256) void resample_u8_kernel(const uint8_t* __restr
             const uint8_t* s = src + ((size_t)lo * n1 + x) * C + c;
             for (int j = 0; j < n; ++j) acc += (int)s[(size_t)j * n1 * C] * k[j];
         }
-        dst[i] = clip8(acc);
+        dst[i] = rt_clip8(acc);
     }
 }
 
@@ -53,7 +46,7 @@ __global__ __launch_bounds__(256) void collate_norm_kernel(const long long* __re
         float v0 = 0.f, v1 = 0.f, v2 = 0.f;
         if (in) {
             const uint8_t* px = img + ((size_t)y * w + x) * 3;
-            v0 = ((float)px[0] / 255.0f - m0) / s0; v1 = ((float)px[1] / 255.0f - m1) / s1; v2 = ((float)px[2] / 255.0f - m2) / s2;
+            v0 = rt_norm_u8(px[0], m0, s0); v1 = rt_norm_u8(px[1], m1, s1); v2 = rt_norm_u8(px[2], m2, s2);
         }
         const size_t plane = (size_t)H * W, o = (size_t)b * 3 * plane + (size_t)y * W + x;
         out[o] = v0; out[o + plane] = v1; out[o + 2 * plane] = v2;
@@ -78,70 +71,64 @@ struct BatchStageArgs {
 };
 static_assert(sizeof(BatchStageArgs) <= 4096, "the argument block of a launch");
 
-// unit u of a [planes][Hc][Wc] byte destination: dst rows <- src[h][w] (plane `p`'s source), `fill` outside
-template <int V>
-__device__ __forceinline__ void stage_bytes(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int h, int w, int Hc, int Wc,
-                                            int p, int y, int x, uint8_t fill) {
+// unit u of a [planes][Hc][Wc] destination with `vec` elements per unit: plane p, row y, first column x
+__device__ __forceinline__ void unit_at(unsigned u, int vec, int Hc, int Wc, int& p, int& y, int& x) {
+    const unsigned ru = (unsigned)(Wc / vec), t = u / ru;
+    x = (int)(u % ru) * vec; y = (int)(t % (unsigned)Hc); p = (int)(t / (unsigned)Hc);
+}
+
+// the unit at (p, y, x) of a [planes][Hc][Wc] destination <- src[h][w] (plane p's source), `fill` outside: one element (vec == 1), or the
+// 16-byte unit of rt_stage.h, read with one 16-byte load when it lies inside the source row at an aligned address
+__device__ __forceinline__ void stage_unit(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int h, int w, int Hc, int Wc, int vec,
+                                           int p, int y, int x, uint8_t fill) {
     uint8_t* d = dst + ((size_t)p * Hc + y) * Wc + x;
-    if constexpr (V == 1) {
-        *d = (y < h && x < w) ? src[(size_t)y * w + x] : fill;
+    const uint8_t* s = src + (size_t)y * w + x;
+    if (vec == 1) { *d = (y < h && x < w) ? *s : fill; return; }
+    rt_bytes16 v;
+    if (y < h && x + 15 < w && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+        v.q = *reinterpret_cast<const uint4*>(s);
     } else {
-        union { uint4 q; uint8_t b[16]; } v;
-        const uint8_t* s = src + (size_t)y * w + x;
-        if (y < h && x + 15 < w && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
-            v.q = *reinterpret_cast<const uint4*>(s);
-        } else {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) v.b[j] = (y < h && x + j < w) ? s[j] : fill;
-        }
-        *reinterpret_cast<uint4*>(d) = v.q;
+        for (int j = 0; j < 16; ++j) v.e[j] = (y < h && x + j < w) ? s[j] : fill;
     }
+    rt_store_unit(d, v, true, x, Wc);
+}
+__device__ __forceinline__ void stage_unit(float* __restrict__ dst, const float* __restrict__ src, int h, int w, int Hc, int Wc, int vec,
+                                           int p, int y, int x, float fill) {
+    float* d = dst + ((size_t)p * Hc + y) * Wc + x;
+    const float* s = src + (size_t)y * w + x;
+    if (vec == 1) { *d = (y < h && x < w) ? *s : fill; return; }
+    float v[4] = {fill, fill, fill, fill};
+    if (y < h && x + 3 < w && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
+        const float4 q = *reinterpret_cast<const float4*>(s);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else if (y < h) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (x + j < w) v[j] = s[j];
+    }
+    *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
 __global__ __launch_bounds__(256) void batch_stage_kernel(const BatchStageArgs a) {
     const size_t total = (size_t)a.n_img + a.n_mask + a.n_tm + a.n_box;
     for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        if (i < a.n_img) {
-            const unsigned u = (unsigned)i, ru = (unsigned)(a.Wc / a.img_vec);
-            const int x = (int)(u % ru) * a.img_vec; const unsigned t = u / ru;
-            const int y = (int)(t % (unsigned)a.Hc), p = (int)(t / (unsigned)a.Hc);          // p = b * 3 + c
-            float* d = a.img + ((size_t)p * a.Hc + y) * a.Wc + x;
-            const float* s = a.src_img + ((size_t)p * a.hs + y) * a.ws + x;
-            if (a.img_vec == 1) {
-                *d = (y < a.hs && x < a.ws) ? *s : 0.f;
-            } else {
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (y < a.hs) {
-                    if (x + 3 < a.ws && (reinterpret_cast<uintptr_t>(s) & 15) == 0) {
-                        v = *reinterpret_cast<const float4*>(s);
-                    } else {
-                        if (x < a.ws) v.x = s[0];
-                        if (x + 1 < a.ws) v.y = s[1];
-                        if (x + 2 < a.ws) v.z = s[2];
-                        if (x + 3 < a.ws) v.w = s[3];
-                    }
-                }
-                *reinterpret_cast<float4*>(d) = v;
-            }
+        int p, y, x;
+        size_t j = i;
+        if (j < a.n_img) {                                // p = b * 3 + c
+            unit_at((unsigned)j, a.img_vec, a.Hc, a.Wc, p, y, x);
+            stage_unit(a.img, a.src_img + (size_t)p * a.hs * a.ws, a.hs, a.ws, a.Hc, a.Wc, a.img_vec, p, y, x, 0.f);
             continue;
         }
-        size_t j = i - a.n_img;
+        j -= a.n_img;
         if (j < a.n_mask) {
-            const unsigned u = (unsigned)j, ru = (unsigned)(a.Wc / a.mask_vec);
-            const int x = (int)(u % ru) * a.mask_vec; const unsigned t = u / ru;
-            const int y = (int)(t % (unsigned)a.Hc), b = (int)(t / (unsigned)a.Hc);
-            const uint8_t* s = a.src_mask + (size_t)b * a.hs * a.ws;
-            if (a.mask_vec == 1) stage_bytes<1>(a.mask, s, a.hs, a.ws, a.Hc, a.Wc, b, y, x, 1);
-            else stage_bytes<16>(a.mask, s, a.hs, a.ws, a.Hc, a.Wc, b, y, x, 1);
+            unit_at((unsigned)j, a.mask_vec, a.Hc, a.Wc, p, y, x);
+            stage_unit(a.mask, a.src_mask + (size_t)p * a.hs * a.ws, a.hs, a.ws, a.Hc, a.Wc, a.mask_vec, p, y, x, (uint8_t)1);
             continue;
         }
         j -= a.n_mask;
         if (j < a.n_tm) {
-            const unsigned u = (unsigned)j, ru = (unsigned)(a.Wc / a.tm_vec);
-            const int x = (int)(u % ru) * a.tm_vec; const unsigned t = u / ru;
-            const int y = (int)(t % (unsigned)a.Hc), b = (int)(t / (unsigned)a.Hc);
-            if (a.tm_vec == 1) stage_bytes<1>(a.tgt_masks, a.tm_ptr[b], a.tm_h[b], a.tm_w[b], a.Hc, a.Wc, b, y, x, 0);
-            else stage_bytes<16>(a.tgt_masks, a.tm_ptr[b], a.tm_h[b], a.tm_w[b], a.Hc, a.Wc, b, y, x, 0);
+            unit_at((unsigned)j, a.tm_vec, a.Hc, a.Wc, p, y, x);
+            stage_unit(a.tgt_masks, a.tm_ptr[p], a.tm_h[p], a.tm_w[p], a.Hc, a.Wc, a.tm_vec, p, y, x, (uint8_t)0);
             continue;
         }
         j -= a.n_tm;
@@ -180,7 +167,7 @@ extern "C" int rt_batch_stage(const float* src_img, const uint8_t* src_mask, int
     BatchStageArgs a{};
     for (int b = 0; b < B; ++b) {
         const int n = box_counts[b];
-        if (n < 0 || n > boxes_per_image || (n > 0 && !box_ptrs[b])) return RT_ERR_BADARG;
+        if (!rt_stage_boxes_ok(n, box_ptrs[b], boxes_per_image)) return RT_ERR_BADARG;
         a.box_ptr[b] = box_ptrs[b]; a.box_n[b] = n;
         if (tm_ptrs) {
             const int h = tm_hw[2 * b], w = tm_hw[2 * b + 1];
@@ -189,17 +176,15 @@ extern "C" int rt_batch_stage(const float* src_img, const uint8_t* src_mask, int
         }
     }
     const size_t plane = (size_t)Hc * Wc;
-    if ((size_t)B * 3 * plane >= ((size_t)1 << 32) || (size_t)B * boxes_per_image * 4 + B + 2 >= ((size_t)1 << 31)) return RT_ERR_UNSUPPORTED;
+    if ((size_t)B * 3 * plane >= ((size_t)1 << 32) || rt_box_tail_words(B, boxes_per_image) >= ((size_t)1 << 31)) return RT_ERR_UNSUPPORTED;
     a.src_img = src_img; a.src_mask = src_mask; a.img = img; a.mask = mask;
     a.boxes = boxes; a.tgt_off = tgt_off; a.num_boxes = num_boxes; a.tgt_masks = tgt_masks;
     a.B = B; a.hs = hs; a.ws = ws; a.Hc = Hc; a.Wc = Wc; a.box_rows = B * boxes_per_image;
-    a.img_vec = (Wc % 4 == 0 && (reinterpret_cast<uintptr_t>(img) & 15) == 0) ? 4 : 1;
-    a.mask_vec = (Wc % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0) ? 16 : 1;
-    a.tm_vec = (Wc % 16 == 0 && (reinterpret_cast<uintptr_t>(tgt_masks) & 15) == 0) ? 16 : 1;
+    a.img_vec = rt_stage_vec(Wc, img, 4); a.mask_vec = rt_stage_vec(Wc, mask, 16); a.tm_vec = rt_stage_vec(Wc, tgt_masks, 16);   // each on its own
     a.n_img = (unsigned)((size_t)B * 3 * plane / a.img_vec);
     a.n_mask = (unsigned)((size_t)B * plane / a.mask_vec);
     a.n_tm = tgt_masks ? (unsigned)((size_t)B * plane / a.tm_vec) : 0u;
-    a.n_box = (unsigned)(a.box_rows * 4 + B + 2);
+    a.n_box = (unsigned)rt_box_tail_words(B, boxes_per_image);
     const size_t total = (size_t)a.n_img + a.n_mask + a.n_tm + a.n_box;
     size_t blocks = (total + 255) / 256; if (blocks > 2048) blocks = 2048;       // 256 CUs x 8 workgroups, grid-stride beyond
     hipLaunchKernelGGL(batch_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);

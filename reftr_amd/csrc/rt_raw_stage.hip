@@ -3,11 +3,10 @@
 // rt_img_collate_norm(pad_to) -> DeviceInputPipeline._target -> rt_batch_stage (rt_input.hip, reftr_amd/data/device_input.py), so every
 // expression that rounds is written as it is there, and nothing in this file may be contracted into a fused multiply-add:
 #pragma clang fp contract(off)
-#include "rt_common.h"
+#include "rt_stage.h"
 
 namespace {
 
-constexpr int PRECISION_BITS = 32 - 8 - 2;
 constexpr int TH = RT_RAW_STAGE_TILE_H, TW = RT_RAW_STAGE_TILE_W;
 constexpr int KMAX = 2 * RT_RAW_STAGE_MAX_SCALE + 1;                 // taps per output index at the largest down-scale
 // Source rows under one tile: the first and last output rows' centres lie (TH - 1) * scale apart, each reaches `support` = scale to
@@ -22,11 +21,6 @@ static_assert(((TW + TH) * (KMAX + 2) * 4 + 3 * 256 * 4) % 16 == 0, "the dynamic
 static_assert(sizeof(rt_raw_stage_args) + 5 * 4 <= 4096, "the argument block of a launch");
 static_assert(TW % 16 == 0 && TH * (TW / 16) <= 256, "one 16-byte unit of a byte plane per thread");
 
-__device__ __forceinline__ uint8_t clip8(int v) {
-    v >>= PRECISION_BITS;
-    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // reftr_amd/data/resample.py taps(), output index xx: IEEE doubles, int() = truncation toward zero, the weights summed in order.
 // k[0 .. cap) receives the 22-bit coefficients, zero behind the count; the count is clamped to cap (only reachable beyond the scale the
 // entry points admit).
@@ -35,7 +29,7 @@ __device__ void resample_taps(int in_size, int out_size, int xx, int cap, int* l
     const double fscale = scale > 1.0 ? scale : 1.0;
     const double support = 1.0 * fscale;
     const double ss = 1.0 / fscale;
-    const double one = (double)(1 << PRECISION_BITS);
+    const double one = (double)(1 << RT_PRECISION_BITS);
     const double center = ((double)xx + 0.5) * scale;
     int xmin = (int)(center - support + 0.5);
     if (xmin < 0) xmin = 0;
@@ -74,7 +68,7 @@ __global__ __launch_bounds__(256) void resample_taps_kernel(int in_size, int out
 // (resample_taps), so the taps behind it re-read the last one and add nothing.  A loop over the count would wait for every load in turn.
 template <int NT>
 __device__ __forceinline__ int dot_taps(const uint8_t* s, int stride, const int* k, int last) {
-    int acc = 1 << (PRECISION_BITS - 1);
+    int acc = RT_RESAMPLE_HALF;
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc += (int)s[(j < last ? j : last) * stride] * k[j];
     return acc;
@@ -91,7 +85,7 @@ __device__ __forceinline__ void horizontal_pass(uint8_t* rows, const uint8_t* sr
 #pragma unroll
     for (int j = 0; j < NT; ++j) k[j] = h_k[xl * KMAX + j];
     const uint8_t* s = src + ((size_t)row_lo * w + h_lo[xl]) * 3 + xc % 3;
-    for (int r = 0; r < nrows; ++r, s += (size_t)w * 3) rows[r * ROW_BYTES + xc] = clip8(dot_taps<NT>(s, 3, k, last));
+    for (int r = 0; r < nrows; ++r, s += (size_t)w * 3) rows[r * ROW_BYTES + xc] = rt_clip8(dot_taps<NT>(s, 3, k, last));
 }
 
 // torch's `nearest` source index (upsample_nearest2d: fp32 scale, fp32 product)
@@ -110,6 +104,8 @@ __global__ __launch_bounds__(256) void raw_stage_kernel(const rt_raw_stage_args 
     const int tiles = tiles_x * tiles_y;
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     if (b >= a.B) {
+        // batch_stage_kernel's box tail (rt_input.hip) with the xyxy-pixels -> cxcywh-normalised value of a live word; why the two are
+        // not one function: DESIGN.md, rt_raw_stage
         const int nbox = a.B * a.boxes_per_image * 4;
         for (int k = tid; k < nbox + a.B + 2; k += 256) {
             if (k < nbox) {                               // boxes[B * boxes_per_image][4]: packed in image order, zero behind the last box
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(256) void raw_stage_kernel(const rt_raw_stage_args 
         const int yl = u / (TW / 16), xl = (u % (TW / 16)) * 16;
         const int y = y0 + yl, x = x0 + xl;
         if (y < Hc && x < Wc) {
-            union { uint4 q; uint8_t e[16]; } v;
+            rt_bytes16 v;
             if (plane == 0) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) v.e[j] = (y < oh && x + j < ow) ? 0 : 1;
@@ -162,13 +158,7 @@ __global__ __launch_bounds__(256) void raw_stage_kernel(const rt_raw_stage_args 
 #pragma unroll
                 for (int j = 0; j < 16; ++j) v.e[j] = (y < oh && x + j < ow) ? (s[row + nearest_src(x + j, sx, w)] != 0 ? 1 : 0) : 0;
             }
-            uint8_t* d = (plane == 0 ? a.mask : a.tgt_masks) + ((size_t)b * Hc + y) * Wc + x;
-            if (byte_vec == 16) {
-                *reinterpret_cast<uint4*>(d) = v.q;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 16; ++j) if (x + j < Wc) d[j] = v.e[j];
-            }
+            rt_store_unit((plane == 0 ? a.mask : a.tgt_masks) + ((size_t)b * Hc + y) * Wc + x, v, byte_vec == 16, x, Wc);
         }
     }
     int row_lo = 0;
@@ -177,7 +167,7 @@ __global__ __launch_bounds__(256) void raw_stage_kernel(const rt_raw_stage_args 
         const int cap = up ? 3 : KMAX;                    // the coefficients the passes read
         if (tid < nx) resample_taps(w, ow, x0 + tid, cap, &h_lo[tid], &h_n[tid], &h_k[tid * KMAX]);
         else if (tid >= TW && tid - TW < ny) resample_taps(h, oh, y0 + tid - TW, cap, &v_lo[tid - TW], &v_n[tid - TW], &v_k[(tid - TW) * KMAX]);
-        for (int i = tid; i < 3 * 256; i += 256) norm[i] = ((float)(i & 255) / 255.0f - a.mean[i >> 8]) / a.std[i >> 8];
+        for (int i = tid; i < 3 * 256; i += 256) norm[i] = rt_norm_u8((uint8_t)(i & 255), a.mean[i >> 8], a.std[i >> 8]);
         __syncthreads();
         // horizontal pass of the source rows [row_lo, row_lo + nrows) the tile's vertical taps read (first indices and ends both
         // grow with the output index), columns x0 .. x0 + nx, into LDS as bytes
@@ -207,11 +197,11 @@ __global__ __launch_bounds__(256) void raw_stage_kernel(const rt_raw_stage_args 
                 for (int e = 0; e < 4; ++e) {
                     if (xl + e < nx) {
                         const int acc = up ? dot_taps<3>(s + e * 3 + c, ROW_BYTES, k, last) : dot_taps<KMAX>(s + e * 3 + c, ROW_BYTES, k, last);
-                        v[e] = norm[c * 256 + clip8(acc)];
+                        v[e] = norm[c * 256 + rt_clip8(acc)];
                     }
                 }
             }
-            float* d = a.img + (((size_t)b * 3 + c) * Hc + y) * Wc + x;
+            float* d = a.img + (((size_t)b * 3 + c) * Hc + y) * Wc + x;       // (written out like the box tail: DESIGN.md)
             if (img_vec == 4) {
                 *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
             } else {
@@ -246,17 +236,17 @@ extern "C" int rt_raw_stage(const rt_raw_stage_args* a, rt_stream_t stream) {
     for (int b = 0; b < B; ++b) {
         const int n = a->box_n[b];
         if (!a->src[b] || a->h[b] <= 0 || a->w[b] <= 0 || a->oh[b] <= 0 || a->ow[b] <= 0 || a->oh[b] > Hc || a->ow[b] > Wc) return RT_ERR_BADARG;
-        if (n < 0 || n > a->boxes_per_image || (n > 0 && !a->box_ptr[b]) || (a->tgt_masks && !a->tm_ptr[b])) return RT_ERR_BADARG;
+        if (!rt_stage_boxes_ok(n, a->box_ptr[b], a->boxes_per_image) || (a->tgt_masks && !a->tm_ptr[b])) return RT_ERR_BADARG;
         too_steep = too_steep || (int64_t)a->h[b] > (int64_t)RT_RAW_STAGE_MAX_SCALE * a->oh[b]
                     || (int64_t)a->w[b] > (int64_t)RT_RAW_STAGE_MAX_SCALE * a->ow[b];
     }
     const int tiles_x = (Wc + TW - 1) / TW, tiles_y = (Hc + TH - 1) / TH;
     const size_t blocks = (size_t)B * tiles_x * tiles_y + 1;
     if (too_steep || (size_t)Hc * Wc >= ((size_t)1 << 31) || blocks >= ((size_t)1 << 31)
-        || (size_t)B * a->boxes_per_image * 4 + B + 2 >= ((size_t)1 << 31)) return RT_ERR_UNSUPPORTED;
-    const int img_vec = (Wc % 4 == 0 && (reinterpret_cast<uintptr_t>(a->img) & 15) == 0) ? 4 : 1;
-    const int byte_vec = (Wc % 16 == 0 && (reinterpret_cast<uintptr_t>(a->mask) & 15) == 0
-                          && (reinterpret_cast<uintptr_t>(a->tgt_masks) & 15) == 0) ? 16 : 1;
+        || rt_box_tail_words(B, a->boxes_per_image) >= ((size_t)1 << 31)) return RT_ERR_UNSUPPORTED;
+    const int img_vec = rt_stage_vec(Wc, a->img, 4);
+    // one width for the two byte planes (a thread's unit goes to either): 16 where both allow it
+    const int byte_vec = rt_stage_vec(Wc, a->mask, 16) == 16 ? rt_stage_vec(Wc, a->tgt_masks, 16) : 1;
     // rows under a tile (ROWS_MAX's bound at this image's scale, rounded up), for the steepest image of the batch
     int rows_cap = 1;
     for (int b = 0; b < B; ++b) {

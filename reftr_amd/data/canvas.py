@@ -239,22 +239,25 @@ class BatchCanvas:
                     out.samples[k].copy_(v, non_blocking=True)
         return out
 
+    @staticmethod
+    def _boxes(targets):
+        """The boxes of `targets` as the stage calls take them: fp32, contiguous."""
+        return [(t["boxes"] if t["boxes"].dtype == torch.float32 else t["boxes"].float()).contiguous() for t in targets]
+
+    def _masks(self, targets, raw):
+        """The target masks as one-byte contiguous tensors, None without masks.  What is not a byte already is converted as its form of
+        batch defines, and the two differ in meaning: a raw mask is resized with its image and DeviceInputPipeline._target thresholds it,
+        `.float() > 0.5`; the mask of a NestedTensor batch is only padded and keeps its values, `.to(torch.uint8)`."""
+        convert = (lambda m: m.float() > 0.5) if raw else (lambda m: m.to(torch.uint8))
+        return [(t["masks"] if t["masks"].element_size() == 1 else convert(t["masks"])).contiguous() for t in targets] if self.masks else None
+
     def _stage_raw(self, img, targets, out):
-        boxes = [t["boxes"] if t["boxes"].dtype == torch.float32 else t["boxes"].float() for t in targets]
-        masks = None
-        if self.masks:           # (DeviceInputPipeline._target thresholds what is not a byte already: `.float() > 0.5`)
-            masks = [(t["masks"] if t["masks"].element_size() == 1 else t["masks"].float() > 0.5).contiguous() for t in targets]
         H.raw_stage([im.contiguous() for im in img.images], img.out_sizes(), out.samples["img"].tensors, out.samples["img"].mask,
-                    [b.contiguous() for b in boxes], self.boxes_per_image, *out.targets_static, MEAN, STD, mask_list=masks,
+                    self._boxes(targets), self.boxes_per_image, *out.targets_static, MEAN, STD, mask_list=self._masks(targets, True),
                     tgt_masks=out.tgt_masks)
 
     def _stage_nested(self, img, targets, out):
         src = img.tensors if img.tensors.dtype == torch.float32 else img.tensors.float()
         src_mask = img.mask if img.mask.element_size() == 1 else img.mask.bool()
-        boxes = [t["boxes"] if t["boxes"].dtype == torch.float32 else t["boxes"].float() for t in targets]
-        masks = None
-        if self.masks:
-            masks = [t["masks"] if t["masks"].element_size() == 1 else t["masks"].to(torch.uint8) for t in targets]
-            masks = [m.contiguous() for m in masks]
-        H.batch_stage(src.contiguous(), src_mask.contiguous(), out.samples["img"].tensors, out.samples["img"].mask,
-                      [b.contiguous() for b in boxes], self.boxes_per_image, *out.targets_static, mask_list=masks, tgt_masks=out.tgt_masks)
+        H.batch_stage(src.contiguous(), src_mask.contiguous(), out.samples["img"].tensors, out.samples["img"].mask, self._boxes(targets),
+                      self.boxes_per_image, *out.targets_static, mask_list=self._masks(targets, False), tgt_masks=out.tgt_masks)

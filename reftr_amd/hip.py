@@ -1698,31 +1698,40 @@ def img_collate_norm(images, H, W, mean, std):
     return out, mask
 
 
+def _stage_dst(B, img, mask, boxes_per_image, boxes, tgt_off, num_boxes, mask_list, tgt_masks):
+    """The destination checks of a stage call (rt_batch_stage, rt_raw_stage): the canvas buffers of a batch of B -> (Hc, Wc)."""
+    _req(img, torch.float32, "img"); _req(boxes, torch.float32, "boxes"); _req(tgt_off, torch.int32, "tgt_off"); _req(num_boxes, torch.float32, "num_boxes")
+    Hc, Wc = img.shape[-2:]
+    assert img.is_contiguous() and mask.is_contiguous() and mask.element_size() == 1
+    assert tuple(img.shape) == (B, 3, Hc, Wc) and tuple(mask.shape) == (B, Hc, Wc)
+    assert boxes.numel() == B * boxes_per_image * 4 and tgt_off.numel() == B + 1 and num_boxes.numel() == 1
+    if mask_list is not None:
+        assert len(mask_list) == B and tgt_masks is not None and tgt_masks.numel() == B * Hc * Wc and tgt_masks.element_size() == 1
+        assert all(t.is_cuda and t.element_size() == 1 and t.is_contiguous() and t.numel() == t.shape[-2] * t.shape[-1] for t in mask_list)
+    return Hc, Wc
+
+
+def _stage_boxes(box_list, B, n):
+    """The box arguments of a stage call: ctypes arrays (pointers, counts) of length n >= B; an image without boxes passes NULL."""
+    assert len(box_list) == B
+    for t in box_list:
+        assert t.numel() == 0 or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4)
+    return (c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in box_list]), (c_int32 * n)(*[t.shape[0] for t in box_list])
+
+
 def batch_stage(src_img, src_mask, img, mask, box_list, boxes_per_image, boxes, tgt_off, num_boxes, mask_list=None, tgt_masks=None):
     """rt_batch_stage: one batch of any size into fixed canvas buffers, one launch, every destination byte rewritten.
     src_img fp32 [B,3,hs,ws] / src_mask bool|u8 [B,hs,ws] -> img fp32 [B,3,Hc,Wc] (zero padded) / mask [B,Hc,Wc] (1 = padding);
     box_list: B fp32 [n_b, 4] device tensors -> boxes [B*boxes_per_image, 4] packed, tgt_off int32 [B+1], num_boxes fp32 [1];
     mask_list (optional): B one-byte [1, h_b, w_b] device tensors -> tgt_masks u8 [B,1,Hc,Wc].  The pointers and sizes go by value in
     the kernel arguments: nothing is copied to the device and nothing synchronises."""
-    _req(src_img, torch.float32, "src_img"); _req(img, torch.float32, "img")
-    _req(boxes, torch.float32, "boxes"); _req(tgt_off, torch.int32, "tgt_off"); _req(num_boxes, torch.float32, "num_boxes")
+    _req(src_img, torch.float32, "src_img")
     B, _, hs, ws = src_img.shape
-    Hc, Wc = img.shape[-2:]
-    assert src_img.is_contiguous() and src_mask.is_contiguous() and src_mask.element_size() == 1
-    assert img.is_contiguous() and mask.is_contiguous() and mask.element_size() == 1
-    assert tuple(img.shape) == (B, 3, Hc, Wc) and tuple(mask.shape) == (B, Hc, Wc) and tuple(src_mask.shape) == (B, hs, ws)
-    assert len(box_list) == B and boxes.numel() == B * boxes_per_image * 4 and tgt_off.numel() == B + 1 and num_boxes.numel() == 1
-    for t in box_list:
-        assert t.numel() == 0 or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4)
-    bp = (c_void_p * B)(*[t.data_ptr() if t.numel() else None for t in box_list])
-    bn = (c_int32 * B)(*[t.shape[0] for t in box_list])
-    tp = thw = None
-    if mask_list is not None:
-        assert len(mask_list) == B and tgt_masks is not None and tgt_masks.numel() == B * Hc * Wc and tgt_masks.element_size() == 1
-        for t in mask_list:
-            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous() and t.numel() == t.shape[-2] * t.shape[-1]
-        tp = (c_void_p * B)(*[t.data_ptr() for t in mask_list])
-        thw = (c_int32 * (2 * B))(*[v for t in mask_list for v in t.shape[-2:]])
+    Hc, Wc = _stage_dst(B, img, mask, boxes_per_image, boxes, tgt_off, num_boxes, mask_list, tgt_masks)
+    assert src_img.is_contiguous() and src_mask.is_contiguous() and src_mask.element_size() == 1 and tuple(src_mask.shape) == (B, hs, ws)
+    bp, bn = _stage_boxes(box_list, B, B)
+    tp = (c_void_p * B)(*[t.data_ptr() for t in mask_list]) if mask_list is not None else None
+    thw = (c_int32 * (2 * B))(*[v for t in mask_list for v in t.shape[-2:]]) if mask_list is not None else None
     _call("rt_batch_stage", src_img, src_mask, B, hs, ws, img, mask, Hc, Wc, bp, bn, int(boxes_per_image), boxes, tgt_off, num_boxes, tp, thw,
           tgt_masks if mask_list is not None else None)
 
@@ -1735,34 +1744,22 @@ def raw_stage(images, out_sizes, img, mask, box_list, boxes_per_image, boxes, tg
     box_list: B fp32 [n_b, 4] xyxy pixels of the raw frame -> boxes [B*boxes_per_image, 4] cxcywh normalised and packed, tgt_off
     int32 [B+1], num_boxes fp32 [1]; mask_list (optional): B one-byte [1, h_b, w_b] raw masks -> tgt_masks u8 [B,1,Hc,Wc] (nearest).
     Every pointer and size goes by value in the kernel arguments: nothing is copied to the device and nothing synchronises."""
-    _req(img, torch.float32, "img"); _req(boxes, torch.float32, "boxes"); _req(tgt_off, torch.int32, "tgt_off")
-    _req(num_boxes, torch.float32, "num_boxes")
     B = len(images)
-    Hc, Wc = img.shape[-2:]
-    assert 0 < B <= BATCH_STAGE_MAX_B and len(out_sizes) == B and len(box_list) == B
-    assert img.is_contiguous() and mask.is_contiguous() and mask.element_size() == 1
-    assert tuple(img.shape) == (B, 3, Hc, Wc) and tuple(mask.shape) == (B, Hc, Wc)
-    assert boxes.numel() == B * boxes_per_image * 4 and tgt_off.numel() == B + 1 and num_boxes.numel() == 1
-    for t in images:
-        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3
-    for t in box_list:
-        assert t.numel() == 0 or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[-1] == 4)
-    if mask_list is not None:
-        assert len(mask_list) == B and tgt_masks is not None and tgt_masks.numel() == B * Hc * Wc and tgt_masks.element_size() == 1
-        for t, im in zip(mask_list, images):
-            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous() and tuple(t.shape[-2:]) == tuple(im.shape[:2])
-            assert t.numel() == im.shape[0] * im.shape[1]
+    assert 0 < B <= BATCH_STAGE_MAX_B and len(out_sizes) == B
+    Hc, Wc = _stage_dst(B, img, mask, boxes_per_image, boxes, tgt_off, num_boxes, mask_list, tgt_masks)
+    assert all(t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3 for t in images)
+    assert mask_list is None or all(tuple(t.shape[-2:]) == tuple(im.shape[:2]) for t, im in zip(mask_list, images))
     hs, ws = [t.shape[0] for t in images], [t.shape[1] for t in images]
     ohs, ows = [int(s[0]) for s in out_sizes], [int(s[1]) for s in out_sizes]
     n = BATCH_STAGE_MAX_B          # (ready-made ctypes arrays: _desc copies them as they are, a list it would convert element by element)
+    bp, bn = _stage_boxes(box_list, B, n)
     _call("rt_raw_stage", _desc(
         RawStageArgs, img=img, mask=mask, tgt_masks=tgt_masks if mask_list is not None else None, boxes=boxes, tgt_off=tgt_off,
         num_boxes=num_boxes, B=B, Hc=Hc, Wc=Wc, boxes_per_image=int(boxes_per_image), mean=(c_float * 3)(*mean), std=(c_float * 3)(*std),
-        src=(c_void_p * n)(*[t.data_ptr() for t in images]), box_ptr=(c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in box_list]),
+        src=(c_void_p * n)(*[t.data_ptr() for t in images]), box_ptr=bp, box_n=bn,
         tm_ptr=(c_void_p * n)(*[t.data_ptr() for t in mask_list]) if mask_list is not None else (c_void_p * n)(),
         h=(c_int32 * n)(*hs), w=(c_int32 * n)(*ws), oh=(c_int32 * n)(*ohs), ow=(c_int32 * n)(*ows),
-        box_n=(c_int32 * n)(*[t.shape[0] for t in box_list]), rw=(c_float * n)(*[float(o) / float(i) for o, i in zip(ows, ws)]),
-        rh=(c_float * n)(*[float(o) / float(i) for o, i in zip(ohs, hs)])))
+        rw=(c_float * n)(*[float(o) / float(i) for o, i in zip(ows, ws)]), rh=(c_float * n)(*[float(o) / float(i) for o, i in zip(ohs, hs)])))
 
 
 def resample_taps(in_size, out_size, ksize, device="cuda"):
