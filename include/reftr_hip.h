@@ -895,6 +895,56 @@ typedef struct rt_eval_canvas_args {
 int rt_eval_canvas(const rt_eval_canvas_args* a, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Prediction on the batch canvas: the RESULT tail of one canvas batch -- boxes in original pixels and, for RES, the mask at the
+ * original resolution (PostProcessSegm's masks_origin) -- with every per-batch fact in DEVICE memory, so that it sits inside a
+ * captured graph behind the forward and is replayed without an argument change.
+ * rt_predict_facts — one small launch per batch, outside the graph.  Per image b the HOST values img_h[b], img_w[b] (the resized
+ *   size, <= the canvas Hc x Wc) and orig_h[b], orig_w[b] (the original size) travel by value in the kernel's argument block, as
+ *   rt_raw_stage's do (B <= RT_BATCH_STAGE_MAX_B), with Q (mask queries per image; 0: a model without masks) and `capacity`, the
+ *   size of the mask buffer in bytes.  Image b's mask block is Q * orig_h * orig_w bytes and starts at a 16-byte unit:
+ *   off16[0] = 0, off16[b + 1] = off16[b] + ceil(Q * orig_h * orig_w / 16).  It writes
+ *   facts int32 [B, RT_PREDICT_FACTS_WORDS] = {img_h, img_w, orig_h, orig_w, off16[b], off16[b + 1], off16[B], 0}.
+ *   RT_ERR_UNSUPPORTED: B > RT_BATCH_STAGE_MAX_B, 16 * off16[B] >= 2^31.  RT_ERR_BADARG, nothing launched: a NULL pointer, B <= 0,
+ *   Q < 0, capacity < 0, a non-positive size, img_h > Hc, img_w > Wc, 16 * off16[B] > capacity.
+ * rt_predict_canvas — at most two launches, reading device memory only; no atomics, plain loads and stores, the same bits from run
+ *   to run:
+ *   (a) boxes, one wave per image: out_boxes fp32 [B, P, 4] = rt_box_postprocess's rows (the image's valid phrases in masked_select
+ *       order, prediction 0 of each, cxcywh -> xyxy) times {orig_w, orig_h, orig_w, orig_h} of `facts`, unused rows 0 -- the rows
+ *       rt_eval_canvas writes to its ring, by the same function; out_counts int32 [B] = valid phrases per image;
+ *   (b) masks (only when pred_masks fp32 [B, Q, h, w] is given): byte i < Q * oh * ow of image b's block (out_masks + 16 * off16[b])
+ *       is pixel (q, y, x) = (i / (oh * ow), (i / ow) % oh, i % ow) of the original frame: rt_mask_postprocess's masks_origin with the
+ *       canvas Hc x Wc as the frame, i.e. its decision function on logits[b][q] at the `nearest` sources of y in img_h and x in
+ *       img_w, as 0 / 1.  The bytes from Q * oh * ow to the end of the block's last 16-byte unit are written 0.  One thread per
+ *       16-byte unit, ONE 16-byte store each (out_masks must be 16-byte aligned, else RT_ERR_BADARG); the thread divides once per
+ *       unit and walks its sixteen pixels row by row.  Every byte of [0, 16 * off16[B]) is rewritten by every call (the buffer holds
+ *       the previous batch); no byte at or past 16 * off16[B], and none past `capacity`, is touched, whatever `facts` holds.  The
+ *       grid is fixed by `capacity`, not by the batch (facts change between replays): workgroups behind the total leave at once.
+ *   RT_ERR_BADARG: a NULL required pointer, a non-positive size, capacity < 0, out_masks not 16-byte aligned; RT_ERR_UNSUPPORTED:
+ *   B > RT_BATCH_STAGE_MAX_B, capacity >= 2^31, h * w or Hc * Wc >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+#define RT_PREDICT_FACTS_WORDS 8
+typedef struct rt_predict_facts_args {
+    int32_t* facts;                /* int32 [B, RT_PREDICT_FACTS_WORDS] */
+    int64_t  capacity;             /* bytes of the mask buffer */
+    int32_t  B, Q, Hc, Wc;
+    int32_t  img_h[RT_BATCH_STAGE_MAX_B], img_w[RT_BATCH_STAGE_MAX_B], orig_h[RT_BATCH_STAGE_MAX_B], orig_w[RT_BATCH_STAGE_MAX_B];
+} rt_predict_facts_args;
+int rt_predict_facts(const rt_predict_facts_args* a, rt_stream_t stream);
+typedef struct rt_predict_canvas_args {
+    const float*   pred_boxes;     /* fp32 [B, P, K, 4] cxcywh */
+    const uint8_t* valid;          /* uint8 [B, P, K] */
+    const int32_t* facts;          /* int32 [B, RT_PREDICT_FACTS_WORDS] */
+    const float*   pred_masks;     /* fp32 [B, Q, h, w] | NULL: the box part only */
+    float*   out_boxes;            /* fp32 [B, P, 4] */
+    int32_t* out_counts;           /* int32 [B] */
+    uint8_t* out_masks;            /* `capacity` bytes, 16-byte aligned (with pred_masks) */
+    int64_t  capacity;
+    int32_t  B, P, K, Q, h, w, Hc, Wc;
+    float    threshold;
+} rt_predict_canvas_args;
+int rt_predict_canvas(const rt_predict_canvas_args* a, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * rt_comm_* — the data-parallel gradient exchange: what the reference gets from
  * torch.nn.parallel.DistributedDataParallel (main_vg.py:290-296) after util/misc.py:392-431 set up one process per GPU.
  * RCCL over xGMI, bound at run time (dlopen: the copy the process already holds -- torch.distributed's -- or the system's);

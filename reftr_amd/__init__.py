@@ -5,7 +5,9 @@ Public surface mirrors the reference (ubc-vision/RefTR) Python protocol; see INT
     from reftr_amd.engine_vg import train_one_epoch, evaluate
     from reftr_amd.optim import build_optimizer
     from reftr_amd.parallel import DistributedDataParallel
+    from reftr_amd import Predictor                        # raw images + phrases -> boxes and original-size masks (predict.py)
 """
 __version__ = "0.1.0"
 
 from .models import build_reftr  # noqa: E402,F401
+from .predict import Predictor  # noqa: E402,F401

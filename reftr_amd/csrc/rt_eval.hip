@@ -182,13 +182,7 @@ __global__ __launch_bounds__(64) void eval_canvas_finish_kernel(const rt_eval_ca
         const int32_t* f = a.facts + (size_t)b * 6;
         const float oh = (float)f[2], ow = (float)f[3];
         float* rows = a.ring_boxes + ((size_t)slot * a.B + b) * a.P * 4;
-        int base = 0, rank;
-        for (int j0 = 0; j0 < a.P; j0 += 64) {
-            const int ph = j0 + lane;
-            if (rt_phrase_rank(valid_b, a.P, a.K, ph, lane, base, rank))
-                rt_eval_shared::select_scale_box(pred_b + ((size_t)ph * a.K) * 4, true, oh, ow, rows + (size_t)rank * 4);
-        }
-        for (int i = base * 4 + lane; i < a.P * 4; i += 64) rows[i] = 0.f;
+        const int base = rt_eval_shared::write_scaled_rows(pred_b, valid_b, a.P, a.K, oh, ow, rows, lane);
         if (lane == 0) {
             a.ring_counts[(size_t)slot * a.B + b] = base;
             a.ring_ids[(size_t)slot * a.B + b] = a.image_ids[b];

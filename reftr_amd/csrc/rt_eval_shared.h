@@ -49,6 +49,21 @@ __device__ __forceinline__ void select_scale_box(const float* __restrict__ s, bo
     o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1;
 }
 
+// One image's result rows by one whole wave (rt_box_postprocess's rows, scaled to the original size): the r-th VALID phrase of
+// pred_b [P, K, 4] / valid_b [P, K] (rt_phrase_rank: masked_select order) -> rows[r] = xyxy * {ow, oh, ow, oh}, the rows behind them
+// 0.  Returns the image's count of valid phrases.  What rt_eval_canvas writes to its ring and rt_predict_canvas to out_boxes.
+__device__ __forceinline__ int write_scaled_rows(const float* __restrict__ pred_b, const uint8_t* __restrict__ valid_b, int P, int K,
+                                                 float oh, float ow, float* __restrict__ rows, int lane) {
+    int base = 0, rank;
+    for (int j0 = 0; j0 < P; j0 += 64) {
+        const int ph = j0 + lane;
+        if (rt_phrase_rank(valid_b, P, K, ph, lane, base, rank))
+            select_scale_box(pred_b + ((size_t)ph * K) * 4, true, oh, ow, rows + (size_t)rank * 4);
+    }
+    for (int i = base * 4 + lane; i < P * 4; i += 64) rows[i] = 0.f;
+    return base;
+}
+
 // the image's scored rectangle: its size, never past the target's own extent or the frame (equal to the size for consistent input)
 __device__ __forceinline__ void scored_rect(int size_h, int size_w, int th, int tw, int max_h, int max_w, int& ih, int& iw) {
     ih = min(min(size_h, th), max_h);
@@ -78,3 +93,8 @@ __device__ __forceinline__ void store_block_iu(int I, int U, int* sm, int32_t* _
 // launch (a) of rt_eval_canvas, defined in rt_post.hip beside rt_mask_postprocess's kernel (see "Contraction" above); the caller has
 // checked the arguments.  Returns RT_OK or the launch's hipError.
 __attribute__((visibility("hidden"))) int rt_eval_canvas_launch_mask(const rt_eval_canvas_args& a, int nchunks, hipStream_t stream);
+
+// launch (b) of rt_predict_canvas (rt_predict.hip), defined in rt_post.hip for the same reason: `units` = capacity / 16, the 16-byte
+// units the grid covers.  The caller has checked the arguments.  Returns RT_OK or the launch's hipError.
+#define RT_PREDICT_UNITS_PER_WG 256
+__attribute__((visibility("hidden"))) int rt_predict_canvas_launch_mask(const rt_predict_canvas_args& a, int units, hipStream_t stream);

@@ -12,7 +12,8 @@
 //                        (x - 0.5*w, then * scale) so the boxes are bit-identical to its CPU result.
 // HBM-bound byte kernels: one thread per output pixel / box, coalesced 1-B stores along the row.
 // Also here: launch (a) of rt_eval_canvas (the mask partials of a canvas evaluation batch, taken from the logits), because it calls
-// mask_decision and must be compiled under this file's contraction setting -- see rt_eval_shared.h.
+// mask_decision and must be compiled under this file's contraction setting -- see rt_eval_shared.h -- and, for the same reason,
+// launch (b) of rt_predict_canvas (masks_origin of a canvas batch, packed in 16-byte units).
 #include "rt_eval_shared.h"
 
 namespace {
@@ -88,7 +89,61 @@ __global__ __launch_bounds__(256) void eval_canvas_mask_kernel(const rt_eval_can
     rt_eval_shared::store_block_iu(I, U, sm, a.partials + ((size_t)b * nchunks + c) * 2);
 }
 
+// launch (b) of rt_predict_canvas (the rest: rt_predict.hip): masks_origin of mask_postprocess_kernel with the canvas as the frame,
+// packed at rt_predict_facts' 16-byte block offsets.  One thread per 16-byte unit of the buffer: it finds its image among the blocks'
+// end offsets (LDS), divides ONCE to get (q, y, x) of its first byte, walks its sixteen pixels row by row (the row's source row is
+// looked up again only where the row changes) and issues ONE 16-byte store; bytes behind the image's Q * oh * ow are 0.  The written
+// range is [0, min(facts' total, units)): nothing at or behind the total, nothing past the capacity, whatever the facts hold -- and
+// every logit index is clamped by bilinear_axis, so that foreign facts cannot direct a read outside image b's Q planes either.
+__global__ __launch_bounds__(RT_PREDICT_UNITS_PER_WG) void predict_canvas_mask_kernel(const rt_predict_canvas_args a, int units) {
+    __shared__ int s_end[RT_BATCH_STAGE_MAX_B];
+    const int total = min(a.facts[6], units);
+    if ((int)(blockIdx.x * RT_PREDICT_UNITS_PER_WG) >= total) return;          // (the whole workgroup: the grid covers the capacity)
+    if ((int)threadIdx.x < a.B) s_end[threadIdx.x] = a.facts[threadIdx.x * RT_PREDICT_FACTS_WORDS + 5];
+    __syncthreads();
+    const int u = blockIdx.x * RT_PREDICT_UNITS_PER_WG + threadIdx.x;
+    if (u >= total) return;
+    int b = 0;
+    while (b < a.B - 1 && u >= s_end[b]) ++b;
+    const int32_t* f = a.facts + (size_t)b * RT_PREDICT_FACTS_WORDS;
+    const int ih = f[0], iw = f[1], oh = f[2], ow = f[3];
+    const long long first = ((long long)u - f[4]) * 16;                        // the unit's first byte within the image's block
+    long long n = oh > 0 && ow > 0 && first >= 0 ? (long long)a.Q * oh * ow : 0;
+    if (n > 0x7fffffffLL) n = 0;                                               // (not rt_predict_facts' table)
+    uint32_t word[4] = {0u, 0u, 0u, 0u};
+    if (first < n) {
+        const unsigned plane = (unsigned)oh * (unsigned)ow, i0 = (unsigned)first;
+        const unsigned q = i0 / plane, r = i0 - q * plane;
+        int y = (int)(r / (unsigned)ow), x = (int)(r - (unsigned)y * (unsigned)ow);
+        const float* lg = a.pred_masks + ((size_t)b * a.Q + q) * a.h * a.w;
+        const float sh = (float)a.h / (float)a.Hc, sw = (float)a.w / (float)a.Wc;
+        const int left = (int)min(n - first, 16ll);
+        int sy = nearest_src(y, ih, oh);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k < left) {
+                const int sx = nearest_src(x, iw, ow);
+                word[k >> 2] |= (mask_decision(lg, a.h, a.w, sy, sx, sh, sw, a.threshold) ? 1u : 0u) << ((k & 3) * 8);
+                if (++x == ow) {
+                    x = 0;
+                    if (++y == oh) { y = 0; lg += (size_t)a.h * a.w; }         // the next query's plane (never read behind the last)
+                    sy = nearest_src(y, ih, oh);
+                }
+            }
+        }
+    }
+    *reinterpret_cast<uint4*>(a.out_masks + (size_t)u * 16) = make_uint4(word[0], word[1], word[2], word[3]);
+}
+
 }  // namespace
+
+int rt_predict_canvas_launch_mask(const rt_predict_canvas_args& a, int units, hipStream_t stream) {
+    if (units <= 0) return RT_OK;
+    hipLaunchKernelGGL(predict_canvas_mask_kernel, dim3((unsigned)((units + RT_PREDICT_UNITS_PER_WG - 1) / RT_PREDICT_UNITS_PER_WG)),
+                       dim3(RT_PREDICT_UNITS_PER_WG), 0, stream, a, units);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
 
 int rt_eval_canvas_launch_mask(const rt_eval_canvas_args& a, int nchunks, hipStream_t stream) {
     hipLaunchKernelGGL(eval_canvas_mask_kernel, dim3((unsigned)nchunks, (unsigned)a.B), dim3(256), 0, stream, a, nchunks);

@@ -28,6 +28,7 @@ CONSTANTS = {
     # rt_eval_metrics: accumulator slots (8 bytes each: int64 but for the two double sums) and the mask kernel's pixels per workgroup
     "RT_EVAL_DET_N": 0, "RT_EVAL_DET_HIT": 1, "RT_EVAL_SEG_N": 6, "RT_EVAL_SEG_HIT": 7, "RT_EVAL_SEG_I": 12, "RT_EVAL_SEG_U": 13,
     "RT_EVAL_DET_SUM": 14, "RT_EVAL_SEG_SUM": 15, "RT_EVAL_SLOTS": 16, "RT_EVAL_CHUNK": 16384,
+    "RT_PREDICT_FACTS_WORDS": 8,         # int32 words per image of rt_predict_facts' table
     "RT_DEC_MAX_LAYERS": 8, "RT_DEC_HANDOFF_BYTES": 256 + 16 * 256 * 36 + 16 * 2048 * 4,
 }
 # ... and its public names: every key without the "RT_" (hip.ACT_RELU, hip.SQ_SLOTS, hip.EVAL_SLOTS, hip.DEC_MAX_LAYERS, ...)
@@ -254,6 +255,19 @@ class EvalCanvasArgs(_Abi, c="rt_eval_canvas_args"):
                 ("Wc", c_int32), ("tgt_rows", c_int32), ("slots", c_int32), ("threshold", c_float)]
 
 
+class PredictFactsArgs(_Abi, c="rt_predict_facts_args"):
+    _N = CONSTANTS["RT_BATCH_STAGE_MAX_B"]
+    _fields_ = [("facts", c_void_p), ("capacity", c_int64), ("B", c_int32), ("Q", c_int32), ("Hc", c_int32), ("Wc", c_int32),
+                ("img_h", c_int32 * _N), ("img_w", c_int32 * _N), ("orig_h", c_int32 * _N), ("orig_w", c_int32 * _N)]
+
+
+class PredictCanvasArgs(_Abi, c="rt_predict_canvas_args"):
+    _fields_ = [("pred_boxes", c_void_p), ("valid", c_void_p), ("facts", c_void_p), ("pred_masks", c_void_p), ("out_boxes", c_void_p),
+                ("out_counts", c_void_p), ("out_masks", c_void_p), ("capacity", c_int64),
+                ("B", c_int32), ("P", c_int32), ("K", c_int32), ("Q", c_int32), ("h", c_int32), ("w", c_int32), ("Hc", c_int32),
+                ("Wc", c_int32), ("threshold", c_float)]
+
+
 class RawStageArgs(_Abi, c="rt_raw_stage_args"):
     _N = CONSTANTS["RT_BATCH_STAGE_MAX_B"]
     _fields_ = [("img", c_void_p), ("mask", c_void_p), ("tgt_masks", c_void_p), ("boxes", c_void_p), ("tgt_off", c_void_p),
@@ -364,6 +378,8 @@ _SIGNATURES = {
     "rt_eval_facts": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_void_p,
                               c_void_p, c_void_p]),
     "rt_eval_canvas": (c_int, [POINTER(EvalCanvasArgs), c_void_p]),
+    "rt_predict_facts": (c_int, [POINTER(PredictFactsArgs), c_void_p]),
+    "rt_predict_canvas": (c_int, [POINTER(PredictCanvasArgs), c_void_p]),
     "rt_small_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rt_pos_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "rt_sqnorm": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
@@ -1325,6 +1341,64 @@ def eval_canvas(pred_boxes, valid_u8, tgt_boxes, tgt_off, facts, image_ids, stat
         veto=veto, B=B, P=P, K=K, Q=Q, h=h, w=w, Hc=Hc, Wc=Wc, tgt_rows=int(tgt_boxes.shape[0]), slots=state.slots,
         threshold=float(threshold)))
     return iou_det, iou_seg, iu
+
+
+def predict_layout(Q, origs):
+    """The mask blocks of a prediction batch (rt_predict_facts' rule, on the host): image b's Q * orig_h * orig_w bytes start at the
+    16-byte unit off16[b]; -> [off16[0] = 0, ..., off16[B]] as python ints.  16 * off16[B] is the batch's used bytes."""
+    off = [0]
+    for oh, ow in origs:
+        off.append(off[-1] + -(-(int(Q) * int(oh) * int(ow)) // 16))
+    return off
+
+
+class PredictState:
+    """What rt_predict_canvas writes, as ONE device block so that a batch's results leave in one copy: the header -- out_boxes fp32
+    [B, P, 4], then out_counts int32 [B], rounded up to 16 bytes -- and behind it the mask buffer of `capacity` bytes (a multiple of
+    16; 0 without masks).  `facts` int32 [B, PREDICT_FACTS_WORDS] is rt_predict_facts' table."""
+
+    def __init__(self, B, P, device, mask_capacity=0):
+        self.B, self.P = int(B), int(P)
+        self.capacity = -(-int(mask_capacity) // 16) * 16
+        nb = self.B * self.P * 16
+        self.header_bytes = -(-(nb + self.B * 4) // 16) * 16
+        self.block = torch.zeros(self.header_bytes + self.capacity, dtype=torch.uint8, device=device)
+        self.out_boxes = self.block[:nb].view(torch.float32).view(self.B, self.P, 4)
+        self.out_counts = self.block[nb:nb + self.B * 4].view(torch.int32)
+        self.masks = self.block[self.header_bytes:]
+        self.facts = torch.zeros((self.B, PREDICT_FACTS_WORDS), dtype=torch.int32, device=device)
+
+
+def predict_facts(sizes, origs, canvas_hw, facts, Q=0, capacity=0):
+    """rt_predict_facts: sizes / origs: B (h, w) pairs of python ints (resized, original), canvas_hw = (Hc, Wc), Q mask queries per
+    image (0: none), capacity: the mask buffer's bytes -> facts int32 [B, PREDICT_FACTS_WORDS] (predict_layout's offsets).  Every
+    value goes by value in the kernel arguments: nothing is copied to the device and nothing synchronises."""
+    B, n = len(sizes), BATCH_STAGE_MAX_B
+    _req(facts, torch.int32, "facts")
+    assert 0 < B <= n and len(origs) == B and facts.numel() == PREDICT_FACTS_WORDS * B and facts.is_contiguous()
+    _call("rt_predict_facts", _desc(
+        PredictFactsArgs, facts=facts, capacity=int(capacity), B=B, Q=int(Q), Hc=int(canvas_hw[0]), Wc=int(canvas_hw[1]),
+        img_h=(c_int32 * n)(*[int(s[0]) for s in sizes]), img_w=(c_int32 * n)(*[int(s[1]) for s in sizes]),
+        orig_h=(c_int32 * n)(*[int(s[0]) for s in origs]), orig_w=(c_int32 * n)(*[int(s[1]) for s in origs])))
+
+
+def predict_canvas(pred_boxes, valid_u8, state, pred_masks=None, canvas_hw=None, threshold=0.5):
+    """rt_predict_canvas for one canvas batch: pred_boxes fp32 [B, P, K, 4], valid uint8 [B, P, K], state a PredictState whose facts
+    predict_facts wrote -> state.out_boxes / out_counts and, with pred_masks fp32 [B, Q, h, w] and canvas_hw = (Hc, Wc), the packed
+    masks_origin blocks in state.masks.  At most two launches, device memory only: it can be captured and replayed."""
+    B, P, K, _ = pred_boxes.shape
+    _req(pred_boxes, torch.float32, "pred_boxes"); _req(valid_u8, torch.uint8, "valid"); _req(pred_masks, torch.float32, "pred_masks")
+    assert tuple(valid_u8.shape) == (B, P, K) and pred_boxes.is_contiguous() and valid_u8.is_contiguous()
+    assert state.B == B and state.P == P
+    Q = h = w = Hc = Wc = 0
+    if pred_masks is not None:
+        assert pred_masks.dim() == 4 and pred_masks.shape[0] == B and pred_masks.is_contiguous() and canvas_hw is not None
+        Q, h, w = (int(v) for v in pred_masks.shape[1:])
+        Hc, Wc = int(canvas_hw[0]), int(canvas_hw[1])
+    _call("rt_predict_canvas", _desc(
+        PredictCanvasArgs, pred_boxes=pred_boxes, valid=valid_u8, facts=state.facts, pred_masks=pred_masks, out_boxes=state.out_boxes,
+        out_counts=state.out_counts, out_masks=state.masks if pred_masks is not None else None, capacity=state.capacity,
+        B=B, P=P, K=K, Q=Q, h=h, w=w, Hc=Hc, Wc=Wc, threshold=float(threshold)))
 
 
 def zero_chunks(base, table, n):
