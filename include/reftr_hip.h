@@ -895,6 +895,73 @@ typedef struct rt_eval_canvas_args {
 int rt_eval_canvas(const rt_eval_canvas_args* a, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Evaluation of RAW batches on the batch canvas (engine_vg.evaluate_raw): rt_eval_canvas runs unchanged behind rt_raw_stage, and the
+ * predicted mask is scored a second time at the annotation's OWN resolution, against the raw target mask untouched.
+ * rt_eval_raw_facts — one small launch per batch, outside the graph; what rt_eval_facts gathers from device tensors, from HOST values
+ *   that travel by value in the kernel's argument block, as rt_predict_facts' do (B <= RT_BATCH_STAGE_MAX_B): per image b the resized
+ *   size img_h[b], img_w[b] (<= the canvas Hc x Wc), the raw size orig_h[b], orig_w[b], image_id[b] (read when has_ids != 0) and
+ *   tm_ptr[b], the device address of the raw target mask (one byte per pixel, [orig_h][orig_w]; read when mask_table is given).
+ *   It writes facts int32 [B, 6] = {img_h, img_w, orig_h, orig_w, img_h, img_w} -- rt_eval_facts' layout; the mask extent words equal
+ *   the resized size, the extent of what rt_raw_stage staged -- image_ids int64 [B] (-1 without ids) and, when given, mask_table
+ *   int64 [B] = the addresses.  max_pixels: the bound rt_eval_orig's grid was sized for.
+ *   RT_ERR_BADARG, nothing launched: a NULL required pointer, B <= 0, a non-positive size, img_h > Hc, img_w > Wc,
+ *   orig_h * orig_w > max_pixels, mask_table given with a NULL tm_ptr[b].  RT_ERR_UNSUPPORTED: B > RT_BATCH_STAGE_MAX_B,
+ *   max_pixels >= 2^31.
+ * rt_eval_orig — two launches behind rt_eval_canvas, reading device memory only; no atomics, the same bits from run to run:
+ *   (a) mask partials, grid (ceil(max_pixels / RT_EVAL_CHUNK), B) -- fixed by max_pixels, not by the batch (the facts change between
+ *       replays): a workgroup whose chunk starts at or behind the image's orig_h * orig_w leaves at once and writes nothing.  Pixel
+ *       i = y * orig_w + x of the raw frame: the prediction is rt_mask_postprocess's masks_origin with the canvas Hc x Wc as the frame
+ *       (rt_predict_canvas (b)): its decision function on query 0 of pred_masks fp32 [B, Q, h, w] at the `nearest` sources of y in
+ *       img_h and x in img_w; the target is byte i of the image's raw mask (mask_table[b]), non-zero = set, not resampled.  One
+ *       thread per 16 consecutive bytes: it divides once, walks its pixels row by row and reads the target with ONE 16-byte load
+ *       where the unit lies wholly inside orig_h * orig_w and its address is 16-byte aligned, byte loads otherwise; no byte at or
+ *       behind orig_h * orig_w is read.  Integer {I, U} of the workgroup's RT_EVAL_CHUNK pixels -> partials[b][chunk] (int32
+ *       [B, ceil(max_pixels / RT_EVAL_CHUNK), 2]).  Every logit index is clamped: foreign facts cannot direct a read outside image
+ *       b's plane.  An image that cannot be scored -- a zero table entry, a non-positive size, orig_h * orig_w > max_pixels --
+ *       contributes nothing;
+ *   (b) finish, ONE wave, image ascending: the first ceil(orig_h * orig_w / RT_EVAL_CHUNK) partials of the image added to int64 ->
+ *       iu int64 [B, 2] = {I_b, U_b}, iou_seg fp32 [B] = (float)I_b / (float)U_b (NaN when both are empty; an image that cannot be
+ *       scored: 0, {0, 0}, not counted), and `acc` = RT_EVAL_ORIG_SLOTS words of 8 bytes, int64 but for the double sum, counted as
+ *       rt_eval_metrics counts its mask samples (hits: fp32 IoU STRICTLY above the fp32 value nearest 0.5 .. 0.9; a NaN is a miss
+ *       and leaves the sum NaN).  acc is never reset here.  `veto` (optional): non-zero -> acc stays as it was (iou_seg and iu are
+ *       still written), as rt_eval_canvas.
+ *   RT_ERR_BADARG: a NULL required pointer, a non-positive size; RT_ERR_UNSUPPORTED: B > RT_BATCH_STAGE_MAX_B, max_pixels, h * w or
+ *   Hc * Wc >= 2^31.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rt_eval_raw_facts_args {
+    int32_t* facts;                /* int32 [B, 6] */
+    int64_t* image_ids;            /* int64 [B] */
+    int64_t* mask_table;           /* int64 [B] | NULL */
+    int64_t  max_pixels;
+    int32_t  B, Hc, Wc, has_ids;
+    int32_t  img_h[RT_BATCH_STAGE_MAX_B], img_w[RT_BATCH_STAGE_MAX_B], orig_h[RT_BATCH_STAGE_MAX_B], orig_w[RT_BATCH_STAGE_MAX_B];
+    int64_t  image_id[RT_BATCH_STAGE_MAX_B];
+    const uint8_t* tm_ptr[RT_BATCH_STAGE_MAX_B];
+} rt_eval_raw_facts_args;
+int rt_eval_raw_facts(const rt_eval_raw_facts_args* a, rt_stream_t stream);
+/* rt_eval_orig's accumulator slots (macros, not enumerators: the RT_EVAL_* enum above is rt_eval_metrics' 16 slots and nothing else) */
+#define RT_EVAL_ORIG_N 0
+#define RT_EVAL_ORIG_HIT 1         /* .. 5 */
+#define RT_EVAL_ORIG_I 6
+#define RT_EVAL_ORIG_U 7
+#define RT_EVAL_ORIG_SUM 8         /* double */
+#define RT_EVAL_ORIG_SLOTS 9
+typedef struct rt_eval_orig_args {
+    const float*   pred_masks;     /* fp32 [B, Q, h, w] */
+    const int32_t* facts;          /* int32 [B, 6] */
+    const int64_t* mask_table;     /* int64 [B] */
+    int32_t* partials;             /* int32 [B, ceil(max_pixels / RT_EVAL_CHUNK), 2] */
+    float*   iou_seg;              /* fp32 [B] */
+    int64_t* iu;                   /* int64 [B, 2] */
+    void*    acc;                  /* RT_EVAL_ORIG_SLOTS words of 8 bytes */
+    const int32_t* veto;           /* int32 [1] | NULL */
+    int64_t  max_pixels;
+    int32_t  B, Q, h, w, Hc, Wc;
+    float    threshold;
+} rt_eval_orig_args;
+int rt_eval_orig(const rt_eval_orig_args* a, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * Prediction on the batch canvas: the RESULT tail of one canvas batch -- boxes in original pixels and, for RES, the mask at the
  * original resolution (PostProcessSegm's masks_origin) -- with every per-batch fact in DEVICE memory, so that it sits inside a
  * captured graph behind the forward and is replayed without an argument change.

@@ -6,6 +6,8 @@
 //                       up per image, and the 16 running accumulators (counts int64, the two IoU sums double) updated in that order
 // rt_eval_canvas / rt_eval_facts (below): the same finish with every per-batch fact in device memory, for a captured evaluation step
 // on a batch canvas; its mask launch lives in rt_post.hip (rt_eval_shared.h says why).
+// rt_eval_raw_facts / rt_eval_orig (below): the facts of a RAW batch from host values in the argument block, and the mask scored once
+// more on the raw frame against the raw annotation -- the mask launch in rt_post.hip again, the finish here with finish_mask.
 // No floating-point atomics and nothing to clear beforehand: the same bits from run to run.  Latency-bound (0.4 MB per 640 x 640
 // image, a few hundred box rows): byte loads, one thread per pixel, and a serial walk over the rows for the ordered double sums.
 #include "rt_eval_shared.h"
@@ -213,7 +215,72 @@ __global__ __launch_bounds__(RT_BATCH_STAGE_MAX_B) void eval_facts_kernel(const 
     a.image_ids[b] = a.id_ptr[b] ? a.id_ptr[b][0] : -1;
 }
 
+// rt_eval_raw_facts: thread b writes image b's rows from the values in the argument block (2.1 KB of the 4 KB a launch carries)
+static_assert(sizeof(rt_eval_raw_facts_args) <= 4096, "the argument block of a launch");
+
+__global__ __launch_bounds__(RT_BATCH_STAGE_MAX_B) void eval_raw_facts_kernel(const rt_eval_raw_facts_args a) {
+    const int b = threadIdx.x;
+    if (b >= a.B) return;
+    int32_t* f = a.facts + (size_t)b * 6;
+    f[0] = a.img_h[b]; f[1] = a.img_w[b]; f[2] = a.orig_h[b]; f[3] = a.orig_w[b];
+    f[4] = a.img_h[b]; f[5] = a.img_w[b];                                    // the extent of what rt_raw_stage staged
+    a.image_ids[b] = a.has_ids ? a.image_id[b] : -1;
+    if (a.mask_table) a.mask_table[b] = (int64_t)reinterpret_cast<uintptr_t>(a.tm_ptr[b]);
+}
+
+// launch (b) of rt_eval_orig: finish_mask over the images in ascending order, each with the partials ITS pixels filled (what the mask
+// launch in rt_post.hip wrote: both ask rt_eval_shared::orig_pixels), counted into the RT_EVAL_ORIG_* slots.
+__global__ __launch_bounds__(64) void eval_orig_finish_kernel(const rt_eval_orig_args a, int nchunks) {
+    const int lane = threadIdx.x;
+    const bool keep = !a.veto || a.veto[0] == 0;                             // a vetoed batch leaves the totals alone
+    long long* acc_i = reinterpret_cast<long long*>(a.acc);
+    double* acc_d = reinterpret_cast<double*>(a.acc);
+    totals t;                                                                // (its seg_* fields hold the original-frame totals here)
+    if (lane == 0) {
+        t.seg_n = acc_i[RT_EVAL_ORIG_N]; t.seg_i = acc_i[RT_EVAL_ORIG_I]; t.seg_u = acc_i[RT_EVAL_ORIG_U];
+        for (int k = 0; k < 5; ++k) t.seg_hit[k] = acc_i[RT_EVAL_ORIG_HIT + k];
+        t.seg_sum = acc_d[RT_EVAL_ORIG_SUM];
+    }
+    for (int b = 0; b < a.B; ++b) {
+        const long long n = rt_eval_shared::orig_pixels(a.facts + (size_t)b * 6, a.mask_table[b], a.max_pixels);
+        const int mine = (int)((n + RT_EVAL_CHUNK - 1) / RT_EVAL_CHUNK);
+        finish_mask(a.partials + (size_t)b * nchunks * 2, mine, n > 0, lane, a.iou_seg + b, a.iu + b * 2, t);
+    }
+    if (lane == 0 && keep) {
+        acc_i[RT_EVAL_ORIG_N] = t.seg_n; acc_i[RT_EVAL_ORIG_I] = t.seg_i; acc_i[RT_EVAL_ORIG_U] = t.seg_u;
+        for (int k = 0; k < 5; ++k) acc_i[RT_EVAL_ORIG_HIT + k] = t.seg_hit[k];
+        acc_d[RT_EVAL_ORIG_SUM] = t.seg_sum;
+    }
+}
+
 }  // namespace
+
+extern "C" int rt_eval_raw_facts(const rt_eval_raw_facts_args* a, rt_stream_t stream) {
+    if (!a || !a->facts || !a->image_ids || a->B <= 0 || a->Hc <= 0 || a->Wc <= 0) return RT_ERR_BADARG;
+    if (a->B > RT_BATCH_STAGE_MAX_B || a->max_pixels >= 0x80000000LL) return RT_ERR_UNSUPPORTED;
+    for (int b = 0; b < a->B; ++b) {
+        if (a->img_h[b] <= 0 || a->img_w[b] <= 0 || a->orig_h[b] <= 0 || a->orig_w[b] <= 0) return RT_ERR_BADARG;
+        if (a->img_h[b] > a->Hc || a->img_w[b] > a->Wc) return RT_ERR_BADARG;
+        if ((long long)a->orig_h[b] * a->orig_w[b] > a->max_pixels) return RT_ERR_BADARG;
+        if (a->mask_table && !a->tm_ptr[b]) return RT_ERR_BADARG;
+    }
+    hipLaunchKernelGGL(eval_raw_facts_kernel, dim3(1), dim3(RT_BATCH_STAGE_MAX_B), 0, (hipStream_t)stream, *a);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
+
+extern "C" int rt_eval_orig(const rt_eval_orig_args* a, rt_stream_t stream) {
+    if (!a || !a->pred_masks || !a->facts || !a->mask_table || !a->partials || !a->iou_seg || !a->iu || !a->acc) return RT_ERR_BADARG;
+    if (a->B <= 0 || a->Q <= 0 || a->h <= 0 || a->w <= 0 || a->Hc <= 0 || a->Wc <= 0 || a->max_pixels <= 0) return RT_ERR_BADARG;
+    if (a->B > RT_BATCH_STAGE_MAX_B || a->max_pixels >= 0x80000000LL) return RT_ERR_UNSUPPORTED;
+    if ((long long)a->h * a->w >= 0x80000000LL || (long long)a->Hc * a->Wc >= 0x80000000LL) return RT_ERR_UNSUPPORTED;
+    const int nchunks = (int)((a->max_pixels + RT_EVAL_CHUNK - 1) / RT_EVAL_CHUNK);
+    const int rc = rt_eval_orig_launch_mask(*a, nchunks, (hipStream_t)stream);
+    if (rc != RT_OK) return rc;
+    hipLaunchKernelGGL(eval_orig_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a, nchunks);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
 
 extern "C" int rt_eval_metrics(const rt_eval_metrics_args* a, rt_stream_t stream) {
     if (!a || !a->pred_boxes || !a->valid || !a->table || !a->iou_det || !a->acc) return RT_ERR_BADARG;

@@ -5,8 +5,9 @@
 // header: what they compile to follows the INCLUDING file's contraction setting.  rt_post.hip compiles under the compiler's default
 // (a product feeding a sum may become one fused operation), rt_eval.hip under `#pragma clang fp contract(off)`.
 //   * mask_decision / bilinear_axis are contraction-sensitive (a borderline pixel flips with one fused multiply-add), so EVERY kernel
-//     that takes a mask decision is compiled in rt_post.hip: rt_mask_postprocess's and rt_eval_canvas's mask kernel sit side by side
-//     there and rt_eval.hip reaches the latter through rt_eval_canvas_launch_mask below.  rt_eval.hip must not call mask_decision.
+//     that takes a mask decision is compiled in rt_post.hip: rt_mask_postprocess's, rt_eval_canvas's, rt_predict_canvas's and
+//     rt_eval_orig's mask kernels sit side by side there and rt_eval.hip reaches its two through rt_eval_canvas_launch_mask and
+//     rt_eval_orig_launch_mask below.  rt_eval.hip must not call mask_decision.
 //   * select_scale_box is not: its only product that feeds a sum is 0.5f * w, which is exact, so the fused and the un-fused forms
 //     round the same value once.  It is used from both files.
 #pragma once
@@ -70,6 +71,15 @@ __device__ __forceinline__ void scored_rect(int size_h, int size_w, int th, int 
     iw = min(min(size_w, tw), max_w);
 }
 
+// rt_eval_orig: the pixels of image b's raw frame that are scored -- orig_h * orig_w of its facts row f, or 0 where the image cannot be
+// scored (a zero table entry, a non-positive size, more pixels than the grid was sized for).  Both launches decide by this one function:
+// the finish adds exactly the partials the mask kernel wrote.
+__device__ __forceinline__ long long orig_pixels(const int32_t* __restrict__ f, int64_t entry, int64_t max_pixels) {
+    if (entry == 0 || f[0] <= 0 || f[1] <= 0 || f[2] <= 0 || f[3] <= 0) return 0;
+    const long long n = (long long)f[2] * f[3];
+    return n <= max_pixels ? n : 0;
+}
+
 __device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -98,3 +108,7 @@ __attribute__((visibility("hidden"))) int rt_eval_canvas_launch_mask(const rt_ev
 // units the grid covers.  The caller has checked the arguments.  Returns RT_OK or the launch's hipError.
 #define RT_PREDICT_UNITS_PER_WG 256
 __attribute__((visibility("hidden"))) int rt_predict_canvas_launch_mask(const rt_predict_canvas_args& a, int units, hipStream_t stream);
+
+// launch (a) of rt_eval_orig (the rest: rt_eval.hip), defined in rt_post.hip for the same reason; the caller has checked the arguments.
+// Returns RT_OK or the launch's hipError.
+__attribute__((visibility("hidden"))) int rt_eval_orig_launch_mask(const rt_eval_orig_args& a, int nchunks, hipStream_t stream);

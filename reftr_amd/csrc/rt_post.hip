@@ -13,7 +13,8 @@
 // HBM-bound byte kernels: one thread per output pixel / box, coalesced 1-B stores along the row.
 // Also here: launch (a) of rt_eval_canvas (the mask partials of a canvas evaluation batch, taken from the logits), because it calls
 // mask_decision and must be compiled under this file's contraction setting -- see rt_eval_shared.h -- and, for the same reason,
-// launch (b) of rt_predict_canvas (masks_origin of a canvas batch, packed in 16-byte units).
+// launch (b) of rt_predict_canvas (masks_origin of a canvas batch, packed in 16-byte units) and launch (a) of rt_eval_orig (the same
+// decisions counted against the raw target mask).
 #include "rt_eval_shared.h"
 
 namespace {
@@ -135,7 +136,61 @@ __global__ __launch_bounds__(RT_PREDICT_UNITS_PER_WG) void predict_canvas_mask_k
     *reinterpret_cast<uint4*>(a.out_masks + (size_t)u * 16) = make_uint4(word[0], word[1], word[2], word[3]);
 }
 
+// launch (a) of rt_eval_orig (the rest: rt_eval.hip): integer {I, U} of query 0's masks_origin decisions -- predict_canvas_mask_kernel's,
+// frame = canvas -- against the image's RAW target mask, read where it lies, over one run of RT_EVAL_CHUNK pixels of the raw frame.
+// The grid covers max_pixels: a workgroup whose chunk starts at or behind the image's pixels leaves at once and writes nothing.
+// A thread takes 16-byte units of the flat raw mask (unit = thread, thread + 256, ...: the workgroup's loads stay contiguous): it
+// divides ONCE per unit to get (y, x) of its first byte, walks its sixteen pixels row by row (the row's source row is looked up again
+// only where the row changes) and reads the sixteen target bytes with ONE 16-byte load where the unit lies wholly inside the image and
+// its address is 16-byte aligned, with byte loads otherwise (the image's last, partial unit; a mask base that is not aligned).  No
+// byte at or behind orig_h * orig_w is read, and every logit index is clamped by bilinear_axis, whatever the facts hold.
+__global__ __launch_bounds__(256) void eval_orig_mask_kernel(const rt_eval_orig_args a, int nchunks) {
+    __shared__ int sm[8];
+    const int b = blockIdx.y, c = blockIdx.x;
+    const int32_t* f = a.facts + (size_t)b * 6;
+    const int64_t entry = a.mask_table[b];
+    const long long n = rt_eval_shared::orig_pixels(f, entry, a.max_pixels), start = (long long)c * RT_EVAL_CHUNK;
+    if (start >= n) return;                                                    // (the whole workgroup)
+    const int ih = f[0], iw = f[1], oh = f[2], ow = f[3];
+    const uint8_t* tg = reinterpret_cast<const uint8_t*>(entry);
+    const float* lg = a.pred_masks + (size_t)b * a.Q * a.h * a.w;              // query 0
+    const float sh = (float)a.h / (float)a.Hc, sw = (float)a.w / (float)a.Wc;
+    const long long end = min(n, start + RT_EVAL_CHUNK);
+    int I = 0, U = 0;
+    for (long long first = start + (long long)threadIdx.x * 16; first < end; first += 256 * 16) {
+        const int left = (int)min(end - first, 16ll);
+        const uint8_t* p = tg + first;
+        uint32_t word[4] = {0u, 0u, 0u, 0u};
+        if (left == 16 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+            const uint4 v = *reinterpret_cast<const uint4*>(p);
+            word[0] = v.x; word[1] = v.y; word[2] = v.z; word[3] = v.w;
+        } else {
+            for (int k = 0; k < left; ++k) word[k >> 2] |= (uint32_t)p[k] << ((k & 3) * 8);
+        }
+        const unsigned i0 = (unsigned)first;                                   // (n <= max_pixels < 2^31)
+        int y = (int)(i0 / (unsigned)ow), x = (int)(i0 - (unsigned)y * (unsigned)ow);
+        int sy = nearest_src(y, ih, oh);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (k < left) {
+                const int sx = nearest_src(x, iw, ow);
+                const int pr = mask_decision(lg, a.h, a.w, sy, sx, sh, sw, a.threshold) ? 1 : 0;
+                const int t = ((word[k >> 2] >> ((k & 3) * 8)) & 0xffu) != 0u;
+                I += pr & t; U += pr | t;
+                if (++x == ow) { x = 0; ++y; sy = nearest_src(y, ih, oh); }
+            }
+        }
+    }
+    rt_eval_shared::store_block_iu(I, U, sm, a.partials + ((size_t)b * nchunks + c) * 2);
+}
+
 }  // namespace
+
+int rt_eval_orig_launch_mask(const rt_eval_orig_args& a, int nchunks, hipStream_t stream) {
+    hipLaunchKernelGGL(eval_orig_mask_kernel, dim3((unsigned)nchunks, (unsigned)a.B), dim3(256), 0, stream, a, nchunks);
+    RT_CHECK_LAUNCH();
+    return RT_OK;
+}
 
 int rt_predict_canvas_launch_mask(const rt_predict_canvas_args& a, int units, hipStream_t stream) {
     if (units <= 0) return RT_OK;

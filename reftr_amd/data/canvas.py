@@ -167,6 +167,53 @@ class BatchCanvas:
                     return "no one-byte [1, h, w] target mask"
         return None
 
+    def why_not_eval_raw(self, samples, targets, segm=False):
+        """What engine_vg.evaluate_raw asks of a RAW batch on top of why_not: None, or the reason as a short phrase.  `size` and
+        `orig_size` are not asked of the targets -- they are RawImages.out_sizes() and the raw images' own (h, w), host values that reach
+        the device by value (rt_eval_raw_facts).  `image_id` (one int64) is on all targets or on none; with a 'segm' post-processor the
+        canvas has masks=True and every target a one-byte [1, h, w] mask of its image's size: rt_eval_orig reads it where it lies.
+        Shapes, dtypes and key presence only: nothing is read from the device."""
+        img = samples.get("img")
+        if segm and not self.masks:
+            return "a 'segm' post-processor needs a masks=True canvas"
+        with_id = sum(1 for t in targets if "image_id" in t)
+        if with_id not in (0, len(targets)):
+            return "image_id on some targets only"
+        for im, t in zip(img.images, targets):
+            v = t.get("image_id")
+            if with_id and not (torch.is_tensor(v) and v.dtype == torch.int64 and v.numel() == 1):
+                return "an image_id that is not one int64"
+            if segm:
+                m = t.get("masks")
+                if m is None or m.dim() != 3 or m.shape[0] != 1 or m.element_size() != 1:
+                    return "no one-byte [1, h, w] target mask"
+                if tuple(m.shape[-2:]) != tuple(im.shape[:2]):
+                    return f"target mask {m.shape[-2]} x {m.shape[-1]} on a raw image {im.shape[0]} x {im.shape[1]}"
+        return None
+
+    def raw_targets(self, samples, targets):
+        """The plain-torch restatement of what evaluate_raw knows about a raw batch without reading its targets: `targets` with `size`
+        (RawImages.out_sizes()) and `orig_size` (the raw (h, w)) added as int64 pairs on the images' device -- what a loader of the
+        NestedTensor form would have collated.  `image_id` stays as it is."""
+        img = samples["img"]
+        out = []
+        for im, (oh, ow), t in zip(img.images, img.out_sizes(), targets):
+            t = dict(t)
+            t["size"] = torch.tensor([oh, ow], dtype=torch.int64, device=im.device)
+            t["orig_size"] = torch.tensor([int(im.shape[0]), int(im.shape[1])], dtype=torch.int64, device=im.device)
+            out.append(t)
+        return out
+
+    def resized_eval(self, samples, targets):
+        """What a raw evaluation batch MEANS for the existing keys, in plain torch: `resized` (the DeviceInputPipeline chain) with
+        `size`, `orig_size` and `image_id` added as tensors -- the batch evaluate(canvas=) takes."""
+        s, t = self.resized(samples, targets)
+        for new, facts in zip(t, self.raw_targets(samples, targets)):
+            new["size"], new["orig_size"] = facts["size"], facts["orig_size"]
+            if "image_id" in facts:
+                new["image_id"] = facts["image_id"]
+        return s, t
+
     # ------------------------------------------------------------------ the definition, in plain torch
     def resized(self, samples, targets, to_canvas=False):
         """A raw batch through the existing device chain (DeviceInputPipeline: rt_resample_u8 per pass and image, rt_img_collate_norm,

@@ -1305,13 +1305,19 @@ class CapturedEvalStep:
     per-image facts and the graph; the accumulators and the ring (`state`, a hip.EvalCanvasState) are handed in and outlive it.
     Per batch the host issues rt_batch_stage, rt_eval_facts and the grouped token copy and replays; nothing is copied back.
 
+    The RAW form (the capture was built from a raw batch, reftr_amd.data.raw): the stage is rt_raw_stage, the facts come from host
+    values by value (rt_eval_raw_facts: the resized sizes are RawImages.out_sizes(), the original sizes the raw images' own; `host_ids`:
+    the image ids as python ints, None: gathered on the device from the targets' tensors) and, with a 'segm' post-processor, the tail
+    ends with rt_eval_orig -- the mask scored once more on the raw frame against the raw annotation, into `acc_orig`.  The graph reads
+    the raw masks through a table of their addresses: the step holds the batch's mask tensors until its next call.
+
     The cooperative decoder's fail-safe: the graph's metric launch takes the decoder's failure word as its veto, so the device tests
     the flag BEFORE the batch's results are kept -- a batch whose hand-off timed out leaves totals, ring and cursor untouched; the
     host reads the word as on every path (one 4-byte read per batch, only while cooperative launches are in use: _CanvasEval)."""
 
-    def __init__(self, model, criterion, postprocessors, canvas, samples, targets, acc, slots, state=None):
+    def __init__(self, model, criterion, postprocessors, canvas, samples, targets, acc, slots, state=None, acc_orig=None, host_ids=None):
         self.model, self.criterion, self.canvas, self.inner = model, criterion, canvas, _inner(model)
-        self.segm = postprocessors.get("segm")
+        self.segm, self.raw = postprocessors.get("segm"), _is_raw(samples)
         if canvas.tokens is None:
             canvas.bind(samples)
         self.key = canvas.key(samples)
@@ -1320,7 +1326,11 @@ class CapturedEvalStep:
         B, dev = len(targets), self.s["img"].tensors.device
         self.facts = torch.zeros((B, 6), dtype=torch.int32, device=dev)
         self.image_ids = torch.zeros(B, dtype=torch.int64, device=dev)
-        self._gather_facts(targets)
+        # the raw form scores masks on the original frame too; every raw batch that fits the canvas has at most this many pixels
+        self.max_pixels = H.RAW_STAGE_MAX_SCALE ** 2 * canvas.height * canvas.width
+        self.orig = H.EvalOrigState(B, self.max_pixels, dev, acc=acc_orig) if self.raw and self.segm is not None else None
+        self._keep = None
+        self._gather_facts(samples, targets, host_ids)
         self.losses = _ForwardLosses(model, criterion)       # held with the graph: the replay reads the weight vector it keeps
         self._gen = _state(model).coop_generation    # a cooperative fall-back anywhere drops this capture: it contains the launches
         with self._building():
@@ -1347,11 +1357,24 @@ class CapturedEvalStep:
         finally:
             crit.targets_static = crit.target_masks_static = None
 
-    def _gather_facts(self, targets):
+    def _gather_facts(self, samples, targets, host_ids=None):
+        if self.raw:
+            return self._raw_facts(samples["img"], targets, host_ids)
         origs = [t["orig_size"] for t in targets] if "orig_size" in targets[0] else None
         ids = [t["image_id"] for t in targets] if "image_id" in targets[0] else None
         hw = [tuple(t["masks"].shape[-2:]) for t in targets] if self.segm is not None else None
         H.eval_facts([t["size"] for t in targets], self.facts, self.image_ids, origs=origs, ids=ids, mask_hw=hw)
+
+    def _raw_facts(self, img, targets, host_ids):
+        origs = [(int(im.shape[0]), int(im.shape[1])) for im in img.images]
+        with_ids = "image_id" in targets[0]
+        masks = self.canvas._masks(targets, True) if self.orig is not None else None
+        H.eval_raw_facts(img.out_sizes(), origs, (self.canvas.height, self.canvas.width), self.facts, self.image_ids,
+                         ids=host_ids if with_ids else None, mask_list=masks,
+                         mask_table=self.orig.mask_table if masks is not None else None, max_pixels=self.max_pixels)
+        if with_ids and host_ids is None:                    # ids that are on the device already are gathered there
+            torch.stack([t["image_id"].reshape(()) for t in targets], out=self.image_ids)
+        self._keep = masks                                   # the graph reads them through the table: alive until the next call
 
     def _tail(self, outputs):
         boxes = outputs["pred_boxes"]
@@ -1361,17 +1384,21 @@ class CapturedEvalStep:
             pm = outputs["pred_masks"]
             pm = (pm.squeeze(2) if pm.dim() == 5 else pm).to(torch.float32).contiguous()
         st = self.staged
-        return H.eval_canvas(boxes.to(torch.float32).contiguous(), outputs["phrase_mask"].reshape(B, P, K).to(torch.uint8).contiguous(),
+        last = H.eval_canvas(boxes.to(torch.float32).contiguous(), outputs["phrase_mask"].reshape(B, P, K).to(torch.uint8).contiguous(),
                              st.targets_static[0], st.targets_static[1], self.facts, self.image_ids, self.state, pred_masks=pm,
                              tgt_masks=st.tgt_masks if pm is not None else None,
                              threshold=self.segm.threshold if self.segm is not None else 0.5, veto=self.fail_word)
+        if self.orig is not None:
+            H.eval_orig(pm, self.facts, self.orig, (self.canvas.height, self.canvas.width), threshold=self.segm.threshold,
+                        veto=self.fail_word)
+        return last
 
     @torch.no_grad()
-    def __call__(self, samples, targets):
+    def __call__(self, samples, targets, host_ids=None):
         """Stages the batch, replays, and returns the loss meters' (names, device vector) -- a static buffer the next replay rewrites."""
         _before_forward_replay(self.inner)
         self.canvas.stage(samples, targets, out=self.staged, tokens=False)
-        self._gather_facts(targets)
+        self._gather_facts(samples, targets, host_ids)
         _copy_batch(self.s, [], {k: v for k, v in samples.items() if k != "img"}, [])
         self.graph.replay()
         return self.names, self.vec
@@ -1383,7 +1410,8 @@ class _EvalPlan:
     replayed: the forward from a hipGraph per input shape; metered: scored on the device; on_canvas: through `canvas` -- refused before
     anything is launched where that cannot be done, ignored (said once) where the loop it would replace is off or not this package's."""
 
-    def __init__(self, model, criterion, postprocessors, device, visualize, canvas):
+    def __init__(self, model, criterion, postprocessors, device, visualize, canvas, raw=False):
+        """raw (evaluate_raw): a raw batch has nowhere else to go, so what would make `canvas` be ignored is refused instead."""
         from .models.post_process import PostProcessSegm, PostProcessVGMultiPhrase
         graph, metrics = (os.environ.get(k, "1") == "1" for k in ("REFTR_EVAL_GRAPH", "REFTR_EVAL_METRICS"))
         cuda = torch.device(device).type == "cuda"
@@ -1402,6 +1430,9 @@ class _EvalPlan:
                    ("a post-processor that is not this package's", not own_post),
                    ("a criterion without targets_static", not hasattr(criterion, "targets_static")))
         why = next((text for text, holds in reasons if holds), None)               # the first that holds, in this order
+        if why is not None and raw:
+            raise NotImplementedError(f"evaluate_raw is not available with {why}: a raw batch is staged into the canvas's buffers and "
+                                      "scored inside the captured graph, there is no other path for it")
         if why is not None:
             _say_once(model, ("eval-canvas", why), f"[reftr_amd] evaluate: {canvas!r} is ignored ({why}); every batch runs at its own shape")
         self.on_canvas = why is None
@@ -1515,6 +1546,7 @@ class _OwnShapeEval:
         outputs, names, vec = self.losses(samples, targets)
         self.book(names, vec)
         self.score(outputs, targets, _stacked_sizes(targets, original=True))
+        return outputs
 
     def dump_visuals(self, outputs, targets, results, results_scaled):
         if self.vis is not None:
@@ -1591,25 +1623,66 @@ class _CanvasEval:
     """A batch that fits `canvas` (why_not, why_not_eval) runs as one replay of one captured graph (CapturedEvalStep; one capture per
     canvas key) with no device-to-host copy: totals and boxes stay on the device, in the wrapped _MeteredEval's accumulators and a results
     ring per key, read back once in finish().  A batch that does not fit goes to that path at its own shape (said once per reason).  A
-    replay whose hand-off timed out was vetoed on the device: every capture goes, the rings stay, the batch is replayed once more."""
+    replay whose hand-off timed out was vetoed on the device: every capture goes, the rings stay, the batch is replayed once more.
+
+    The fit test follows the form of the batch.  A RAW batch (evaluate_raw) is asked why_not and why_not_eval_raw; one that does not fit
+    is converted once by the existing device chain (BatchCanvas.resized_eval) and goes to the same own-shape path, and with a 'segm'
+    post-processor its original-frame mask totals are added by the same two ABI calls, eagerly (_orig_own_shape).  `host_ids`: the
+    coming raw batch's image ids as python ints where the loader delivered them in host memory (set by evaluate_raw per batch)."""
 
     def __init__(self, model, criterion, postprocessors, canvas, slots, own_shape):
         assert isinstance(own_shape, _MeteredEval)           # its meter, loader order and `book` are this path's too
         self.model, self.canvas, self.slots, self.capture_args = model, canvas, slots, (model, criterion, postprocessors, canvas)
         self.own_shape, self.meter, self.order, self.segm = own_shape, own_shape.meter, own_shape.order, "segm" in postprocessors
         self.steps, self.rings = {}, {}      # by canvas key: the capture; (the ring's device state, its batches as replayed, decoded)
+        self.post, self.host_ids, self._keep_orig = postprocessors, None, None
         self.meter.reset(fresh=False)
 
     def _replay(self, key, samples, targets):
         step = self.steps.get(key)
         if step is None:
             state = self.rings[key][0] if key in self.rings else None
-            step = self.steps[key] = CapturedEvalStep(*self.capture_args, samples, targets, self.meter.acc, self.slots, state=state)
+            step = self.steps[key] = CapturedEvalStep(*self.capture_args, samples, targets, self.meter.acc, self.slots, state=state,
+                                                      acc_orig=self.meter.acc_orig, host_ids=self.host_ids)
             self.rings.setdefault(key, (step.state, [], []))
-        return step(samples, targets)
+        return step(samples, targets, self.host_ids) if step.raw else step(samples, targets)
+
+    def _orig_own_shape(self, outputs, frame_hw, samples, targets):
+        """The original-frame mask totals of a raw batch that ran at its own shape: rt_eval_raw_facts + rt_eval_orig, eagerly, with
+        the batch's own padded size as the frame and its largest image as max_pixels.  An image whose target mask does not have its
+        size cannot be scored on its frame: its table entry is zeroed and it contributes nothing."""
+        pm = outputs["pred_masks"]
+        pm = (pm.squeeze(2) if pm.dim() == 5 else pm).to(torch.float32).contiguous()
+        img, n, keep = samples["img"], H.BATCH_STAGE_MAX_B, []
+        for b0 in range(0, len(img), n):                     # (a batch of more than RT_BATCH_STAGE_MAX_B images: in slices)
+            ims, sizes, tg = img.images[b0:b0 + n], img.out_sizes()[b0:b0 + n], targets[b0:b0 + n]
+            origs = [(int(im.shape[0]), int(im.shape[1])) for im in ims]
+            tm = [t.get("masks") for t in tg]
+            ok = [m is not None and m.dim() == 3 and m.shape[0] == 1 and tuple(m.shape[-2:]) == o for m, o in zip(tm, origs)]
+            masks = [(m if m.element_size() == 1 else m.float() > 0.5).contiguous() if k
+                     else torch.zeros(o, dtype=torch.uint8, device=pm.device) for m, o, k in zip(tm, origs, ok)]
+            st = H.EvalOrigState(len(ims), max(h * w for h, w in origs), pm.device, acc=self.meter.acc_orig)
+            facts = torch.zeros((len(ims), 6), dtype=torch.int32, device=pm.device)
+            H.eval_raw_facts(sizes, origs, frame_hw, facts, torch.zeros(len(ims), dtype=torch.int64, device=pm.device), mask_list=masks,
+                             mask_table=st.mask_table, max_pixels=st.max_pixels)
+            if not all(ok):
+                st.mask_table.mul_(torch.tensor([int(k) for k in ok], dtype=torch.int64).to(pm.device, non_blocking=True))
+            H.eval_orig(pm[b0:b0 + n].contiguous(), facts, st, frame_hw, threshold=self.post["segm"].threshold)
+            keep.append((st, facts, masks))
+        self._keep_orig = (keep, pm)                         # alive until the next such batch
 
     def __call__(self, batch_no, samples, targets):
-        why = self.canvas.why_not(samples, targets) or self.canvas.why_not_eval(samples, targets, segm=self.segm)
+        raw = _is_raw(samples)
+        why = self.canvas.why_not(samples, targets) or (self.canvas.why_not_eval_raw(samples, targets, segm=self.segm) if raw else
+                                                        self.canvas.why_not_eval(samples, targets, segm=self.segm))
+        if why is not None and raw:
+            _say_once(self.model, ("eval-canvas", why), f"[reftr_amd] evaluate_raw: a raw batch does not fit {self.canvas!r} ({why}): "
+                      "it is resized by the DeviceInputPipeline chain and runs at its own shape")
+            ns, nt = self.canvas.resized_eval(samples, targets)
+            outputs = self.own_shape(batch_no, ns, nt)
+            if self.segm:
+                self._orig_own_shape(outputs, tuple(ns["img"].tensors.shape[-2:]), samples, targets)
+            return None
         if why is not None:
             _say_once(self.model, ("eval-canvas", why), f"[reftr_amd] evaluate: a batch does not fit {self.canvas!r} ({why}): it runs at "
                       "its own shape")
@@ -1651,7 +1724,8 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     for batch_no in board.log_every(range(len(data_loader)), 50, "Test:"):
         if _is_raw(samples):
             raise NotImplementedError("evaluate: a raw batch (reftr_amd.data.RawImages) is not taken: the metric tail reads the resized "
-                                      "`size` of every image from device memory (rt_eval_facts), which a raw batch has on the host only")
+                                      "`size` of every image from device memory (rt_eval_facts), which a raw batch has on the host only; "
+                                      "evaluate_raw takes it")
         path(batch_no, samples, targets)
         samples, targets = prefetcher.next()
     _check_cooperative(model)
@@ -1659,3 +1733,69 @@ def evaluate(model, criterion, postprocessors, data_loader, device, output_dir=N
     stats, results_dict = board.global_avg(), {}
     path.finish(stats, results_dict)
     return {k: v for k, v in stats.items() if k.split("_")[-1] not in ("unscaled", "0", "1", "2")}, results_dict      # engine_vg.py:221
+
+
+@torch.no_grad()
+def evaluate_raw(model, criterion, postprocessors, data_loader, device, canvas, output_dir=None):
+    """evaluate() for a loader of RAW batches (reftr_amd.data.raw: samples["img"] a RawImages on the host or the device, targets in the
+    raw frame -- `boxes` xyxy pixels, with a 'segm' post-processor a one-byte [1, h, w] `masks` of the image's own size, `image_id` one
+    int64 on all targets or on none; `size` and `orig_size` are not read, they are RawImages.out_sizes() and the raw (h, w)).
+    -> (stats, results_dict).
+
+    The existing keys and results_dict are what evaluate(canvas=canvas) returns on the batches converted by BatchCanvas.resized_eval
+    (the DeviceInputPipeline chain, `size` / `orig_size` / `image_id` as tensors).  With a 'segm' post-processor the stats also carry
+    'seg_miou_orig', 'seg_oiou_orig' and 'seg_prec@0.5_orig' ... '@0.9_orig': metrics.stats_from_orig_accumulators over integer {I, U}
+    counted on the raw h x w frame, query 0's masks_origin (Predictor's mask: the canvas as the frame) against the raw mask bytes.
+    Per fitting batch the host issues rt_raw_stage, rt_eval_raw_facts, the grouped token copy and ONE replay of the one graph per
+    canvas key; a batch that does not fit (why_not, why_not_eval_raw) is converted once and runs at its own shape, said once per
+    reason, adding to the same totals.  Refused before anything is launched: more than one rank, the data-parallel wrapper, a CPU
+    device, foreign post-processors, a criterion without targets_static, REFTR_EVAL_GRAPH=0 / REFTR_EVAL_METRICS=0 (a raw batch has
+    nowhere else to go); a batch that is not raw raises TypeError.  The model's and the criterion's train / eval mode and the
+    criterion's targets_static are restored on exit."""
+    import itertools
+    if canvas is None:
+        raise NotImplementedError("evaluate_raw needs a canvas: rt_raw_stage writes a raw batch into a canvas's buffers")
+    _canvas_single_process(model)
+    plan = _EvalPlan(model, criterion, postprocessors, device, False, canvas, raw=True)
+    assert plan.on_canvas and plan.metered
+    loader = iter(data_loader)
+    first = next(loader, None)
+    if first is not None and not _is_raw(first[0]):          # (before anything touches the device)
+        raise TypeError("evaluate_raw takes raw batches: samples['img'] must be a reftr_amd.data.RawImages, not "
+                        f"{type(first[0].get('img') if isinstance(first[0], dict) else first[0]).__name__}")
+    modes = (model.training, criterion.training)
+    static = (criterion.targets_static, getattr(criterion, "target_masks_static", None))
+    model.eval()
+    criterion.eval()
+    try:
+        criterion.targets_static = None                      # (a batch at its own shape reads its targets from the list)
+        if hasattr(criterion, "target_masks_static"):
+            criterion.target_masks_static = None
+        board = utils.StatBoard()
+        own_shape = _MeteredEval(model, criterion, postprocessors, device, plan.replayed, None, board.add_device)
+        path = _CanvasEval(model, criterion, postprocessors, canvas, len(data_loader), own_shape)
+        if "segm" in postprocessors:
+            path.meter.book_orig()
+        batches = itertools.chain([first] if first is not None else [], loader)
+        for batch_no in board.log_every(range(len(data_loader)), 50, "Test:"):
+            samples, targets = next(batches)
+            if not _is_raw(samples):
+                raise TypeError(f"evaluate_raw takes raw batches: batch {batch_no} has no reftr_amd.data.RawImages")
+            ids = [t.get("image_id") for t in targets]
+            # ids the loader left in host memory travel by value (free to read here); ids on the device are gathered there
+            path.host_ids = ([int(v) for v in ids] if ids and all(torch.is_tensor(v) and not v.is_cuda and v.numel() == 1 for v in ids)
+                             else None)
+            if not _on_device(samples):                      # a host batch: the raw bytes cross, everything else happens on the device
+                samples, targets = _to_device(samples, targets, device)
+            path(batch_no, samples, targets)
+        _check_cooperative(model)
+        board.synchronize_between_processes()
+        stats, results_dict = board.global_avg(), {}
+        path.finish(stats, results_dict)
+    finally:
+        model.train(modes[0])
+        criterion.train(modes[1])
+        criterion.targets_static = static[0]
+        if hasattr(criterion, "target_masks_static"):
+            criterion.target_masks_static = static[1]
+    return {k: v for k, v in stats.items() if k.split("_")[-1] not in ("unscaled", "0", "1", "2")}, results_dict

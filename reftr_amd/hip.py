@@ -28,6 +28,8 @@ CONSTANTS = {
     # rt_eval_metrics: accumulator slots (8 bytes each: int64 but for the two double sums) and the mask kernel's pixels per workgroup
     "RT_EVAL_DET_N": 0, "RT_EVAL_DET_HIT": 1, "RT_EVAL_SEG_N": 6, "RT_EVAL_SEG_HIT": 7, "RT_EVAL_SEG_I": 12, "RT_EVAL_SEG_U": 13,
     "RT_EVAL_DET_SUM": 14, "RT_EVAL_SEG_SUM": 15, "RT_EVAL_SLOTS": 16, "RT_EVAL_CHUNK": 16384,
+    # rt_eval_orig: its own accumulator slots (int64 but for the double sum)
+    "RT_EVAL_ORIG_N": 0, "RT_EVAL_ORIG_HIT": 1, "RT_EVAL_ORIG_I": 6, "RT_EVAL_ORIG_U": 7, "RT_EVAL_ORIG_SUM": 8, "RT_EVAL_ORIG_SLOTS": 9,
     "RT_PREDICT_FACTS_WORDS": 8,         # int32 words per image of rt_predict_facts' table
     "RT_DEC_MAX_LAYERS": 8, "RT_DEC_HANDOFF_BYTES": 256 + 16 * 256 * 36 + 16 * 2048 * 4,
 }
@@ -255,6 +257,20 @@ class EvalCanvasArgs(_Abi, c="rt_eval_canvas_args"):
                 ("Wc", c_int32), ("tgt_rows", c_int32), ("slots", c_int32), ("threshold", c_float)]
 
 
+class EvalRawFactsArgs(_Abi, c="rt_eval_raw_facts_args"):
+    _N = CONSTANTS["RT_BATCH_STAGE_MAX_B"]
+    _fields_ = [("facts", c_void_p), ("image_ids", c_void_p), ("mask_table", c_void_p), ("max_pixels", c_int64),
+                ("B", c_int32), ("Hc", c_int32), ("Wc", c_int32), ("has_ids", c_int32),
+                ("img_h", c_int32 * _N), ("img_w", c_int32 * _N), ("orig_h", c_int32 * _N), ("orig_w", c_int32 * _N),
+                ("image_id", c_int64 * _N), ("tm_ptr", c_void_p * _N)]
+
+
+class EvalOrigArgs(_Abi, c="rt_eval_orig_args"):
+    _fields_ = [("pred_masks", c_void_p), ("facts", c_void_p), ("mask_table", c_void_p), ("partials", c_void_p), ("iou_seg", c_void_p),
+                ("iu", c_void_p), ("acc", c_void_p), ("veto", c_void_p), ("max_pixels", c_int64),
+                ("B", c_int32), ("Q", c_int32), ("h", c_int32), ("w", c_int32), ("Hc", c_int32), ("Wc", c_int32), ("threshold", c_float)]
+
+
 class PredictFactsArgs(_Abi, c="rt_predict_facts_args"):
     _N = CONSTANTS["RT_BATCH_STAGE_MAX_B"]
     _fields_ = [("facts", c_void_p), ("capacity", c_int64), ("B", c_int32), ("Q", c_int32), ("Hc", c_int32), ("Wc", c_int32),
@@ -378,6 +394,8 @@ _SIGNATURES = {
     "rt_eval_facts": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int, c_void_p,
                               c_void_p, c_void_p]),
     "rt_eval_canvas": (c_int, [POINTER(EvalCanvasArgs), c_void_p]),
+    "rt_eval_raw_facts": (c_int, [POINTER(EvalRawFactsArgs), c_void_p]),
+    "rt_eval_orig": (c_int, [POINTER(EvalOrigArgs), c_void_p]),
     "rt_predict_facts": (c_int, [POINTER(PredictFactsArgs), c_void_p]),
     "rt_predict_canvas": (c_int, [POINTER(PredictCanvasArgs), c_void_p]),
     "rt_small_dgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -1341,6 +1359,66 @@ def eval_canvas(pred_boxes, valid_u8, tgt_boxes, tgt_off, facts, image_ids, stat
         veto=veto, B=B, P=P, K=K, Q=Q, h=h, w=w, Hc=Hc, Wc=Wc, tgt_rows=int(tgt_boxes.shape[0]), slots=state.slots,
         threshold=float(threshold)))
     return iou_det, iou_seg, iu
+
+
+def eval_orig_chunks(max_pixels):
+    """The chunks per image of rt_eval_orig's grid and partials: ceil(max_pixels / EVAL_CHUNK)."""
+    return max(1, -(-int(max_pixels) // EVAL_CHUNK))
+
+
+class EvalOrigState:
+    """What rt_eval_orig reads and writes beside the model's logits, for batches of B images of at most `max_pixels` original pixels:
+    mask_table int64 [B] (rt_eval_raw_facts writes it), partials int32 [B, eval_orig_chunks(max_pixels), 2], iou_seg fp32 [B], iu int64
+    [B, 2].  `acc` (int64 [EVAL_ORIG_SLOTS], slot EVAL_ORIG_SUM holds a double) is handed in or made here, zeroed once by the caller."""
+
+    def __init__(self, B, max_pixels, device, acc=None):
+        self.B, self.max_pixels = int(B), int(max_pixels)
+        self.acc = torch.zeros(EVAL_ORIG_SLOTS, dtype=torch.int64, device=device) if acc is None else acc
+        self.mask_table = torch.zeros(self.B, dtype=torch.int64, device=device)
+        self.partials = torch.zeros((self.B, eval_orig_chunks(self.max_pixels), 2), dtype=torch.int32, device=device)
+        self.iou_seg = torch.zeros(self.B, dtype=torch.float32, device=device)
+        self.iu = torch.zeros((self.B, 2), dtype=torch.int64, device=device)
+
+
+def eval_raw_facts(sizes, origs, canvas_hw, facts, image_ids, ids=None, mask_list=None, mask_table=None, max_pixels=0):
+    """rt_eval_raw_facts: sizes / origs: B (h, w) pairs of python ints (resized, raw), canvas_hw = (Hc, Wc), ids: B python ints (None:
+    -1) -> facts int32 [B, 6] (rt_eval_facts' layout, the mask extent = the resized size), image_ids int64 [B]; with mask_list (B
+    one-byte raw masks on the device, image b's of orig_h * orig_w bytes) also mask_table int64 [B] = their addresses, for rt_eval_orig
+    with a grid sized for `max_pixels`.  Every value goes by value in the kernel arguments: nothing is copied to the device and
+    nothing synchronises.  The caller keeps the masks alive until the kernels that read the table have run."""
+    B, n = len(sizes), BATCH_STAGE_MAX_B
+    _req(facts, torch.int32, "facts"); _req(image_ids, torch.int64, "image_ids"); _req(mask_table, torch.int64, "mask_table")
+    assert 0 < B <= n and len(origs) == B and facts.numel() == 6 * B and image_ids.numel() == B and facts.is_contiguous()
+    assert ids is None or len(ids) == B
+    tm = (c_void_p * n)()
+    if mask_table is not None:
+        assert mask_list is not None and len(mask_list) == B and mask_table.numel() == B
+        for t, (oh, ow) in zip(mask_list, origs):
+            assert t.is_cuda and t.element_size() == 1 and t.is_contiguous() and t.numel() == int(oh) * int(ow), (t.dtype, tuple(t.shape))
+        tm = (c_void_p * n)(*[t.data_ptr() for t in mask_list])
+    _call("rt_eval_raw_facts", _desc(
+        EvalRawFactsArgs, facts=facts, image_ids=image_ids, mask_table=mask_table, max_pixels=int(max_pixels), B=B,
+        Hc=int(canvas_hw[0]), Wc=int(canvas_hw[1]), has_ids=0 if ids is None else 1,
+        img_h=(c_int32 * n)(*[int(s[0]) for s in sizes]), img_w=(c_int32 * n)(*[int(s[1]) for s in sizes]),
+        orig_h=(c_int32 * n)(*[int(s[0]) for s in origs]), orig_w=(c_int32 * n)(*[int(s[1]) for s in origs]),
+        image_id=(c_int64 * n)(*([int(v) for v in ids] if ids is not None else [])), tm_ptr=tm))
+
+
+def eval_orig(pred_masks, facts, state, canvas_hw, threshold=0.5, veto=None):
+    """rt_eval_orig for one batch: pred_masks fp32 [B, Q, h, w] (query 0 of every image is scored), facts / state.mask_table what
+    eval_raw_facts wrote, state an EvalOrigState (accumulators updated in place), canvas_hw = (Hc, Wc) the frame of the mask decision.
+    veto: device int32 word; non-zero at run time -> the accumulators stay as they were.  Two launches, device memory only: it can be
+    captured and replayed.  Returns (iou_seg fp32 [B], iu int64 [B, 2]) of this batch, views of the state."""
+    _req(pred_masks, torch.float32, "pred_masks"); _req(facts, torch.int32, "facts"); _req(veto, torch.int32, "veto")
+    assert pred_masks.dim() == 4 and pred_masks.is_contiguous() and facts.is_contiguous()
+    B, Q, h, w = (int(v) for v in pred_masks.shape)
+    assert state.B == B and facts.numel() == 6 * B and state.acc.numel() == EVAL_ORIG_SLOTS and state.acc.dtype == torch.int64
+    assert state.partials.numel() == B * eval_orig_chunks(state.max_pixels) * 2
+    _call("rt_eval_orig", _desc(
+        EvalOrigArgs, pred_masks=pred_masks, facts=facts, mask_table=state.mask_table, partials=state.partials, iou_seg=state.iou_seg,
+        iu=state.iu, acc=state.acc, veto=veto, max_pixels=state.max_pixels, B=B, Q=Q, h=h, w=w, Hc=int(canvas_hw[0]), Wc=int(canvas_hw[1]),
+        threshold=float(threshold)))
+    return state.iou_seg, state.iu
 
 
 def predict_layout(Q, origs):

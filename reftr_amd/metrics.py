@@ -70,6 +70,20 @@ def stats_from_accumulators(slots, seg=False, world=1, local_seg_n=0):
     return stats
 
 
+def stats_from_orig_accumulators(slots):
+    """The original-frame mask statistics from the RT_EVAL_ORIG_SLOTS accumulator values (python ints, the sum a python float), summed
+    over the ranks: stats_from_accumulators' mask formulas applied to counts taken on the raw frame against the raw annotation
+    (rt_eval_orig).  'seg_miou_orig' = the double sum of the fp32 IoUs / the sample count, 'seg_oiou_orig' = total intersection /
+    total union (NaN without a union), 'seg_prec@t_orig' = hits / the sample count; the count is clamped to 1.  Pure host arithmetic."""
+    n = max(int(slots[H.EVAL_ORIG_N]), 1)
+    union = int(slots[H.EVAL_ORIG_U])
+    stats = {"seg_miou_orig": float(slots[H.EVAL_ORIG_SUM]) / n,
+             "seg_oiou_orig": int(slots[H.EVAL_ORIG_I]) / union if union else float("nan")}
+    for t, thr in enumerate(THRESHOLDS):
+        stats[f"seg_prec@{thr}_orig"] = int(slots[H.EVAL_ORIG_HIT + t]) / n
+    return stats
+
+
 def decode_ring(boxes, counts, ids, cursor, overflow, batches):
     """The results ring of rt_eval_canvas, read back once after an evaluation, as one results dict per slot (the caller merges them
     in loader order).  Pure host work on numpy arrays:
@@ -103,15 +117,19 @@ class EvalMeter:
         """seg: whether compute() reports the mask keys; None: iff an update scored masks."""
         self.device = torch.device(device)
         self._seg = seg
-        self.acc = torch.zeros(H.EVAL_SLOTS, dtype=torch.int64, device=self.device)
+        # one block, so that both sets of totals are zeroed by one launch and leave in one copy: `acc` (rt_eval_metrics /
+        # rt_eval_canvas) and behind it `acc_orig`, the original-frame mask totals of a raw evaluation (rt_eval_orig)
+        self._block = torch.zeros(H.EVAL_SLOTS + H.EVAL_ORIG_SLOTS, dtype=torch.int64, device=self.device)
+        self.acc, self.acc_orig = self._block[:H.EVAL_SLOTS], self._block[H.EVAL_SLOTS:]
         self.reset()
 
     def reset(self, fresh=True):
         """Zeroes the accumulators now.  fresh: the next update also starts them from zero inside its own launch; False for a loop in
         which another producer (engine_vg.CapturedEvalStep: rt_eval_canvas inside a replayed graph) adds to `acc` beside update()."""
-        self.acc.zero_()
+        self._block.zero_()
         self._fresh = fresh
         self.seg = bool(self._seg)
+        self.orig = False
         self.local_seg_n = 0
         self.last = None
         self._keep = None
@@ -121,6 +139,10 @@ class EvalMeter:
         if seg:
             self.seg = True if self._seg is None else self.seg
             self.local_seg_n += int(n_images)
+
+    def book_orig(self):
+        """Books that a producer adds to `acc_orig`: compute() reports the '_orig' keys."""
+        self.orig = True
 
     @torch.no_grad()
     def update(self, outputs, targets, masks=None, sizes=None):
@@ -147,13 +169,18 @@ class EvalMeter:
 
     @torch.no_grad()
     def compute(self, world_reduce=True):
-        acc = self.acc
+        block = self._block
         world = 1
         if world_reduce and utils.is_dist_avail_and_initialized():
             world = utils.get_world_size()
-            acc = acc.clone()
-            torch.distributed.all_reduce(acc[:H.EVAL_DET_SUM])                           # the int64 counts
-            torch.distributed.all_reduce(acc[H.EVAL_DET_SUM:].view(torch.float64))       # the two double sums
-        host = acc.cpu()                                                     # the ONE device-to-host copy
-        slots = host[:H.EVAL_DET_SUM].tolist() + host[H.EVAL_DET_SUM:].view(torch.float64).tolist()
-        return stats_from_accumulators(slots, seg=self.seg, world=world, local_seg_n=self.local_seg_n)
+            block = block.clone()
+            torch.distributed.all_reduce(block[:H.EVAL_DET_SUM])                                     # the int64 counts
+            torch.distributed.all_reduce(block[H.EVAL_DET_SUM:H.EVAL_SLOTS].view(torch.float64))     # the two double sums
+            # (acc_orig is not reduced: a raw evaluation runs on one rank)
+        host = block.cpu()                                                   # the ONE device-to-host copy
+        acc, orig = host[:H.EVAL_SLOTS], host[H.EVAL_SLOTS:]
+        slots = acc[:H.EVAL_DET_SUM].tolist() + acc[H.EVAL_DET_SUM:].view(torch.float64).tolist()
+        stats = stats_from_accumulators(slots, seg=self.seg, world=world, local_seg_n=self.local_seg_n)
+        if self.orig:
+            stats.update(stats_from_orig_accumulators(orig[:H.EVAL_ORIG_SUM].tolist() + orig[H.EVAL_ORIG_SUM:].view(torch.float64).tolist()))
+        return stats
