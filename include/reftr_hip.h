@@ -742,6 +742,36 @@ int rt_raw_stage(const rt_raw_stage_args* a, rt_stream_t stream);
 int rt_resample_taps(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize, rt_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * rt_hsv_jitter — the reference's RandomIntensitySaturation (datasets/transforms.py:266-285) on a batch of RAW images, in front of
+ * rt_raw_stage, ONE launch: per image b, dst[b] = the 8-bit RGB -> HSV -> gains -> RGB round trip of src[b] (uint8 [h[b]][w[b]][3]),
+ * the bytes of reftr_amd/data/jitter.py `apply`, bit for bit.  That module is the definition (OpenCV's scalar 8-bit paths restated
+ * operation for operation; not pinned against a cv2 build):
+ *   RGB -> HSV in integers, hsv_shift = 12: v = max, d = v - min, s = (d * sdiv[v] + 2048) >> 12, h = (h0 * hdiv[d] + 2048) >> 12
+ *     (arithmetic shift; + 180 when negative; H in [0, 180)), sdiv[i] = rint((255 << 12) / (1.0 * i)), hdiv[i] = rint((180 << 12) /
+ *     (6.0 * i)) in double, round half to even, both 0 at i = 0 -- the two tables are computed in the kernel, into LDS;
+ *   gains: y = (float)x * gain, clipped to [0, 255] only when gain > 1, x' = (uint8)(int)y -- S with s_gain[b], V with v_gain[b]
+ *     (the reference never scales S: its gain is 1; a gain of exactly 1 keeps the byte);
+ *   HSV -> RGB in fp32 with NO fused multiply-add: hf = h * (6.f / 180.f), sf = s' * (1.f / 255.f), vf = v' * (1.f / 255.f), the four
+ *     products {vf, vf * (1 - sf), vf * (1 - sf * f), vf * (1 - sf * (1 - f))} chosen by the sector, each channel
+ *     clamp(rintf(c * 255.f), 0, 255), round half to even.
+ * The round trip alone moves bytes: gains (1, 1) are not the identity.
+ * Every per-image fact (HOST values) rides by value in the kernel's argument block, as rt_raw_stage's do.  An image is a flat run of
+ * h * w pixels and a thread takes 16 consecutive ones (48 bytes): three 16-byte loads and three 16-byte stores where the unit lies
+ * wholly inside the image and src[b] and dst[b] are 16-byte aligned, byte accesses otherwise; no byte at or behind 3 * h * w of an
+ * image is read or written.  dst[b] == src[b] is allowed (a thread reads its unit before it writes it), a partial overlap is not.
+ * No atomics: the same bits from run to run.  Nothing is launched on an error: RT_ERR_UNSUPPORTED for B > RT_BATCH_STAGE_MAX_B or
+ * 3 * h * w >= 2^31; RT_ERR_BADARG for a NULL pointer, B <= 0, a non-positive size, a gain that is negative, NaN or infinite.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct rt_hsv_jitter_args {
+    int32_t B;
+    const uint8_t* src[RT_BATCH_STAGE_MAX_B];   /* [h][w][3] */
+    uint8_t*       dst[RT_BATCH_STAGE_MAX_B];   /* [h][w][3]; dst[b] == src[b] allowed, partial overlap not */
+    int32_t h[RT_BATCH_STAGE_MAX_B], w[RT_BATCH_STAGE_MAX_B];
+    float   s_gain[RT_BATCH_STAGE_MAX_B], v_gain[RT_BATCH_STAGE_MAX_B];
+} rt_hsv_jitter_args;
+int rt_hsv_jitter(const rt_hsv_jitter_args* a, rt_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * rt_cem_fwd / rt_cem_bwd — the CEM block of RefTRSeg (--ablation cem_loss, models/reftr_segmentation.py:16-41) for the one
  * query per image of RES: u_b = c3(hs_b) (hs bf16 [B, E] = last decoder output, w3 [16, E], b3 [16]), res bf16 [B*HW, ld] =
  * MaskHeadSmallConv's last feature map (16 channels in front of the padding), a_p = res_p . w2 + b2,

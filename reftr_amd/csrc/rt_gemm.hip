@@ -487,6 +487,8 @@ extern "C" int rt_conv_gemm_grouped(const rt_conv_gemm_desc* descs, int n, rt_st
     return RT_OK;
 }
 
+// 39 also with rt_hsv_jitter: a new entry point changes no existing signature (rt_predict_*, rt_eval_raw_facts and rt_eval_orig kept the
+// number the same way), and three test files pin it
 extern "C" int rt_abi_version(void) { return 39; }
 
 extern "C" int rt_device_arch(int dev, char* buf, int buflen) {

@@ -13,7 +13,9 @@ stay where they are, which is what a captured step needs.  Opt-in: engine_vg's e
 
 A RAW batch (reftr_amd.data.raw: `samples["img"]` a RawImages, targets in the raw frame) is defined the same way: `pad_on_host` runs
 the DeviceInputPipeline chain to the canvas's size and then the padding above; `stage` writes the same bytes with ONE rt_raw_stage
-launch -- resize, ToTensor, Normalize, the target transforms and the padding all happen on the way into the buffers.
+launch -- resize, ToTensor, Normalize, the target transforms and the padding all happen on the way into the buffers.  A raw batch
+that carries gains (RawImages.gains: the reference's RandomIntensitySaturation, reftr_amd.data.jitter) is colour-jittered first, on
+both paths, by one rt_hsv_jitter launch into a scratch; a batch without gains issues the launches it always did.
 """
 import torch
 
@@ -30,10 +32,13 @@ def _token_shapes(samples):
 
 class StagedBatch:
     """The static buffers of one canvas batch: `samples` (the canvas-sized 'img' NestedTensor + the token fields), `targets_static`
-    = (boxes [B * boxes_per_image, 4] fp32, tgt_off [B + 1] int32, num_boxes [1] fp32) and `tgt_masks` (uint8 [B, 1, H, W] or None)."""
+    = (boxes [B * boxes_per_image, 4] fp32, tgt_off [B + 1] int32, num_boxes [1] fp32) and `tgt_masks` (uint8 [B, 1, H, W] or None).
+    `jitter_scratch`: the uint8 bytes rt_hsv_jitter writes and rt_raw_stage reads when a raw batch carries gains (None until one
+    does; it grows when a batch needs more)."""
 
     def __init__(self, samples, targets_static, tgt_masks):
         self.samples, self.targets_static, self.tgt_masks = samples, targets_static, tgt_masks
+        self.jitter_scratch = None
 
 
 class BatchCanvas:
@@ -84,6 +89,8 @@ class BatchCanvas:
     def _why_not_raw(self, img, targets):
         """The image and mask part of why_not for a raw batch."""
         if not img.well_formed():
+            if img.gains is not None and RawImages(img.images, img.size, img.max_size).well_formed():
+                return "gains that are not one finite, non-negative (s_gain, v_gain) pair per image"
             return "a raw image that is not uint8 [h, w, 3]"
         S = H.RAW_STAGE_MAX_SCALE
         for im, (oh, ow) in zip(img.images, img.out_sizes()):
@@ -218,13 +225,17 @@ class BatchCanvas:
     def resized(self, samples, targets, to_canvas=False):
         """A raw batch through the existing device chain (DeviceInputPipeline: rt_resample_u8 per pass and image, rt_img_collate_norm,
         the target transforms in torch): the NestedTensor form of the batch, collated to its own largest image -- or, `to_canvas`,
-        straight to the canvas's size."""
+        straight to the canvas's size.  A batch that carries gains is jittered in front of the chain by rt_hsv_jitter, whose bytes are
+        reftr_amd.data.jitter.apply's."""
         img = samples["img"]
         pkey = (img.size, img.max_size, bool(to_canvas))
         if pkey not in self._pipes:
             self._pipes[pkey] = DeviceInputPipeline(img.size, img.max_size, device=img.device if img.is_cuda else "cuda",
                                                     pad_to=(self.height, self.width) if to_canvas else None)
-        nested, out_t = self._pipes[pkey](img.images, targets)
+        images = img.images
+        if img.gains is not None:                # the colour jitter first, on the raw bytes, into temporaries (rt_hsv_jitter)
+            images = self._jittered(img if img.is_cuda else img.to(self._pipes[pkey].device, non_blocking=True))
+        nested, out_t = self._pipes[pkey](images, targets)
         s = dict(samples)
         s["img"] = nested
         return s, out_t
@@ -298,8 +309,33 @@ class BatchCanvas:
         convert = (lambda m: m.float() > 0.5) if raw else (lambda m: m.to(torch.uint8))
         return [(t["masks"] if t["masks"].element_size() == 1 else convert(t["masks"])).contiguous() for t in targets] if self.masks else None
 
+    @staticmethod
+    def _jittered(img, holder=None):
+        """The images the resize reads: a raw batch's own, contiguous -- or, when it carries gains, their colour-jittered copies
+        (reftr_amd.data.jitter.apply's bytes) written by ONE rt_hsv_jitter launch on the current stream into a uint8 scratch, each image
+        at a 16-byte aligned offset.  The scratch is `holder.jitter_scratch` (a StagedBatch's: kept, and replaced by a larger one when
+        a batch needs more) or a temporary; it is allocated and used under the current stream.  The batch's tensors are never written."""
+        images = [im.contiguous() for im in img.images]
+        if img.gains is None:
+            return images
+        offsets, total = [], 0
+        for im in images:
+            offsets.append(total)
+            total += -(-im.numel() // 16) * 16
+        dev = images[0].device
+        scratch = holder.jitter_scratch if holder is not None else None
+        if scratch is None or scratch.numel() < total or scratch.device != dev:
+            scratch = torch.empty(total, dtype=torch.uint8, device=dev)
+            if holder is not None:
+                holder.jitter_scratch = scratch
+        else:
+            scratch.record_stream(torch.cuda.current_stream(dev))          # (kept from an earlier call: perhaps under another stream)
+        outs = [scratch[o:o + im.numel()].view(im.shape) for o, im in zip(offsets, images)]
+        H.hsv_jitter(images, img.gains, outs)
+        return outs
+
     def _stage_raw(self, img, targets, out):
-        H.raw_stage([im.contiguous() for im in img.images], img.out_sizes(), out.samples["img"].tensors, out.samples["img"].mask,
+        H.raw_stage(self._jittered(img, out), img.out_sizes(), out.samples["img"].tensors, out.samples["img"].mask,
                     self._boxes(targets), self.boxes_per_image, *out.targets_static, MEAN, STD, mask_list=self._masks(targets, True),
                     tgt_masks=out.tgt_masks)
 

@@ -2,8 +2,10 @@
 max_size) -> ToTensor -> Normalize of datasets/refer_resc.py:100-121 / datasets/transforms.py, and the batch padding of
 util/collate_fn.py:24-41, fed from uint8 HWC images (pinned host memory or device).  Output is the `samples['img']`
 NestedTensor and the updated targets (boxes xyxy pixels -> cxcywh normalised, 'size', nearest-resized 'masks') the model
-and the criterion expect.  Stochastic augmentations (RandomIntensitySaturation, cv2 HSV jitter) stay on the host: they
-run before the resize on the raw image."""
+and the criterion expect.  The stochastic augmentation in front of it (RandomIntensitySaturation, the reference's cv2 HSV
+jitter on the raw image) is not this class's: a raw batch carries it as per-image gains (RawImages.gains, defined by
+reftr_amd.data.jitter) and BatchCanvas applies them to the raw bytes with one rt_hsv_jitter launch before the images get
+here; a caller of this class alone passes images that are jittered already, or none."""
 import torch
 
 from .. import hip as H

@@ -236,6 +236,13 @@ def _is_raw(samples):
     return isinstance(samples, dict) and isinstance(samples.get("img"), RawImages)
 
 
+def _no_gains(samples, batch_no):
+    """evaluate_raw's refusal of a raw batch that carries the colour jitter (RawImages.gains), before anything of it is launched."""
+    if samples["img"].gains is not None:
+        raise ValueError(f"evaluate_raw: batch {batch_no} carries gains (RawImages.gains): the colour jitter is a training augmentation, "
+                         "and an evaluation that applied it would silently score other images")
+
+
 def _on_device(samples):
     """Whether the batch's image -- a NestedTensor, or a raw batch's RawImages -- is in device memory."""
     img = samples.get("img")
@@ -1763,7 +1770,9 @@ def evaluate_raw(model, criterion, postprocessors, data_loader, device, canvas, 
     if first is not None and not _is_raw(first[0]):          # (before anything touches the device)
         raise TypeError("evaluate_raw takes raw batches: samples['img'] must be a reftr_amd.data.RawImages, not "
                         f"{type(first[0].get('img') if isinstance(first[0], dict) else first[0]).__name__}")
-    modes = (model.training, criterion.training)
+    if first is not None:
+        _no_gains(first[0], 0)
+    modes =(model.training, criterion.training)
     static = (criterion.targets_static, getattr(criterion, "target_masks_static", None))
     model.eval()
     criterion.eval()
@@ -1781,6 +1790,7 @@ def evaluate_raw(model, criterion, postprocessors, data_loader, device, canvas, 
             samples, targets = next(batches)
             if not _is_raw(samples):
                 raise TypeError(f"evaluate_raw takes raw batches: batch {batch_no} has no reftr_amd.data.RawImages")
+            _no_gains(samples, batch_no)
             ids = [t.get("image_id") for t in targets]
             # ids the loader left in host memory travel by value (free to read here); ids on the device are gathered there
             path.host_ids = ([int(v) for v in ids] if ids and all(torch.is_tensor(v) and not v.is_cuda and v.numel() == 1 for v in ids)

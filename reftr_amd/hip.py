@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libreftr_hip_lab.so" if os.environ.get("REFTR_LAB", "0") == "1" else "libreftr_hip.so")   # _build.py
-ABI_VERSION = 39
+ABI_VERSION = 39          # (stays 39 with rt_hsv_jitter: additive entries -- rt_predict_*, rt_eval_raw_facts / rt_eval_orig -- never bumped it)
 
 # The Python copy of the header's #defines and enumerators (tests/test_abi.py prints each from C and compares) ...
 CONSTANTS = {
@@ -294,6 +294,12 @@ class RawStageArgs(_Abi, c="rt_raw_stage_args"):
                 ("rw", c_float * _N), ("rh", c_float * _N)]
 
 
+class HsvJitterArgs(_Abi, c="rt_hsv_jitter_args"):
+    _N = CONSTANTS["RT_BATCH_STAGE_MAX_B"]
+    _fields_ = [("B", c_int32), ("src", c_void_p * _N), ("dst", c_void_p * _N), ("h", c_int32 * _N), ("w", c_int32 * _N),
+                ("s_gain", c_float * _N), ("v_gain", c_float * _N)]
+
+
 class DecoderLayerFwd(_Abi, c="rt_decoder_layer_fwd"):
     _PTRS = ("Wv", "Wo", "Wq", "Wo2", "W1", "W2", "bv", "bo", "bq", "bo2", "b1", "b2", "g1", "be1", "g2", "be2", "g3", "be3",
              "k2", "v2", "o", "t1q16", "q2", "o2", "t2_16", "hdn", "t3_16", "u", "u2", "u3",
@@ -419,6 +425,7 @@ _SIGNATURES = {
                                c_void_p, c_void_p]),
     "rt_raw_stage": (c_int, [POINTER(RawStageArgs), c_void_p]),
     "rt_resample_taps": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "rt_hsv_jitter": (c_int, [POINTER(HsvJitterArgs), c_void_p]),
     "rt_gn_nhwc_fwd": (c_int, [POINTER(GnNhwcDesc), c_void_p]),
     "rt_gn_nhwc_bwd": (c_int, [POINTER(GnNhwcBwdDesc), c_void_p]),
     "rt_upsample_add": (c_int, [POINTER(UpsampleAddDesc), c_void_p]),
@@ -1912,6 +1919,21 @@ def raw_stage(images, out_sizes, img, mask, box_list, boxes_per_image, boxes, tg
         tm_ptr=(c_void_p * n)(*[t.data_ptr() for t in mask_list]) if mask_list is not None else (c_void_p * n)(),
         h=(c_int32 * n)(*hs), w=(c_int32 * n)(*ws), oh=(c_int32 * n)(*ohs), ow=(c_int32 * n)(*ows),
         rw=(c_float * n)(*[float(o) / float(i) for o, i in zip(ows, ws)]), rh=(c_float * n)(*[float(o) / float(i) for o, i in zip(ohs, hs)])))
+
+
+def hsv_jitter(images, gains, out_list):
+    """rt_hsv_jitter: the colour jitter of reftr_amd.data.jitter.apply on B raw images, one launch.  images: B uint8 [h_b, w_b, 3]
+    device tensors, gains: B (s_gain, v_gain) host floats, out_list: B uint8 device tensors of h_b * w_b * 3 bytes each (out_list[b]
+    may be images[b] itself; any alignment -- 16-byte aligned pairs take the 16-byte accesses).  Every pointer, size and gain goes by
+    value in the kernel arguments: nothing is copied to the device and nothing synchronises."""
+    B, n = len(images), BATCH_STAGE_MAX_B
+    assert 0 < B <= n and len(gains) == B and len(out_list) == B
+    assert all(t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3 for t in images)
+    assert all(o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() and o.numel() == t.numel() for o, t in zip(out_list, images))
+    _call("rt_hsv_jitter", _desc(
+        HsvJitterArgs, B=B, src=(c_void_p * n)(*[t.data_ptr() for t in images]), dst=(c_void_p * n)(*[o.data_ptr() for o in out_list]),
+        h=(c_int32 * n)(*[t.shape[0] for t in images]), w=(c_int32 * n)(*[t.shape[1] for t in images]),
+        s_gain=(c_float * n)(*[float(g[0]) for g in gains]), v_gain=(c_float * n)(*[float(g[1]) for g in gains])))
 
 
 def resample_taps(in_size, out_size, ksize, device="cuda"):

@@ -183,6 +183,9 @@ class Predictor:
         img = samples.get("img")
         if not isinstance(img, RawImages):
             raise TypeError(f"Predictor takes a raw batch: samples['img'] must be a reftr_amd.data.RawImages, not {type(img).__name__}")
+        if img.gains is not None:             # (before anything is launched)
+            raise ValueError("Predictor takes a raw batch without gains: the colour jitter (RawImages.gains) is a training augmentation, "
+                             "and a prediction that applied it would describe another image")
         model = self.model
         was_training = model.training
         model.eval()
